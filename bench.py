@@ -2,7 +2,7 @@
 """SISS unlearning-step benchmark (BASELINE.json metric: unlearning-steps/sec + samples/sec,
 CelebA-HQ 256x256 DDPM, SISS lambd=0.5, bf16, bs=16 per GPU, 1/2/4/8 GPUs).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one optimizer update of delete_celeb.py:557-773 with gradient accumulation 1:
@@ -11,9 +11,15 @@ backward -> (N>1: ONE all-reduce of [g_x ; g_a]) -> norm-fix + clip + AdamW.  In
 (x0 ~ U[-1,1], a0 = one image repeated, noise ~ N(0,1), t = 999, u ~ U[0,1)), resident in HBM
 before the timed region; weights are random-init at the exact google/ddpm-celebahq-256 shapes.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps, writes the last timed step's outputs when
+--dump-outputs is given, and prints the line.  --full adds the secondary legs after the timed steps:
+the eager task-loop step, the device reading under load, per-kernel timing and the roofline, the CPU
+oracle baseline, and for N > 1 the replica self-check and the exchange on its own.
 """
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -47,9 +53,17 @@ def parse():
     ap.add_argument("--stepper-attr", action="append", default=[], help="name=int: set a switch of the stepper (A/B runs)")
     ap.add_argument("--lib-set", action="append", default=[], help="name=int: call a process-wide setter of the library (A/B runs)")
     ap.add_argument("--lib", default=None, help="path of another build of libsiss_hip.so (same-box A/B of a kernel change)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
-    return ap.parse_args()
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU oracle baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="(--full) skip per-kernel timing, roofline and device reading")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the secondary legs: eager task-loop step, device reading under load, "
+                         "per-kernel timing + roofline, CPU oracle baseline; N > 1: replica self-check, exchange timing")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, under 64 MB)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 CPU_MICRO_BATCH = 4          # the CPU oracle walks the B samples of a step in micro-batches of 4 (bounded host memory)
@@ -147,6 +161,44 @@ def hbm_traffic(launcher):
             tot += v["hbm_bytes_per_launch"] * v["launches"]
             n += v["launches"]
     return (round(tot / n) if n else None), src
+
+
+DUMP_BYTES = 60 << 20        # --dump-outputs budget: the sampled parameter / gradient arrays, float32
+
+
+def dump_outputs(d, eng, st, stats):
+    """--dump-outputs: what the last timed step gave its caller, one .npy per array.
+      step_scalars   float64 [4]: norm_loss_x, norm_loss_a, scaling_factor, pre_clip_norm (the line's step_scalars)
+      <row>          float32 [B]: the per-sample rows the step logs (loss_x, loss_a, iw_x, iw_a, ... as the loss has them)
+      params_sample  float32 [n]: the updated parameters, grads_sample float32 [sets, n]: the step's gradient sets
+    The two samples take the same n positions of the parameters in the reference layout (state-dict order and shapes, so that
+    builds with different native layouts compare), drawn from a fixed seed; every position when the model is small enough."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "step_scalars.npy"),
+            np.array([stats[k] for k in ("norm_loss_x", "norm_loss_a", "scaling_factor", "pre_clip_norm")], dtype=np.float64))
+    for k, v in sorted((st.last or {}).items()):
+        if torch.is_tensor(v):
+            np.save(os.path.join(d, k + ".npy"), v.detach().float().cpu().numpy())
+    ps = eng.ps
+    specs = list(ps.specs.values())
+    sizes = torch.tensor([math.prod(sp.ref_shape) for sp in specs], dtype=torch.int64)
+    total = int(sizes.sum())
+    sets = ps.grads.shape[0]
+    n = min(total, DUMP_BYTES // 4 // (1 + sets))
+    if n == total:
+        idx = torch.arange(total)
+    else:
+        idx = torch.randint(0, total, (n,), generator=torch.Generator().manual_seed(0)).sort().values
+    ends = torch.cumsum(sizes, 0)
+    cuts = torch.searchsorted(idx, torch.cat([torch.zeros(1, dtype=torch.int64), ends])).tolist()
+    picks = [(sp, (idx[cuts[i]:cuts[i + 1]] - (ends[i] - sizes[i])).to(ps.flat.device))
+             for i, sp in enumerate(specs) if cuts[i + 1] > cuts[i]]
+
+    def sample(buf):
+        return torch.cat([ps.from_native(sp, buf[sp.off:sp.off + sp.numel]).reshape(-1)[j] for sp, j in picks]).cpu().numpy()
+    np.save(os.path.join(d, "params_sample.npy"), sample(ps.flat))
+    np.save(os.path.join(d, "grads_sample.npy"), np.stack([sample(ps.grads[k]) for k in range(sets)]))
 
 
 def self_launch(a):
@@ -330,11 +382,15 @@ def main():
         dt = float(tt.item())
     ms = dt / a.steps * 1e3
     stats = st.stats()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, eng, st, stats)
+
+    # Everything below up to the result line is a secondary leg of --full: a plain run goes straight to the line.
 
     # ---- the same step as the shipped task loop runs it (siss_amd/tasks.py: eager launches, no hipGraph, and the
     #      device-to-host copy of every optimizer step's scalars that feeds the log line, read one step later) -- secondary figure ----
     eager_ms = None
-    if graph is not None:
+    if a.full and graph is not None:
         sync()
         t0 = time.perf_counter()
         pending = None
@@ -352,14 +408,14 @@ def main():
     #      silicon clocks there is most of the box-to-box spread of `value`.  One rocm-smi reading taken WHILE ~1.5 s
     #      of replays are in flight; absent (None) where the tool or the permission is missing ----
     device_state = None
-    if rank == 0 and world == 1 and graph is not None and not a.no_kernel_timing:
+    if a.full and rank == 0 and world == 1 and graph is not None and not a.no_kernel_timing:
         device_state = _smi_under_load(lambda: [graph.replay() for _ in range(max(8, int(1500 / max(ms, 1.0))))])
         sync()
 
     # ---- N > 1 self-check: every rank must hold bit-identical parameters after the timed steps (the replicated
     #      norm-fix / clip / AdamW only stays in step if the exchange really summed [g_x ; g_a] over all ranks) ----
     selfcheck = None
-    if world > 1:
+    if a.full and world > 1:
         flat = eng.ps.flat
         chk = torch.stack([flat.double().sum(), flat.double().abs().sum(),
                            flat.view(torch.int32).to(torch.int64).sum().double()])
@@ -373,7 +429,7 @@ def main():
 
     # ---- N > 1: the exchange on its own (untimed leg): one all-reduce of the flat [g_x ; g_a] buffer, SURVEY.md §8e ----
     exchange = None
-    if world > 1:
+    if a.full and world > 1:
         from siss_amd.dp import EXCHANGES
         g = eng.ps.grads
         nbytes = g.numel() * g.element_size()
@@ -405,7 +461,8 @@ def main():
     # ---- per-kernel timing of the dominant kernels (eager, HIP events on the launch stream) ----
     roof = None
     kern = {}
-    if not a.no_kernel_timing:
+    kernel_timing = a.full and not a.no_kernel_timing
+    if kernel_timing:
         # every rank runs these steps (the step holds a collective when N>1); only rank 0 records events
         lib.PROF = [] if rank == 0 else None
         ksteps = min(a.steps, 3)
@@ -428,7 +485,7 @@ def main():
             sync()
             prof1, lib.PROF = lib.PROF, None
             eng.wgrad_side, eng.prep_side = saved
-    if not a.no_kernel_timing and rank == 0:
+    if kernel_timing and rank == 0:
         ksym = {}
         hbm = {}
         dom_split = {}
@@ -492,7 +549,7 @@ def main():
                                      for k, v in sorted(ksym.items(), key=lambda kv: -kv[1][1])}}
 
     cpu = None
-    if rank == 0 and not a.no_cpu_baseline and world == 1:
+    if a.full and rank == 0 and not a.no_cpu_baseline and world == 1:
         cfg_kw = {k: getattr(cfg, k) for k in ("sample_size", "in_channels", "out_channels", "block_out_channels",
                                                 "down_block_types", "up_block_types", "layers_per_block",
                                                 "attention_head_dim", "norm_num_groups", "norm_eps",
@@ -514,7 +571,7 @@ def main():
                "steps_per_sec_at_bs%d" % Bc: round(1.0 / cdt, 6),
                "timed_steps_s": [round(x, 2) for x in cdts]}
 
-    if rank == 0 and cpu is None and world > 1:
+    if a.full and rank == 0 and cpu is None and world > 1:
         # N > 1: the CPU baseline is timed at N = 1 only (rank 0, one GPU's workload); a scaling record carries that measurement BY VALUE
         # from the committed N = 1 line of this workload, so that it is self-contained
         try:

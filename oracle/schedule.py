@@ -7,13 +7,21 @@ delete_celeb.py:229 (load), :367-371 (gamma/sigma), :602-603 (add_noise).
 import torch
 
 
+def _sqrt(v):
+    """float32 square root rounded once from float64: torch's float32 CPU sqrt / pow(0.5) can be 1 ulp off the rounded root,
+    differently on different hosts, and the golden vectors pin add_noise bit for bit"""
+    return v.double().sqrt().to(v.dtype)
+
+
 def make_betas(num_train_timesteps=1000, beta_start=1e-4, beta_end=0.02,
                beta_schedule="linear"):
+    # float32 values rounded once from float64: torch's float32 CPU linspace rounds differently with the CPU's
+    # vector ISA (up to 1 ulp), which would make the schedule -- and the golden vectors built on it -- host-dependent
     if beta_schedule == "linear":
-        return torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=torch.float32)
+        return torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=torch.float64).float()
     if beta_schedule == "scaled_linear":
-        return torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps,
-                              dtype=torch.float32) ** 2
+        return (torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps,
+                               dtype=torch.float64) ** 2).float()
     raise ValueError(beta_schedule)
 
 
@@ -23,15 +31,15 @@ def alphas_cumprod(**kw):
 
 def gamma_sigma(ac):
     """delete_celeb.py:367-371: gamma = sqrt(abar), sigma = sqrt(1 - abar)."""
-    return ac ** 0.5, (1 - ac) ** 0.5
+    return _sqrt(ac), _sqrt(1 - ac)
 
 
 def add_noise(ac, x, noise, t):
     """DDPMScheduler.add_noise: alphas_cumprod is cast to the SAMPLE dtype first
     (so in bf16 mode gamma/sigma used for noising come from bf16-rounded abar)."""
     ac = ac.to(device=x.device, dtype=x.dtype)
-    a = ac[t] ** 0.5
-    b = (1 - ac[t]) ** 0.5
+    a = _sqrt(ac[t])
+    b = _sqrt(1 - ac[t])
     a = a.flatten()
     b = b.flatten()
     while a.dim() < x.dim():

@@ -9,11 +9,11 @@ bash tools/pmc_traffic.sh $tag > $out/pmc_traffic.log 2>&1
 cp gpurun_out/${tag}_hbm_traffic.json profiles/latest_hbm_traffic.json
 cp gpurun_out/${tag}_hbm_traffic.json gpurun_out/${tag}_kernel_stats.csv $out/
 echo "[evidence] pmc traffic done" >> $out/progress.txt
-python bench.py --steps 20 --warmup 3 > $out/bench_celeb_bs16.json 2> $out/bench_celeb_bs16.err
+python bench.py --full --steps 20 --warmup 3 > $out/bench_celeb_bs16.json 2> $out/bench_celeb_bs16.err
 echo "[evidence] celeb done" >> $out/progress.txt
-python bench.py --steps 20 --warmup 3 --loss-fn double_forward_with_neg_del --no-cpu-baseline > $out/bench_celeb_bs16_no_is.json 2> /dev/null
-python bench.py --config sd15 --batch 16 --steps 10 --warmup 3 --no-cpu-baseline > $out/bench_sd15_bs16.json 2> /dev/null
-python bench.py --config sd15 --batch 4 --steps 10 --warmup 3 --no-cpu-baseline > $out/bench_sd15_bs4.json 2> /dev/null
+python bench.py --full --steps 20 --warmup 3 --loss-fn double_forward_with_neg_del --no-cpu-baseline > $out/bench_celeb_bs16_no_is.json 2> /dev/null
+python bench.py --full --config sd15 --batch 16 --steps 10 --warmup 3 --no-cpu-baseline > $out/bench_sd15_bs16.json 2> /dev/null
+python bench.py --full --config sd15 --batch 4 --steps 10 --warmup 3 --no-cpu-baseline > $out/bench_sd15_bs4.json 2> /dev/null
 echo "[evidence] bench lines done" >> $out/progress.txt
 python tools/step_breakdown.py --top 200 > $out/step_breakdown_celeb_bs16.txt 2>&1
 python tools/step_breakdown.py --config sd15 --batch 16 --top 200 > $out/step_breakdown_sd15_bs16.txt 2>&1
