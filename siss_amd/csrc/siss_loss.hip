@@ -285,6 +285,80 @@ __global__ __launch_bounds__(kThreads) void ddpm_step_kernel(const float* __rest
     }
 }
 
+// One DDIM step (eta = 0, epsilon prediction) behind classifier-free guidance, fused: the denoising loop body of
+// StableDiffusionPipeline.__call__ with DDIMScheduler.step (reference: data/src/local_sd_pipeline.py:153-200,
+// delete_sd.py:204), in diffusers' order, each product / sum rounded on its own as torch does:
+//   d = e_text - e_uncond;  e = e_uncond + g * d
+//   x0 = (x - sqrt_b * e) * (1 / sqrt_a)      (clamped to +-clip when clip > 0; torch's form of a division by a scalar)
+//   x_prev = sqrt_a_prev * x0 + sqrt_b_prev * e   (the unclipped e: use_clipped_model_output = False)
+// CFG: eps holds 2n rows (uncond first), and each block also writes its partial sums of e_uncond^2 and d^2 to
+// norms[2][n][gridDim.x] (f32; fixed order, no atomics: bitwise reproducible).  !CFG: eps holds n rows, no norms.
+__device__ __forceinline__ float ddim_one(float e, float xv, float inv_sa, float sb, float sap, float sbp, float clip) {
+    // "/ alpha_prod_t ** 0.5": torch divides by a scalar as a product with its f32 reciprocal (inv_sa = 1.f / sqrt_a)
+    float x0 = __fmul_rn(__fsub_rn(xv, __fmul_rn(sb, e)), inv_sa);
+    if (clip > 0.f) x0 = fminf(fmaxf(x0, -clip), clip);
+    return __fadd_rn(__fmul_rn(sap, x0), __fmul_rn(sbp, e));
+}
+
+template <bool CFG, bool VEC>
+__global__ __launch_bounds__(kThreads) void cfg_ddim_kernel(const float* __restrict__ eps, const float* x, float* out, int n,
+                                                            long chw, float g, float sa, float sb, float sap, float sbp,
+                                                            float clip, float* __restrict__ norms) {
+    __shared__ double sh[2 * kThreads / 64];
+    const int s = blockIdx.y;
+    const long base = (long)s * chw;
+    const float* eu = eps + base;
+    const float* et = eps + (long)n * chw + base;            // (read only when CFG)
+    double su = 0, sd = 0;
+    const float inv_sa = 1.f / sa;                            // (IEEE division: no fast-math in this file)
+    auto guide = [&](float u, float t, float& e) {
+        if constexpr (CFG) {
+            const float d = __fsub_rn(t, u);
+            e = __fadd_rn(u, __fmul_rn(g, d));
+            su += (double)u * (double)u;
+            sd += (double)d * (double)d;
+        } else {
+            e = u;
+        }
+    };
+    if constexpr (VEC) {                                      // every row starts 16-B aligned: one f32x4 per lane
+        const long nq = chw / 4;
+        for (long i = (long)blockIdx.x * kThreads + threadIdx.x; i < nq; i += (long)gridDim.x * kThreads) {
+            const f32x4_t u = reinterpret_cast<const f32x4_t*>(eu)[i];
+            const f32x4_t xv = reinterpret_cast<const f32x4_t*>(x + base)[i];
+            f32x4_t t = u, o;
+            if constexpr (CFG) t = reinterpret_cast<const f32x4_t*>(et)[i];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float e;
+                guide(u[j], t[j], e);
+                o[j] = ddim_one(e, xv[j], inv_sa, sb, sap, sbp, clip);
+            }
+            reinterpret_cast<f32x4_t*>(out + base)[i] = o;
+        }
+        if (blockIdx.x == 0) {                                // scalar tail (one row, C*H*W not a multiple of 4)
+            for (long k = nq * 4 + threadIdx.x; k < chw; k += kThreads) {
+                float e;
+                guide(eu[k], CFG ? et[k] : 0.f, e);
+                out[base + k] = ddim_one(e, x[base + k], inv_sa, sb, sap, sbp, clip);
+            }
+        }
+    } else {                                                  // rows not 16-B aligned (odd C*H*W): one element per lane
+        for (long k = (long)blockIdx.x * kThreads + threadIdx.x; k < chw; k += (long)gridDim.x * kThreads) {
+            float e;
+            guide(eu[k], CFG ? et[k] : 0.f, e);
+            out[base + k] = ddim_one(e, x[base + k], inv_sa, sb, sap, sbp, clip);
+        }
+    }
+    if constexpr (CFG) {
+        block_reduce2(su, sd, sh);
+        if (threadIdx.x == 0) {
+            norms[(long)s * gridDim.x + blockIdx.x] = (float)su;
+            norms[((long)n + s) * gridDim.x + blockIdx.x] = (float)sd;
+        }
+    }
+}
+
 inline int blocks_for(long chw) {
     long v = chw / kVec / kThreads;
     if (v < 1) v = 1;
@@ -382,6 +456,27 @@ int siss_ddpm_step(const float* x, const float* eps, const float* noise, float* 
     long nb = (n + kThreads - 1) / kThreads;
     if (nb > 4096) nb = 4096;
     ddpm_step_kernel<<<(int)nb, kThreads, 0, (hipStream_t)stream>>>(x, eps, noise, out, n, sqrt_a, sqrt_b, c_x0, c_xt, sigma, clip);
+    SISS_LAUNCH_RET();
+}
+
+// Classifier-free guidance + DDIM step (eta = 0) over n samples of chw f32 each: eps [2n][chw] (uncond rows first) when
+// guidance > 1, else [n][chw] (no guidance, norms unused); x, out [n][chw] (out may be x).  clip > 0: clamp x0 to +-clip.
+// nblk blocks per sample (1..1024); with guidance, norms[2][n][nblk] receives the per-block partial sums of e_uncond^2 and
+// (e_text - e_uncond)^2 -- the caller sums a sample's nblk partials (fixed order) and takes the square root.
+int siss_cfg_ddim_step(const float* eps, const float* x, float* out, int n, long chw, float guidance, float sqrt_a,
+                       float sqrt_b, float sqrt_a_prev, float sqrt_b_prev, float clip, float* norms, int nblk, void* stream) {
+    const bool cfg = guidance > 1.f;
+    SISS_CHECK_ARG(eps && x && out && n > 0 && n <= 65535 && chw > 0 && sqrt_a > 0.f && nblk >= 1 && nblk <= 1024);
+    SISS_CHECK_ARG(!cfg || norms);
+    // f32x4 lanes when every row starts 16-B aligned (a single row always does; the rest of it is the scalar tail)
+    const bool vec = (chw % 4 == 0 || (n == 1 && !cfg)) && ((uintptr_t)eps | (uintptr_t)x | (uintptr_t)out) % 16 == 0;
+    hipStream_t s = (hipStream_t)stream;
+    dim3 grid(nblk, n);
+    const float a = sqrt_a, b = sqrt_b, ap = sqrt_a_prev, bp = sqrt_b_prev;
+    if (cfg && vec) cfg_ddim_kernel<true, true><<<grid, kThreads, 0, s>>>(eps, x, out, n, chw, guidance, a, b, ap, bp, clip, norms);
+    else if (cfg) cfg_ddim_kernel<true, false><<<grid, kThreads, 0, s>>>(eps, x, out, n, chw, guidance, a, b, ap, bp, clip, norms);
+    else if (vec) cfg_ddim_kernel<false, true><<<grid, kThreads, 0, s>>>(eps, x, out, n, chw, guidance, a, b, ap, bp, clip, nullptr);
+    else cfg_ddim_kernel<false, false><<<grid, kThreads, 0, s>>>(eps, x, out, n, chw, guidance, a, b, ap, bp, clip, nullptr);
     SISS_LAUNCH_RET();
 }
 

@@ -21,6 +21,7 @@ SIGNATURES = {
     "siss_mixture_fwd": [P, P, P, I, P, P, P, P, P, F, I, L, P, P, P, P, P, P, P, P, P],
     "siss_mixture_select": [P, P, P, P, I, P, P, P, P, F, I, L, P, P, P, P, P, P, P, P, P],
     "siss_ddpm_step": [P, P, P, P, L, F, F, F, F, F, I, P],
+    "siss_cfg_ddim_step": [P, P, P, I, L, F, F, F, F, F, F, P, I, P],
     "siss_loss_bwd_seed": [P, P, P, P, I, P, P, P, P, F, I, L, P, P, P, P, P, P, P, P],
     "siss_mse_bwd_seed": [P, P, I, F, I, L, P, P, P, P, P],
     "siss_opt_partials_words": [],
@@ -136,7 +137,7 @@ F32_ENTRY.update({n: n + "_f32" for n in ("siss_gemm_nt_d2s", "siss_gemm_nt_d2s_
                                           "siss_upsample_phase_weights")})
 F32_SAME = {"siss_zero_ranges", "siss_upsample_phase_wgrad_fold", "siss_timestep_sincos", "siss_linear_small_fwd", "siss_linear_small_bwd", "siss_linear_multi_fwd", "siss_linear_multi_bwd",
             "siss_nchw_channel_sums", "siss_mixture_fwd", "siss_mixture_select", "siss_loss_bwd_seed", "siss_mse_bwd_seed",
-            "siss_ddpm_step", "siss_grad_norms_scale", "siss_grad_norm_partials", "siss_grad_scalars", "siss_recombine_clip_adamw"}
+            "siss_ddpm_step", "siss_cfg_ddim_step", "siss_grad_norms_scale", "siss_grad_norm_partials", "siss_grad_scalars", "siss_recombine_clip_adamw"}
 for _b, _f in F32_ENTRY.items():
     SIGNATURES[_f] = SIGNATURES[_b]
 _MODE = threading.local()        # per thread: autograd runs an engine's backward on its own device thread (siss_amd/model.py)

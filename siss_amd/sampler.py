@@ -45,31 +45,38 @@ class Evaluator:
         self.unet, self.noise_scheduler = unet, noise_scheduler
         self._graphs = {}
 
-    def _eps(self, x, t):
-        """eps = UNet(x, t).  The forward is a fixed schedule of ~230 launches whose only per-step inputs are the
-        sample and the timestep, both device tensors: it is captured ONCE per batch shape into a hipGraph and
-        replayed for every denoising step (at batch 1 the eager launch path costs as much as the kernels)."""
+    def _eps(self, x, t, encoder_hidden_states=None):
+        """eps = UNet(x, t[, encoder_hidden_states]).  The forward is a fixed schedule of ~230 launches whose only per-step
+        inputs are the sample, the timestep and (text-conditioned UNet) the prompt embedding, all device tensors: it is
+        captured ONCE per input shape into a hipGraph and replayed for every denoising step (at batch 1 the eager launch
+        path costs as much as the kernels)."""
         eng = self.unet.engine
+        cond = () if encoder_hidden_states is None else (encoder_hidden_states,)
         if not self.use_graph:
             tt = torch.full((x.shape[0],), int(t), dtype=torch.long, device=x.device)
-            return eng.forward(x.contiguous(), tt)
-        key = tuple(x.shape)
+            return eng.forward(x.contiguous(), tt, *cond)
+        key = (tuple(x.shape),) + tuple(tuple(c.shape) for c in cond)
         ent = self._graphs.get(key)
         if ent is None:
             xs = torch.zeros(x.shape, dtype=torch.float32, device=x.device)
             ts = torch.zeros(x.shape[0], dtype=torch.long, device=x.device)
+            cs = tuple(torch.zeros(c.shape, dtype=torch.float32, device=x.device) for c in cond)
+            for c, c_in in zip(cs, cond):
+                c.copy_(c_in)
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                eng.forward(xs, ts)                       # settle every buffer of this shape before the capture
+                eng.forward(xs, ts, *cs)                  # settle every buffer of this shape before the capture
                 graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graph, stream=side):
-                    out = eng.forward(xs, ts)
+                    out = eng.forward(xs, ts, *cs)
             torch.cuda.current_stream().wait_stream(side)
-            ent = self._graphs[key] = (graph, xs, ts, out)
-        graph, xs, ts, out = ent
+            ent = self._graphs[key] = (graph, xs, ts, cs, out)
+        graph, xs, ts, cs, out = ent
         xs.copy_(x)
         ts.fill_(int(t))
+        for c, c_in in zip(cs, cond):
+            c.copy_(c_in)
         graph.replay()
         return out
 

@@ -1,0 +1,148 @@
+"""Stable Diffusion validation sampling on the HIP forward kernels: the reference's ``LocalStableDiffusionPipeline.__call__``
+(data/src/local_sd_pipeline.py:60-215) with ``DDIMScheduler.from_config`` (delete_sd.py:204), as ``log_validation``
+(delete_sd.py:170-340) runs it after every optimizer step.
+
+Per denoising step: ONE replay of the captured text-conditioned UNet forward over the 2n batch (``cat([x, x])``,
+``cat([uncond, text])``) and ONE fused launch (csrc/siss_loss.hip ``siss_cfg_ddim_step``) that applies classifier-free
+guidance and the DDIM update and leaves the step's per-block partial sums of ||eps_uncond||^2 and ||eps_text - eps_uncond||^2
+in a [steps, 2, n, blocks] slab.  The host reads that slab ONCE, after the last step (the reference pays 2n ``.item()``
+syncs per step for the same norms), and sums each sample's partials in f64.  Then the VAE decoder (siss_amd/vae.py) and
+diffusers' postprocess.
+"""
+import contextlib
+import os
+
+import torch
+
+from . import lib
+from .sampler import Evaluator
+from .scheduler import DDIMScheduler
+
+# CLIPTokenizer("") of the SD v1 checkpoints padded to 77: <|startoftext|>, then <|endoftext|> as the pad token
+SD_V1_UNCOND_IDS = [49406] + [49407] * 76
+
+
+def uncond_ids(path=None):
+    """[1, 77] token ids of the empty prompt (diffusers' default negative prompt): the checkpoint's own tokenizer/ when it is
+    on disk, else SD_V1_UNCOND_IDS."""
+    if path and os.path.isdir(os.path.join(str(path), "tokenizer")):
+        from transformers import CLIPTokenizer
+        tok = CLIPTokenizer.from_pretrained(str(path), subfolder="tokenizer")
+        return tok([""], max_length=tok.model_max_length, padding="max_length", truncation=True, return_tensors="pt").input_ids
+    return torch.tensor([SD_V1_UNCOND_IDS], dtype=torch.long)
+
+
+def ddim_blocks(n, chw):
+    """Blocks per sample of siss_cfg_ddim_step: one per 1024 elements (one f32x4 sweep of 256 lanes), the grid capped at
+    2048 blocks (a streaming kernel: cdna_hip_programming.md Guideline 11); the rest is grid-strided."""
+    return max(1, min(-(-chw // 1024), 2048 // n, 1024))
+
+
+def cfg_ddim_step(eps, x, out, coeffs, guidance, clip=0.0, norms=None):
+    """out = DDIM step (eta = 0) of x under eps_uncond + g (eps_text - eps_uncond); eps [2n, ...] when guidance > 1 (the
+    partial sums of the two norms go to `norms`, [2, n, ddim_blocks(n, chw)] f32), else [n, ...].  coeffs:
+    DDIMScheduler.coeffs(t).  out may be x."""
+    n, chw = x.shape[0], x[0].numel()
+    cfg = guidance > 1.0
+    assert x.dtype == eps.dtype == out.dtype == torch.float32 and x.is_contiguous() and eps.is_contiguous() and out.is_contiguous()
+    assert eps.numel() == (2 if cfg else 1) * n * chw and out.shape == x.shape
+    nblk = ddim_blocks(n, chw)
+    if cfg:
+        assert norms is not None and norms.dtype == torch.float32 and norms.is_contiguous() and norms.numel() == 2 * n * nblk
+    lib.call("siss_cfg_ddim_step", eps, x, out, n, chw, float(guidance), *coeffs, float(clip), norms if cfg else None, nblk)
+    return out
+
+
+class SDSampler:
+    """Text-to-image pipeline over the HIP ``UNet2DConditionModel``, ``VAEDecoder`` and ``CLIPTextEncoder``; the call surface of
+    the reference's LocalStableDiffusionPipeline.  ``unconditional_ids``: token ids of the negative (empty) prompt; or pass
+    ``negative_prompt_embeds`` to every call (then no text encoder is needed)."""
+
+    def __init__(self, unet, vae=None, text_encoder=None, scheduler=None, unconditional_ids=None, use_graph=True):
+        self.unet, self.vae, self.text_encoder = unet, vae, text_encoder
+        self.scheduler = scheduler or DDIMScheduler.from_pretrained(None)
+        self.unconditional_ids = torch.tensor([SD_V1_UNCOND_IDS]) if unconditional_ids is None else unconditional_ids
+        self.use_graph = use_graph
+        self._ev, self._hold = None, False
+        self.vae_scale_factor = 2 ** (len(vae.cfg.block_out_channels) - 1) if vae is not None else 8
+
+    @contextlib.contextmanager
+    def holding_graphs(self):
+        """Calls inside the block share their captured forwards (one capture per batch shape for a whole validation pass);
+        they are dropped when it ends.  Outside such a block every call drops its own."""
+        self._hold = True
+        try:
+            yield self
+        finally:
+            self._hold, self._ev = False, None
+
+    def _negative(self, n_prompts):
+        if self.text_encoder is None:
+            raise ValueError("classifier-free guidance needs negative_prompt_embeds or a text encoder for the empty prompt")
+        e = self.text_encoder(self.unconditional_ids.reshape(1, -1))[0].float()
+        return e.expand(n_prompts, *e.shape[1:])
+
+    @torch.no_grad()
+    def __call__(self, prompt_embeds, negative_prompt_embeds=None, num_inference_steps=50, guidance_scale=7.5,
+                 num_images_per_prompt=1, generator=None, latents=None, output_type="pil", track_noise_norm=True,
+                 height=None, width=None, eta=0.0, lp=2):
+        """prompt_embeds [B, L, X].  Returns (images, {"uncond_noise_norm", "text_noise_norm"}): images a list of PIL images
+        ("pil"), a uint8 [n, H, W, 3] array ("np") or the final latents ("latent"); the norms per image and denoising step,
+        in step order (empty without guidance)."""
+        if eta != 0.0:
+            raise NotImplementedError(f"eta={eta}: only the deterministic DDIM step (eta = 0) is implemented")
+        if lp != 2:
+            raise NotImplementedError(f"lp={lp}: only the L2 noise norm is implemented")
+        if output_type not in ("pil", "np", "latent"):
+            raise ValueError(f"output_type={output_type!r}: one of 'pil', 'np', 'latent'")
+        if output_type != "latent" and self.vae is None:
+            raise ValueError(f"output_type={output_type!r} needs a VAE decoder")
+        unet = self.unet
+        dev = unet.device
+        cfg = guidance_scale > 1.0                       # do_classifier_free_guidance (local_sd_pipeline.py:109)
+        text = prompt_embeds.to(dev).float().repeat_interleave(num_images_per_prompt, dim=0)
+        n = text.shape[0]
+        if cfg:
+            neg = self._negative(prompt_embeds.shape[0]) if negative_prompt_embeds is None else negative_prompt_embeds
+            neg = neg.to(dev).float().repeat_interleave(num_images_per_prompt, dim=0)
+            emb = torch.cat([neg, text]).contiguous()    # uncond rows first, as diffusers orders them
+        else:
+            emb = text.contiguous()
+        C, s = unet.config.in_channels, unet.config.sample_size
+        h = (height or s * self.vae_scale_factor) // self.vae_scale_factor
+        w = (width or s * self.vae_scale_factor) // self.vae_scale_factor
+        if latents is None:
+            gdev = generator.device if generator is not None else dev
+            latents = torch.randn((n, C, h, w), generator=generator, device=gdev)
+        x = latents.to(dev).float().contiguous().clone()       # (DDIM: init_noise_sigma = 1)
+        sch = self.scheduler
+        steps = sch.set_timesteps(num_inference_steps)
+        clip = sch.clip_sample_range if sch.clip_sample else 0.0
+        chw = x[0].numel()
+        slab = torch.zeros(len(steps), 2, n, ddim_blocks(n, chw), dtype=torch.float32, device=dev) if cfg else None
+        unet.engine.refresh_weights(cast_shadow=True)
+        if self._ev is None:
+            self._ev = Evaluator(use_graph=self.use_graph)
+            self._ev.load_model(unet, None)
+        try:
+            for i, t in enumerate(steps):
+                eps = self._ev._eps(torch.cat([x, x]) if cfg else x, t, emb)
+                cfg_ddim_step(eps, x, x, sch.coeffs(t), guidance_scale, clip, slab[i] if cfg else None)
+        finally:
+            if not self._hold:
+                self._ev = None                          # the captured graphs and their static buffers live for this call only
+        stats = {"uncond_noise_norm": [], "text_noise_norm": []}
+        if cfg:
+            nrm = slab.cpu().double().sum(-1).sqrt()     # [steps, 2, n]: the one device -> host read of the loop
+            stats["uncond_noise_norm"] = nrm[:, 0].t().tolist()
+            stats["text_noise_norm"] = nrm[:, 1].t().tolist()
+        if not track_noise_norm:
+            stats = {"uncond_noise_norm": None, "text_noise_norm": None}
+        if output_type == "latent":
+            return x, stats
+        img = self.vae.decode(x / self.vae.cfg.scaling_factor)
+        u8 = ((img / 2 + 0.5).clamp(0, 1) * 255).round().to(torch.uint8).permute(0, 2, 3, 1).cpu().numpy()
+        if output_type == "np":
+            return u8, stats
+        from PIL import Image
+        return [Image.fromarray(a) for a in u8], stats

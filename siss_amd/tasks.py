@@ -256,7 +256,7 @@ class _DeleteBase(Task):
                 if pending is not None:
                     write_log(*pending)
                 pending = (handle, meta)
-                if eval_every and (step + 1) % eval_every == 0 and not isinstance(self, DeleteSD):
+                if eval_every and (step + 1) % eval_every == 0:
                     write_log(*pending)                 # every rank flushes at an evaluation step (the logs stay in step)
                     pending = None
                     if rank == 0:
@@ -395,20 +395,21 @@ class DeleteSD(_DeleteBase):
         return (SyntheticImages(4096, shape, seed=1, scale=self.VAE_SCALE, normal=True),
                 SyntheticImages(1, shape, seed=2, scale=self.VAE_SCALE, normal=True))
 
-    def conditioning(self, B, device):
+    def _prompt_embedding(self, p, device):
+        """[1, L, X] f32 embedding of one validation prompt: a .pt embedding / token-id file, a string through text_encoder/ +
+        tokenizer/, or (allow_synthetic) a seeded synthetic embedding."""
         cfg = self.cfg
-        vp = cfg.get("validation_prompts")
         X = int((cfg.get("unet") or {}).get("cross_attention_dim", 768))
-        if vp and str(vp[0]).endswith(".pt") and os.path.exists(str(vp[0])):
-            e = torch.load(str(vp[0])).to(device)
+        if p and str(p).endswith(".pt") and os.path.exists(str(p)):
+            e = torch.load(str(p)).to(device)
             if not e.is_floating_point():                       # token ids [77] / [1,77]: run the text encoder
                 assert self.text_encoder is not None, "token ids given but no text_encoder/ in the checkpoint directory"
                 e = self.text_encoder(e.reshape(1, -1))[0]
             e = e.float().reshape(-1, e.shape[-2], e.shape[-1])[:1]
-        elif vp and self.text_encoder is not None:
+        elif p and self.text_encoder is not None:
             from transformers import CLIPTokenizer               # delete_sd.py:395-410 tokenize_captions
             tok = CLIPTokenizer.from_pretrained(str(cfg.pretrained_model_name_or_path), subfolder="tokenizer")
-            ids = tok([str(vp[0])], max_length=tok.model_max_length, padding="max_length", truncation=True,
+            ids = tok([str(p)], max_length=tok.model_max_length, padding="max_length", truncation=True,
                       return_tensors="pt").input_ids
             e = self.text_encoder(ids)[0].float()
         elif cfg.get("allow_synthetic"):
@@ -416,4 +417,89 @@ class DeleteSD(_DeleteBase):
         else:
             raise FileNotFoundError("validation_prompts[0] is neither a .pt embedding / token file on disk nor a prompt with a "
                                     "text_encoder/ + tokenizer/ on disk; pass allow_synthetic=true for a synthetic embedding")
+        return e
+
+    def conditioning(self, B, device):
+        vp = self.cfg.get("validation_prompts")
+        e = self._prompt_embedding(vp[0] if vp else None, device)
         return {"encoder_hidden_states": e.repeat(B, 1, 1)}     # one prompt for the whole batch (delete_sd.py:941-944)
+
+    pipeline = None             # the validation pipeline (SDSampler), built at the first evaluation
+
+    def _validation_pipeline(self, unet, device):
+        """The SD pipeline of log_validation (delete_sd.py:185-204), built at the first evaluation: the VAE decoder is read from
+        vae/ only now (no vae/ on disk: noise norms without images); the negative prompt is the text encoder's output for the
+        empty prompt, or a seeded synthetic embedding where the prompts are synthetic too."""
+        from .scheduler import DDIMScheduler
+        from .sd_sampler import SDSampler, uncond_ids
+        cfg = self.cfg
+        path = str(cfg.get("pretrained_model_name_or_path") or "")
+        vae = None
+        if os.path.isdir(os.path.join(path, "vae")):
+            from .vae import VAEDecoder
+            vae = VAEDecoder.from_pretrained(path, "vae", device)
+        else:
+            print(f"[siss_amd] evaluation: no vae/ under {path!r}: noise norms only, no validation images")
+        if self.text_encoder is not None:
+            ids = uncond_ids(path)
+            if int(ids.max()) >= self.text_encoder.tok.shape[0]:      # (checked here: a bad id would fault the gather on the device)
+                raise ValueError(f"empty-prompt token ids reach {int(ids.max())}, beyond the text encoder's vocabulary of "
+                                 f"{self.text_encoder.tok.shape[0]}: put the checkpoint's tokenizer/ beside it")
+            neg = self.text_encoder(ids)[0].float()
+        elif cfg.get("allow_synthetic"):
+            X = int((cfg.get("unet") or {}).get("cross_attention_dim", 768))
+            neg = torch.randn(1, 77, X, generator=torch.Generator().manual_seed(self.seed() + 1)).to(device)
+        else:
+            raise FileNotFoundError("evaluation needs the empty prompt's embedding: no text_encoder/ in the checkpoint directory "
+                                    "(pass allow_synthetic=true for a synthetic one)")
+        self.pipeline = SDSampler(unet, vae=vae, scheduler=DDIMScheduler.from_pretrained(path or None))
+        self._negative_embeds = neg
+        return self.pipeline
+
+    def evaluate(self, unet, sched, forget_image, step, device):
+        """The image and noise-norm part of log_validation (delete_sd.py:170-340): per validation prompt, eval_batches x
+        eval_batch_size images (DDIM, pipeline.num_inference_steps or 50 steps, guidance 7.5) from ONE generator seeded from
+        cfg.seed per evaluation (:213-218), written as a PNG grid (nrow = int(sqrt(N)), :246), and the per-step text-conditional
+        and unconditional noise norms averaged over the images, index 0 = the smallest timestep (:284-291), appended to
+        noise_norms_rank0.jsonl.  Opt-in through eval_every; its own RNG; the engine's weights are only read."""
+        import numpy as np
+        cfg = self.cfg
+        sampler = self.pipeline or self._validation_pipeline(unet, device)
+        nb, bs = int(cfg.get("eval_batches") or 8), int(cfg.get("eval_batch_size") or 1)
+        steps = int(((cfg.get("pipeline") or {}).get("num_inference_steps")) or 50)
+        vp = cfg.get("validation_prompts") or [None]
+        g = torch.Generator(device=device).manual_seed(self.seed())
+        out_type = "np" if sampler.vae is not None else "latent"
+        with sampler.holding_graphs():
+            for i, p in enumerate(vp):
+                e = self._prompt_embedding(p, device)
+                imgs, text_n, uncond_n = [], [], []
+                for _ in range(nb):
+                    im, st = sampler(e, negative_prompt_embeds=self._negative_embeds, num_inference_steps=steps,
+                                     guidance_scale=7.5, num_images_per_prompt=bs, generator=g, output_type=out_type)
+                    if out_type == "np":
+                        imgs.extend(list(im))
+                    text_n.extend(st["text_noise_norm"])
+                    uncond_n.extend(st["uncond_noise_norm"])
+                if imgs:
+                    _grid(imgs, int(np.sqrt(len(imgs)))).save(os.path.join(cfg.output_dir, f"validation_p{i}_step{step}.png"))
+                rec = {"step": step, "prompt": i, "prompt_text": None if p is None else str(p),
+                       "timesteps": sampler.scheduler.timesteps[::-1],
+                       "text_noise_norm": np.mean(np.asarray(text_n), axis=0)[::-1].tolist(),
+                       "uncond_noise_norm": np.mean(np.asarray(uncond_n), axis=0)[::-1].tolist()}
+                with open(os.path.join(cfg.output_dir, "noise_norms_rank0.jsonl"), "a") as f:
+                    f.write(json.dumps(rec) + "\n")
+
+
+def _grid(images, nrow, padding=2):
+    """torchvision.utils.make_grid's layout (nrow images per row, 2-pixel black padding) of uint8 [H, W, 3] images, as a PIL image."""
+    import numpy as np
+    from PIL import Image
+    n, (h, w, c) = len(images), images[0].shape
+    cols = min(max(1, nrow), n)
+    rows = -(-n // cols)
+    out = np.zeros((rows * (h + padding) + padding, cols * (w + padding) + padding, c), dtype=np.uint8)
+    for k, im in enumerate(images):
+        r, q = divmod(k, cols)
+        out[r * (h + padding) + padding:r * (h + padding) + padding + h, q * (w + padding) + padding:q * (w + padding) + padding + w] = im
+    return Image.fromarray(out)

@@ -6,10 +6,16 @@
 256 x 256 architecture, random-init weights, synthetic inputs.
 
     python tools/bench_sampler.py [--batch 1 16] > profiles/rNN_sampler_celeb.json
+    python tools/bench_sampler.py --sd [--sd-batch 1 4] [--sd-dtype bf16 f32]
 
 One JSON line: per batch size, the two schedules timed end to end (captured forward replayed per denoising step vs eager launches),
 images / s, UNet forwards / s, and the forward's fraction of the bf16 MFMA roof (1 x 498.35 GFLOP per sample and forward, SURVEY.md
-§8d, against 2.5 PFLOP/s)."""
+§8d, against 2.5 PFLOP/s).
+
+--sd: the SD v1.5 validation pipeline of delete_sd.py:170-340 instead (siss_amd/sd_sampler.py: DDIM, guidance 7.5, 512 x 512):
+ms per denoising step (one replay of the captured UNet forward over the 2n batch + the fused guidance / DDIM launch) at each
+--sd-batch, the fused siss_cfg_ddim_step launch alone (us), the VAE decode per 512 x 512 image (ms), and one reference-sized
+validation (eval_batches 8 x eval_batch_size 1 images x 50 steps + decode, s).  Random-init weights, synthetic prompts."""
 import argparse
 import json
 import os
@@ -36,12 +42,80 @@ def timed(fn):
     return time.perf_counter() - t0
 
 
+def sd_main(a):
+    from siss_amd.config import UNet2DConditionConfig
+    from siss_amd.model import UNet2DConditionModel
+    from siss_amd.scheduler import DDIMScheduler
+    from siss_amd.sd_sampler import SDSampler, cfg_ddim_step, ddim_blocks
+    from siss_amd.vae import VAEDecoder
+    dev = torch.device("cuda:0")
+    vae = VAEDecoder(device=dev)
+    vae.load_state_dict({k: 0.02 * torch.randn(v) if len(v) > 1 else (torch.ones(v) if "norm" in k and k.endswith(".weight")
+                                                                        else torch.zeros(v))
+                         for k, v in vae.diffusers_shapes().items()})
+    g = torch.Generator().manual_seed(0)
+    out = {"metric": "SD v1.5 validation sampling (delete_sd.py:170-340): DDIM + CFG 7.5, 512 x 512", "data": "synthetic",
+           "device": torch.cuda.get_device_name(0), "results": {}}
+    # the fused guidance + DDIM launch alone: latents of one 512 x 512 image per sample
+    sch = DDIMScheduler.from_pretrained(None)
+    sch.set_timesteps(50)
+    kern = {}
+    for n in a.sd_batch:
+        eps, x = torch.randn(2 * n, 4, 64, 64, device=dev), torch.randn(n, 4, 64, 64, device=dev)
+        slab = torch.empty(2, n, ddim_blocks(n, 4 * 64 * 64), device=dev)
+        co = sch.coeffs(501)
+        for _ in range(10):
+            cfg_ddim_step(eps, x, x, co, 7.5, 0.0, slab)
+        s0, s1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s0.record()
+        for _ in range(200):
+            cfg_ddim_step(eps, x, x, co, 7.5, 0.0, slab)
+        s1.record()
+        torch.cuda.synchronize()
+        kern[f"n{n}"] = round(s0.elapsed_time(s1) / 200 * 1e3, 2)
+    out["results"]["cfg_ddim_step_us"] = kern
+    z = torch.randn(1, 4, 64, 64, device=dev)
+    vae.decode(z)
+    out["results"]["decode_ms_per_512px_image"] = round(timed(lambda: [vae.decode(z) for _ in range(5)]) / 5 * 1e3, 2)
+    for dt in a.sd_dtype:
+        unet = UNet2DConditionModel(UNet2DConditionConfig.sd15(), device=dev,
+                                    compute_dtype=torch.float32 if dt == "f32" else torch.bfloat16)
+        unet.engine.init_random(seed=0)
+        pipe = SDSampler(unet, vae=vae)
+        neg = torch.randn(1, 77, 768, generator=g).to(dev)
+        row = {}
+        for n in a.sd_batch:
+            text = torch.randn(n, 77, 768, generator=g).to(dev)
+            with pipe.holding_graphs():
+                run = lambda k: pipe(text, negative_prompt_embeds=neg.expand(n, -1, -1), num_inference_steps=k, output_type="latent")
+                run(2)                                                  # the capture
+                t10, t60 = timed(lambda: run(10)), timed(lambda: run(60))
+            row[f"ms_per_denoising_step_n{n}"] = round((t60 - t10) / 50 * 1e3, 3)
+        text = torch.randn(1, 77, 768, generator=g).to(dev)
+        gen = torch.Generator(device=dev).manual_seed(42)
+
+        def validation():
+            with pipe.holding_graphs():
+                for _ in range(8):
+                    pipe(text, negative_prompt_embeds=neg, num_inference_steps=50, generator=gen, output_type="np")
+        row["validation_8x1_images_50_steps_s"] = round(timed(validation), 3)
+        out["results"][dt] = row
+        del pipe, unet
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, nargs="+", default=[1, 16], help="eval_batch_size (config/delete_celeb.yaml:101 ships 1)")
     ap.add_argument("--sample-steps", type=int, default=50)
     ap.add_argument("--inject-t", type=int, default=250)
+    ap.add_argument("--sd", action="store_true", help="the SD v1.5 validation pipeline (DDIM + CFG + VAE decode) instead")
+    ap.add_argument("--sd-batch", type=int, nargs="+", default=[1, 4], help="images per pipeline call")
+    ap.add_argument("--sd-dtype", nargs="+", default=["bf16", "f32"], choices=["bf16", "f32"],
+                    help="UNet engine: bf16, or f32 (mixed_precision: null, config/delete_sd.yaml)")
     a = ap.parse_args()
+    if a.sd:
+        return sd_main(a)
     dev = torch.device("cuda:0")
     unet = UNet2DModel(UNet2DConfig.celebahq256(), device=dev)
     unet.engine.init_random(seed=0)
