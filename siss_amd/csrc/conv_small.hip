@@ -276,6 +276,63 @@ __global__ __launch_bounds__(kThreads) void conv_out_wgrad_kernel(
     if (ky == 0 && threadIdx.x < CO) atomicAdd(dbias + (long)set * set_stride_b + threadIdx.x, sh[3 * CO * C + threadIdx.x]);
 }
 
+// conv_in data gradient (the input VJP of the likelihood metric): the cotangent of conv_in's output -> the image's.
+//   dx[n][ci][y][x] = sum_{tap, co} dh[n, y - ky + 1, x - kx + 1, co] * w[co][tap * CIN + ci]
+// dh: padded NHWC rows [N][H+2][W+2] of C0 channels at row stride ld (a column view of a concat buffer: ld > C0), T = bf16
+// (the product path) or f32 (the f32 mode); w: conv_in's native [C0][Kp] operand copy (k = tap * CIN + ci, zero beyond 9 CIN),
+// same T; dx: NCHW f32.  C0 / 8 lanes per pixel, 8 channels per lane, folded with wave shuffles (conv_out_fprop_kernel's shape).
+__device__ __forceinline__ void load8(const bf16_t* p, float (&v)[8]) { unpack8(*reinterpret_cast<const u32x4_t*>(p), v); }
+__device__ __forceinline__ void load8(const float* p, float (&v)[8]) {
+    const f32x4_t a = reinterpret_cast<const f32x4_t*>(p)[0], b = reinterpret_cast<const f32x4_t*>(p)[1];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { v[e] = a[e]; v[4 + e] = b[e]; }
+}
+
+template <typename T, int CIN>
+__global__ __launch_bounds__(kThreads) void conv_in_dgrad_kernel(const T* __restrict__ dh, long ld, const T* __restrict__ w, int kp,
+                                                                 float* __restrict__ dx, int N, int H, int W, int C0) {
+    extern __shared__ float shw[];   // [9][CIN][C0]
+    for (int i = threadIdx.x; i < 9 * CIN * C0; i += kThreads) {
+        const int co = i % C0, r = i / C0;
+        shw[i] = to_f(w[(long)co * kp + r]);
+    }
+    __syncthreads();
+    const int lpp = C0 / 8, ppb = kThreads / lpp;
+    const int slot = threadIdx.x / lpp, cc = threadIdx.x - slot * lpp;
+    const long npix = (long)N * H * W;
+    const int Wp = W + 2;
+    for (long pbase = (long)blockIdx.x * ppb; pbase < npix; pbase += (long)gridDim.x * ppb) {
+        const long p = pbase + slot;
+        const bool ok = p < npix;
+        const long pc = ok ? p : npix - 1;
+        const int xx = pc % W; long t = pc / W;
+        const int yy = t % H; const int n = t / H;
+        float acc[CIN];
+#pragma unroll
+        for (int ci = 0; ci < CIN; ++ci) acc[ci] = 0.f;
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            const int yo = yy - tap / 3 + 1, xo = xx - tap % 3 + 1;     // the output pixel that read (yy, xx) through this tap
+            if (yo < 0 || yo >= H || xo < 0 || xo >= W) continue;
+            float v[8];
+            load8(dh + (((long)n * (H + 2) + yo + 1) * Wp + xo + 1) * ld + cc * 8, v);
+#pragma unroll
+            for (int ci = 0; ci < CIN; ++ci) {
+                const float* ww = shw + (tap * CIN + ci) * C0 + cc * 8;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc[ci] = fmaf(v[e], ww[e], acc[ci]);
+            }
+        }
+        for (int off = lpp >> 1; off > 0; off >>= 1)
+#pragma unroll
+            for (int ci = 0; ci < CIN; ++ci) acc[ci] += __shfl_xor(acc[ci], off, 64);
+        if (ok && cc == 0) {
+#pragma unroll
+            for (int ci = 0; ci < CIN; ++ci) dx[(((long)n * CIN + ci) * H + yy) * W + xx] = acc[ci];
+        }
+    }
+}
+
 inline bool lpp_ok(int C) {
     if (C % 8) return false;
     const int l = C / 8;
@@ -340,6 +397,37 @@ int siss_conv_out_wgrad(const float* c, const void* x, float* dW, float* dbias, 
     hipStream_t st = (hipStream_t)stream;
     DISPATCH_CO(CO, (conv_out_wgrad_kernel<kCO><<<grid, kThreads, (3 * kCO * C + kCO) * sizeof(float), st>>>(c, (const bf16_t*)x, dW, dbias, set_images, nx, set_stride_w, set_stride_b, H, W, C)));
     SISS_LAUNCH_RET();
+}
+
+}  // extern "C"
+
+template <typename T>
+static int conv_in_dgrad_launch(const void* dh, long ld, const void* w, int kp, float* dx, int N, int Cin, int H, int W, int C0,
+                                void* stream) {
+    SISS_CHECK_ARG(dh && w && dx && N > 0 && H > 0 && W > 0 && Cin >= 1 && Cin <= 4 && lpp_ok(C0) && ld >= C0 && ld % 8 == 0);
+    SISS_CHECK_ARG(kp >= 9 * Cin && (uintptr_t)dh % 16 == 0 && 9L * Cin * C0 * sizeof(float) <= 64 * 1024);
+    const int ppb = kThreads / (C0 / 8);
+    long nb = ((long)N * H * W + ppb - 1) / ppb;
+    if (nb > 4096) nb = 4096;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t lds = 9 * (size_t)Cin * C0 * sizeof(float);
+    DISPATCH_CO(Cin, (conv_in_dgrad_kernel<T, kCO><<<(int)nb, kThreads, lds, st>>>((const T*)dh, ld, (const T*)w, kp, dx, N, H, W, C0)));
+    SISS_LAUNCH_RET();
+}
+
+extern "C" {
+
+// conv_in's data gradient: dh = the cotangent of its output (padded NHWC bf16, C0 channels at row stride ld >= C0, 16-B aligned),
+// w = its bf16 operand copy [C0][Kp] (k = tap * Cin + ci), dx = the image's cotangent, NCHW f32 [N][Cin][H][W] (Cin 1..4).
+int siss_conv_in_dgrad(const void* dh, long ld, const void* w, int kp, float* dx, int N, int Cin, int H, int W, int C0,
+                       void* stream) {
+    return conv_in_dgrad_launch<bf16_t>(dh, ld, w, kp, dx, N, Cin, H, W, C0, stream);
+}
+
+// siss_conv_in_dgrad with an f32 cotangent and f32 weights (the f32 mode)
+int siss_conv_in_dgrad_f32(const void* dh, long ld, const void* w, int kp, float* dx, int N, int Cin, int H, int W, int C0,
+                           void* stream) {
+    return conv_in_dgrad_launch<float>(dh, ld, w, kp, dx, N, Cin, H, W, C0, stream);
 }
 
 }  // extern "C"

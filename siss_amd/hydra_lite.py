@@ -170,6 +170,10 @@ TARGET_REMAP = {
     "torchvision.transforms.ToTensor": "siss_amd.data.ToTensor",
     "torchvision.transforms.Normalize": "siss_amd.data.Normalize",
     "data.src.celeb_dataset.CelebAHQ": "siss_amd.data.CelebAHQ",
+    "metrics.likelihood.LikelihoodEvaluator": "siss_amd.likelihood.LikelihoodEvaluator",
+    "metrics.song_likelihood.sde_lib.VPSDE": "siss_amd.likelihood.VPSDE",
+    "metrics.song_likelihood.sde_lib.VESDE": "siss_amd.likelihood.VESDE",          # (refused when built)
+    "metrics.song_likelihood.sde_lib.subVPSDE": "siss_amd.likelihood.subVPSDE",    # (refused when built)
 }
 
 

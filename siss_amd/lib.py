@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SISS_LIB_PATH") or os.path.join(_HERE, "libsiss_hip.so")   # override: A/B two builds
 
-P, I, L, F = C.c_void_p, C.c_int, C.c_long, C.c_float
+P, I, L, F, D = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double
 IP = C.POINTER(C.c_int)
 
 # name -> argtypes (all launchers return int status unless listed in _RET_LONG)
@@ -91,6 +91,11 @@ SIGNATURES = {
     "siss_conv_out_fprop": [P, P, P, P, I, I, I, I, I, P],
     "siss_conv_out_dgrad": [P, P, P, I, I, I, I, I, P],
     "siss_conv_out_wgrad": [P, P, P, P, I, I, I, L, L, I, I, I, I, P],
+    "siss_conv_in_dgrad": [P, L, P, I, P, I, I, I, I, I, P],
+    "siss_pflow_drift_div": [P, P, P, P, P, P, P, I, L, I, P],
+    "siss_slab_rowsum_f64": [P, P, I, I, P],
+    "siss_rk_combine": [P, P, D, P, P, L, L, P],
+    "siss_rk_norm": [P, D, P, P, D, D, L, P, I, P],
     "siss_mha_small_fwd": [P, P, P, P, P, I, I, I, I, F, P],
     "siss_mha_small_bwd": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, P],
     "siss_softmax_fwd": [P, P, L, I, P],
@@ -127,7 +132,7 @@ F32_ENTRY = {n: n + "_f32" for n in (
     "siss_pad_to_compact", "siss_compact_add_to_pad", "siss_im2col3x3", "siss_conv_out_fprop", "siss_mha_small_fwd",
     "siss_mha_small_bwd", "siss_softmax_fwd", "siss_softmax_bwd", "siss_softmax_rows_fwd", "siss_softmax_rows_bwd",
     "siss_layernorm_fwd", "siss_layernorm_bwd", "siss_geglu_fwd", "siss_geglu_bwd", "siss_head_split", "siss_head_merge",
-    "siss_rowdot", "siss_gemm_nt_mulsub")}
+    "siss_rowdot", "siss_gemm_nt_mulsub", "siss_conv_in_dgrad")}
 F32_ENTRY.update({"siss_transpose_bf16": "siss_transpose_f32", "siss_cast_f32_bf16": "siss_copy_f32",
                   "siss_conv_weight_dgrad_multi_bf16": "siss_conv_weight_dgrad_multi_f32"})
 # round 5: f32 forms of the engine's SCHEDULE SWITCHES (folded shortcut, depth-to-space epilogue, sub-pixel upsample, grouped wgrads),
@@ -137,7 +142,7 @@ F32_ENTRY.update({n: n + "_f32" for n in ("siss_gemm_nt_d2s", "siss_gemm_nt_d2s_
                                           "siss_upsample_phase_weights")})
 F32_SAME = {"siss_zero_ranges", "siss_upsample_phase_wgrad_fold", "siss_timestep_sincos", "siss_linear_small_fwd", "siss_linear_small_bwd", "siss_linear_multi_fwd", "siss_linear_multi_bwd",
             "siss_nchw_channel_sums", "siss_mixture_fwd", "siss_mixture_select", "siss_loss_bwd_seed", "siss_mse_bwd_seed",
-            "siss_ddpm_step", "siss_cfg_ddim_step", "siss_grad_norms_scale", "siss_grad_norm_partials", "siss_grad_scalars", "siss_recombine_clip_adamw"}
+            "siss_ddpm_step", "siss_cfg_ddim_step", "siss_pflow_drift_div", "siss_slab_rowsum_f64", "siss_rk_combine", "siss_rk_norm", "siss_grad_norms_scale", "siss_grad_norm_partials", "siss_grad_scalars", "siss_recombine_clip_adamw"}
 for _b, _f in F32_ENTRY.items():
     SIGNATURES[_f] = SIGNATURES[_b]
 _MODE = threading.local()        # per thread: autograd runs an engine's backward on its own device thread (siss_amd/model.py)
@@ -187,6 +192,22 @@ class TNJob(C.Structure):
                 ("N", I), ("C", I), ("npanels", I), ("nsets", I), ("rows_per_set", I), ("row_begin", I), ("row_end", I),
                 ("nsplits", I), ("x_set_rows", L), ("zero_page", P), ("dbias", P), ("dbias2", P),
                 ("shifts", I * 9), ("coffs", I * 9), ("bias_set_stride", L)]
+
+
+class RkTerms(C.Structure):
+    """siss_rk_terms of include/siss_hip.h: sum_j c[j] * row[j] over up to 8 f64 device rows (csrc/likelihood.hip)."""
+    _fields_ = [("row", P * 8), ("c", D * 8), ("n", I)]
+
+    @classmethod
+    def of(cls, pairs):
+        pairs = list(pairs)
+        assert len(pairs) <= 8
+        t = cls()
+        for j, (c, r) in enumerate(pairs):
+            assert r.dtype == torch.float64 and r.is_cuda and r.is_contiguous()
+            t.row[j], t.c[j] = r.data_ptr(), float(c)
+        t.n = len(pairs)
+        return t
 
 
 _lib = None

@@ -34,15 +34,26 @@ class _UNetFn(torch.autograd.Function):
             # activations, so recompute this forward before differentiating it (checkpoint-style).
             eng.forward(*ctx.inputs)
             m._fwd_token = ctx.token
+        grads = [None] * len(ctx.needs_input_grad)
+        sample = ctx.inputs[0]
+        want_dx = bool(ctx.needs_input_grad[2]) and m._supports_input_vjp     # (the SD UNet: no sample gradient, as before)
+        if want_dx and not torch._C._will_engine_execute_node(m._anchor_node()):
+            # torch.autograd.grad(..., sample): the image's cotangent only -- no parameter gradient is formed or touched
+            grads[2] = eng.input_vjp(gout.contiguous().float()).to(sample.dtype)
+            return tuple(grads)
+        dx = torch.empty(sample.shape, dtype=torch.float32, device=sample.device) if want_dx else None
         eng.ps.grads[0].zero_()
-        eng.backward(gout.contiguous().float(), nsets=1)
+        eng.backward(gout.contiguous().float(), nsets=1, **({"dx": dx} if want_dx else {}))
         m._accumulate_param_grads()
-        return (None,) * len(ctx.needs_input_grad)
+        if want_dx:
+            grads[2] = dx.to(sample.dtype)
+        return tuple(grads)
 
 
 class UNet2DModel:
     config_cls = UNet2DConfig
     class_name = "UNet2DModel"
+    _supports_input_vjp = True
 
     @staticmethod
     def _make_engine(config, device, dtype=torch.bfloat16):
@@ -88,6 +99,12 @@ class UNet2DModel:
         for p in self._params.values():
             p.requires_grad_(flag)
         return self
+
+    def _anchor_node(self):
+        """The anchor's gradient-accumulation node: whether the running backward pass executes it tells a full backward
+        (parameter gradients wanted) from torch.autograd.grad(out, sample) (the same test torch.utils.checkpoint makes)."""
+        with torch.enable_grad():
+            return self._anchor.view_as(self._anchor).grad_fn.next_functions[0][0]
 
     def _accumulate_param_grads(self):
         ps = self.engine.ps
@@ -153,6 +170,7 @@ class UNet2DConditionModel(UNet2DModel):
     (delete_sd.py:458-462 load, :977-985 -> losses/ddpm_deletion_loss.py:24 call)."""
     config_cls = UNet2DConditionConfig
     class_name = "UNet2DConditionModel"
+    _supports_input_vjp = False
 
     @staticmethod
     def _make_engine(config, device, dtype=torch.bfloat16):

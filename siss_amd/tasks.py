@@ -182,6 +182,33 @@ class _DeleteBase(Task):
         grid(imgs).save(os.path.join(cfg.output_dir, f"samples_step{step}.png"))
         grid(den).save(os.path.join(cfg.output_dir, f"denoised_forget_t{t_inj}_step{step}.png"))
 
+    def likelihood_metric(self, unet, forget_image, device):
+        """`metrics.likelihood` (class_cfg, step_frequency) of the reference's T-shirt config: the forget image's bits/dim under the
+        current model (delete_tshirt.py:438-461).  OPT-IN (absent from the repo's configs): None when not configured.  Returns
+        (step_frequency, log(global_step)); each evaluation appends {global_step, bpd, nfe, seconds} to likelihood_rank0.jsonl.
+        The image is metrics.classifier.tshirt_path through cfg.transform when that file exists, else the first forget image.  The
+        Hutchinson probe comes from a generator of its own, seeded from random_seed."""
+        cfg = self.cfg
+        metrics = cfg.get("metrics") or {}
+        lk = metrics.get("likelihood")
+        if not lk:
+            return None
+        from .likelihood import log_likelihood
+        freq = int(lk.get("step_frequency") or 0)
+        if freq <= 0:
+            raise ValueError(f"metrics.likelihood.step_frequency={lk.get('step_frequency')!r}: a positive step count is needed")
+        evaluator = hydra_lite.instantiate(lk.class_cfg)
+        path = (metrics.get("classifier") or {}).get("tshirt_path")
+        if path and os.path.isfile(str(path)):
+            from PIL import Image
+            image = hydra_lite.instantiate(cfg.transform)(Image.open(str(path)))
+        else:
+            image = forget_image
+        image = image.to(device).float()
+        gen = torch.Generator(device=device).manual_seed(self.seed())
+        out = os.path.join(cfg.output_dir, "likelihood_rank0.jsonl")
+        return freq, lambda global_step: log_likelihood(evaluator, unet, image, global_step, out, gen)
+
     # -- the loop ------------------------------------------------------------------------------
     def run(self):
         cfg = self.cfg
@@ -228,6 +255,9 @@ class _DeleteBase(Task):
         t0 = time.perf_counter()
         eval_every = int(cfg.get("eval_every") or 0)
         pending = None
+        likelihood = self.likelihood_metric(unet, ds_del[0], device) if rank == 0 else None
+        if likelihood is not None:
+            likelihood[1](0)                             # before the first optimizer step
 
         def write_log(handle, meta):
             st = handle.get()
@@ -261,6 +291,8 @@ class _DeleteBase(Task):
                     pending = None
                     if rank == 0:
                         self.evaluate(unet, sched, ds_del[0], step + 1, device)
+                if likelihood is not None and (step + 1) % likelihood[0] == 0:
+                    likelihood[1](step + 1)
         finally:
             # the last COMPLETED optimizer step reaches the log also when the next one raises or the job is interrupted
             if pending is not None:

@@ -263,6 +263,7 @@ class UNetEngine:
         self._prep_pending, self._wT_stale = False, False
         self._fill_key, self._fill_plan, self._fill_plans, self._fill_tables = None, None, {}, []
         self._up_w = {}
+        self._vjp, self._dx, self._vjp_sums = False, None, None
 
     # ------------------------------------------------------------------ parameters
     def _early_blocks(self):
@@ -771,6 +772,8 @@ class UNetEngine:
     def _wgrad(self, dy: Act, x: Act, dW_view, co, ci, ksize, shifts=None, coffs=None, ldx=None, dbias=None,
                dbias2=None):
         """dW_view: grads[gbase:, off:] -- a strided view whose [0,0] element is the target."""
+        if self._vjp:                                   # input_vjp(): data gradients only
+            return
         ps = self.ps
         if shifts is None:
             if ksize == 3:
@@ -845,6 +848,8 @@ class UNetEngine:
                  self.temb_ntot, self.temb_dim)
 
         def bwd():
+            if self._vjp:                               # (the timestep is an integer: nothing flows past the MLP)
+                return
             nb, T = self.nb, self.temb_dim
             d_s = self._buf("temb.d_s", (nb, T))           # grad wrt silu(emb)
             d_s1 = self._buf("temb.d_s1", (nb, T))
@@ -987,7 +992,9 @@ class UNetEngine:
                 """dyt [rows2,C] cotangent of y = xin W^T + b (xin has B*S rows shared by the sets)."""
                 dW = ps.grads[gb:, ps.specs[wname + ".weight"].off:]
                 tiles = (-(-C // 128)) ** 2
-                if self.group_attn and self.group_rows:
+                if self._vjp:
+                    pass
+                elif self.group_attn and self.group_rows:
                     z9 = (lib.I * 9)(*([0] * 9))
                     self._wq.append((lib.TNJob(Y=dyt.data_ptr(), ldy=C, X=xin.data_ptr(), ldx=C, dW=dW.data_ptr(),
                                                set_stride=ps.total, N=C, C=C, npanels=1, nsets=ns, rows_per_set=si * S,
@@ -1090,7 +1097,9 @@ class UNetEngine:
             dW = ps.grads[gb:, sq.off:]
             zp = ops.zero_page(self.device)
             xsr = si * S if B == nb else 0
-            if grouped:
+            if self._vjp:
+                pass
+            elif grouped:
                 z9 = (lib.I * 9)(*([0] * 9))
                 self._wq.append((lib.TNJob(Y=dqkv.data_ptr(), ldy=3 * C, X=hn.data_ptr(), ldx=C, dW=dW.data_ptr(),
                                            set_stride=ps.total, N=3 * C, C=C, npanels=1, nsets=ns, rows_per_set=si * S,
@@ -1251,10 +1260,11 @@ class UNetEngine:
             queued = bool(self.subpixel_queue and self.group_rows and re - rb <= self.group_rows)
             # (queued: the scratch must survive until the grouped launch has run -- one per site, not the shared one)
             dW4 = self._buf((pre if queued else "up") + ".dW4", (self.nsets, 4, 4, C, C))
-            dW4.zero_()
             dWt, nsets_ = ps.grads[gb:, ps.specs[wname].off:], self.nsets
             fold = lambda: lib.call("siss_upsample_phase_wgrad_fold", dW4, dWt, ps.total, nsets_, C, C)
-            for plane in range(4):                       # (the scratch's set stride is 16 C^2, the bias gradient's the flat buffer's)
+            if not self._vjp:
+                dW4.zero_()
+            for plane in range(4 if not self._vjp else 0):                       # (the scratch's set stride is 16 C^2, the bias gradient's the flat buffer's)
                 if queued:
                     sh4 = phase_shifts(plane)
                     self._wq.append((lib.TNJob(Y=z.data[:, plane * C:].data_ptr(), ldy=4 * C, X=x.data.data_ptr(), ldx=ldx,
@@ -1268,7 +1278,9 @@ class UNetEngine:
                     lib.call("siss_gemm_tn_bs", z.data[:, plane * C:], 4 * C, x.data, ldx, dW4[:, plane], dW4[0].numel(), C, C, 4,
                              lib.int_array(phase_shifts(plane)), z4, self.nsets, rows_per_set, rows_per_set if x.n == nb else 0,
                              rb, re, 0, zp, ps.g(pre + ".conv.bias", gb), None, ps.total)
-            if queued:                                   # the nine-tap fold follows the grouped launch that forms the 16 phase-tap gradients
+            if self._vjp:
+                pass
+            elif queued:                                 # the nine-tap fold follows the grouped launch that forms the 16 phase-tap gradients
                 self._held[id(z.buf)] = z
                 self._wq_post.append(fold)
             else:
@@ -1439,6 +1451,9 @@ class UNetEngine:
             dh = self._take(h0)
             dW = ps.grads[self.gbase:, ps.specs["conv_in.weight"].off:]
             self._wgrad(dh, col, dW, c0, kp, 1, dbias=ps.g("conv_in.bias", self.gbase))
+            if self._dx is not None:                    # the image's cotangent (input_vjp / a sample that requires grad)
+                lib.call("siss_conv_in_dgrad", dh.data, getattr(dh, "ld", c0), ps.sh("conv_in.weight"), kp, self._dx, dh.n, cin, H, W,
+                         c0)
             self._put(dh)
         self.tape.append(conv_in_bwd)
         return h
@@ -1462,12 +1477,15 @@ class UNetEngine:
             kc = self._wd_out.shape[1]
             col = self._get(nb, H, W, kc)
             lib.call("siss_im2col3x3", c, 0, col.data, nb, co, H, W, kc, 1)
-            lib.call("siss_nchw_channel_sums", c, self.nsets, self.set_images, co, H * W, ps.total,
-                     ps.g("conv_out.bias", gb))
+            if not self._vjp:
+                lib.call("siss_nchw_channel_sums", c, self.nsets, self.set_images, co, H * W, ps.total,
+                         ps.g("conv_out.bias", gb))
             rows_per_set = self.set_images * col.rows_per_image
             rb, re = col.wp + 1, rows_per_set - (col.wp + 1)
             ns = ops._nsplits(1, 1, self.nsets, re - rb, False)
-            if self.pair_top and not self.f32 and re - rb >= self.pair_min_rows:
+            if self._vjp:
+                pass
+            elif self.pair_top and not self.f32 and re - rb >= self.pair_min_rows:
                 zp = ops.zero_page(self.device)
                 z9 = (lib.I * 9)(*([0] * 9))
                 self._pair1.append((lib.TNJob(Y=col.data.data_ptr(), ldy=kc, X=a.data.data_ptr(), ldx=c0,
@@ -1575,12 +1593,67 @@ class UNetEngine:
         self._fill_plans[key] = dict(stretches=got, n=len(starts), granules=pre[-1], table=table,
                                      skipped_bytes=16 * (total // 4 - pre[-1]))
 
-    def backward(self, cot, nsets=2, grad_base_set=0):
+    def backward(self, cot, nsets=2, grad_base_set=0, dx=None):
         """cot: [nb, Cout, H, W] f32 cotangent of pred, nb = nsets * set_images.  With the shared
         forward (SISS) nb = 2*N: rows [0,N) seed g_x and rows [N,2N) seed g_a.  Gradients are
-        ACCUMULATED into ps.grads[grad_base_set + set] (call zero_grad() at the start of a step)."""
+        ACCUMULATED into ps.grads[grad_base_set + set] (call zero_grad() at the start of a step).
+        dx: [nb, Cin, H, W] f32, also receives the cotangent of the input image (the weight gradients are unchanged)."""
         with lib.f32_mode(self.f32):
-            return self._backward(cot, nsets, grad_base_set)
+            self._dx = self._check_dx(dx, cot)
+            try:
+                return self._backward(cot, nsets, grad_base_set)
+            finally:
+                self._dx = None
+
+    def _check_dx(self, dx, cot):
+        if dx is not None:
+            assert dx.is_cuda and dx.dtype == torch.float32 and dx.is_contiguous()
+            assert tuple(dx.shape) == (cot.shape[0], self.cfg.in_channels, *cot.shape[2:])
+        return dx
+
+    def input_vjp(self, cot, out=None):
+        """The vector-Jacobian product of the last forward(x, t) with respect to the IMAGE x: cot [N, Cout, H, W] f32 -> dx
+        [N, Cin, H, W] f32 (the likelihood metric's Hutchinson divergence, and autograd.grad with respect to the sample).  The taped
+        backward replayed with one cotangent set and no weight-gradient product at all (no weight-gradient TN GEMM, no grouped / pair /
+        side-stream job, no time-embedding MLP backward; the unfused one-head attention's dK / dV -- data gradients -- still run on
+        the TN kernel, as in the full backward); the per-channel sums that fused kernels form on the way (GroupNorm gamma / beta) land
+        in a one-set scratch of the ParamStore layout, never in ps.grads.  The weights, the gradient buffers, the sparse-fill state and
+        the overwrite log are left as they were."""
+        assert cot.is_cuda and cot.dtype == torch.float32 and cot.is_contiguous()
+        N = cot.shape[0]
+        assert N == self.nf, "input_vjp: one cotangent per sample of the last forward()"
+        if out is None:
+            out = torch.empty(N, self.cfg.in_channels, *cot.shape[2:], dtype=torch.float32, device=self.device)
+        ps = self.ps
+        if self._vjp_sums is None:
+            self._vjp_sums = torch.zeros(1, ps.total, dtype=torch.float32, device=self.device)
+        with lib.f32_mode(self.f32):
+            dx = self._check_dx(out, cot)
+            grads, ps.grads = ps.grads, self._vjp_sums
+            self._vjp, self._dx = True, dx
+            try:
+                self._input_vjp(cot)
+            finally:
+                ps.grads = grads
+                self._vjp, self._dx = False, None
+        return out
+
+    def _input_vjp(self, cot):
+        nb = cot.shape[0]
+        self.nb, self.nsets, self.set_images, self.gbase, self.cot = nb, 1, nb, 0, cot
+        if self._wT_stale:
+            self._refresh_dgrad_copies()
+        if self._prep_pending:
+            torch.cuda.current_stream().wait_stream(self._side)
+            self._prep_pending = False
+        d_s = self._buf("temb.d_s", (nb, self.temb_dim))
+        d_s.zero_()
+        self.dtp_all = self._buf("temb.dtp_all", (nb, self.temb_ntot))
+        self.dtp_all.zero_()
+        for idx in range(len(self.tape) - 1, -1, -1):
+            self.tape[idx]()
+        assert not (self._wq or self._pair1 or self._wq_post or self._held or self._side_busy), "input_vjp queued a weight gradient"
+        assert not self.gmap, f"{len(self.gmap)} dangling cotangents"
 
     def _backward(self, cot, nsets, grad_base_set):
         assert cot.is_cuda and cot.dtype == torch.float32 and cot.is_contiguous()
