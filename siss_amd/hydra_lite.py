@@ -174,10 +174,20 @@ TARGET_REMAP = {
     "metrics.song_likelihood.sde_lib.VPSDE": "siss_amd.likelihood.VPSDE",
     "metrics.song_likelihood.sde_lib.VESDE": "siss_amd.likelihood.VESDE",          # (refused when built)
     "metrics.song_likelihood.sde_lib.subVPSDE": "siss_amd.likelihood.subVPSDE",    # (refused when built)
+    "metrics.classifier.Classifier": "siss_amd.classifier.Classifier",
+    "metrics.inception_score.InceptionScore": "siss_amd.classifier.InceptionScore",
+    "metrics.mnist_resnet.resnet18": "siss_amd.classifier.resnet18",
+    "metrics.tshirt.TShirtClassifier": "siss_amd.classifier.TShirtClassifier",
+    "hydra.utils.get_object": "siss_amd.hydra_lite.get_object",        # classifier: {_target_: hydra.utils.get_object, path: ...}
 }
+# the reference's other classifiers: not built (no CIFAR ResNet-56 kernels here, no network for torch.hub)
+REFUSED = ("metrics.cifar_resnet.", "torch.hub.load")
 
 
 def get_object(path):
+    if any(path == r or (r.endswith(".") and path.startswith(r)) for r in REFUSED):
+        raise NotImplementedError(f"{path}: the CIFAR ResNet-56 classifiers (metrics.cifar_resnet.*) and torch.hub.load are not "
+                                  "provided; the MNIST classifier is metrics.mnist_resnet.resnet18")
     path = TARGET_REMAP.get(path, path)
     mod, _, name = path.rpartition(".")
     return getattr(importlib.import_module(mod), name)

@@ -81,12 +81,13 @@ class Evaluator:
         return out
 
     @torch.no_grad()
-    def sample_images(self, num_samples, num_inference_steps=None, set_generator=False, x_T=None, noises=None):
-        """Returns [N, H, W, C] float numpy images in [0, 1] (DDPMPipeline output_type='numpy')."""
+    def sample_images(self, num_samples, num_inference_steps=None, set_generator=False, x_T=None, noises=None, generator=None):
+        """Returns [N, H, W, C] float numpy images in [0, 1] (DDPMPipeline output_type='numpy').  generator: a device generator the
+        noise is drawn from (instead of the global one, or the fresh seeded one of set_generator)."""
         u, sch = self.unet, self.noise_scheduler
         dev = u.device
         steps = num_inference_steps or (self.cfg.pipeline.num_inference_steps if self.cfg else 50)
-        gen = None
+        gen = generator
         if set_generator:
             gen = torch.Generator(device=dev).manual_seed(int(self.cfg.random_seed) if self.cfg else 0)
         shape = (num_samples, u.config.in_channels, u.config.sample_size, u.config.sample_size)

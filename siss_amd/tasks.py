@@ -209,6 +209,13 @@ class _DeleteBase(Task):
         out = os.path.join(cfg.output_dir, "likelihood_rank0.jsonl")
         return freq, lambda global_step: log_likelihood(evaluator, unet, image, global_step, out, gen)
 
+    def check_metrics(self):
+        """Refuse, before the first step, a metrics block that cannot run (a host-side check: no GPU needed).  Nothing here."""
+
+    def deletion_metrics(self, unet, sched, forget_image, device):
+        """The tracker of the configured deletion metrics (a callable of global_step), or None: none here."""
+        return None
+
     # -- the loop ------------------------------------------------------------------------------
     def run(self):
         cfg = self.cfg
@@ -218,6 +225,7 @@ class _DeleteBase(Task):
         seed = self.seed()
         torch.manual_seed(seed + rank)
         self.check_supported()
+        self.check_metrics()
         unet = self.load_unet(device)
         eng = unet.engine
         sched = self.load_scheduler()
@@ -258,6 +266,9 @@ class _DeleteBase(Task):
         likelihood = self.likelihood_metric(unet, ds_del[0], device) if rank == 0 else None
         if likelihood is not None:
             likelihood[1](0)                             # before the first optimizer step
+        metrics = self.deletion_metrics(unet, sched, ds_del[0], device) if rank == 0 else None
+        if metrics is not None:
+            metrics(0)
 
         def write_log(handle, meta):
             st = handle.get()
@@ -293,6 +304,8 @@ class _DeleteBase(Task):
                         self.evaluate(unet, sched, ds_del[0], step + 1, device)
                 if likelihood is not None and (step + 1) % likelihood[0] == 0:
                     likelihood[1](step + 1)
+                if metrics is not None:
+                    metrics(step + 1)
         finally:
             # the last COMPLETED optimizer step reaches the log also when the next one raises or the job is interrupted
             if pending is not None:
@@ -319,6 +332,76 @@ class DeleteTShirt(_DeleteBase):
     timestep_low = 0
     inf_guard = True
     default_unet = staticmethod(UNet2DConfig.mnist_tshirt)
+
+    def check_metrics(self):
+        """metrics.fraction_deletion needs a positive sampling_steps; metrics.inception_score needs metrics.classifier_cfg, a positive
+        step_frequency and, when classifier_ckpt is set, that file on disk -- all refused here, before the first step."""
+        cfg = self.cfg
+        m = cfg.get("metrics") or {}
+        if m.get("fraction_deletion"):
+            ss = cfg.get("sampling_steps")
+            if not isinstance(ss, int) or isinstance(ss, bool) or ss <= 0:
+                raise ValueError(f"metrics.fraction_deletion=true needs a positive sampling_steps (the reference's key: the T-shirt "
+                                 f"fraction runs every sampling_steps optimizer steps); got sampling_steps={ss!r}")
+        isc = m.get("inception_score")
+        if isc:
+            cc = m.get("classifier_cfg")
+            if not cc:
+                raise ValueError("metrics.inception_score needs metrics.classifier_cfg (the classifier the score is taken with)")
+            freq = isc.get("step_frequency")
+            if not isinstance(freq, int) or isinstance(freq, bool) or freq <= 0:
+                raise ValueError(f"metrics.inception_score.step_frequency={freq!r}: a positive step count is needed")
+            ckpt = cc.get("classifier_ckpt")
+            if ckpt is not None and not os.path.isfile(str(ckpt)):
+                raise FileNotFoundError(f"metrics.classifier_cfg.classifier_ckpt {ckpt!r} is not a file on disk")
+
+    def deletion_metrics(self, unet, sched, forget_image, device):
+        """delete_tshirt.py:438-482 without wandb, OPT-IN (absent from the repo's configs): `metrics.fraction_deletion` -- the share of
+        `eval_images` samples (batches of `eval_batch_size`, `pipeline.num_inference_steps` steps) within L2 distance 10 of the T-shirt,
+        at step 0 and every `sampling_steps` steps, `deletion_steps` = the first step where it is 0 -- and `metrics.inception_score`
+        (class_cfg, step_frequency, num_imgs_to_generate, batch_size) -- the Inception Score under metrics.classifier_cfg of the
+        samples that do not match the T-shirt, at step 0, every step_frequency steps and at deletion_steps.  Lines go to
+        metrics_rank0.jsonl (classifier.TShirtMetrics).  The T-shirt is metrics.classifier.tshirt_path through ToTensor when that
+        file exists, else the first forget image mapped to [0, 1].  The sampling noise and the score's permutation come from
+        generators of their own, seeded once from random_seed; the classifier is built here, and only when the score is configured."""
+        import numpy as np
+        from .classifier import InceptionScore, TShirtMetrics
+        from .sampler import Evaluator
+        cfg = self.cfg
+        m = cfg.get("metrics") or {}
+        frac, isc = bool(m.get("fraction_deletion")), m.get("inception_score") or None
+        if not frac and not isc:
+            return None
+        path = (m.get("classifier") or {}).get("tshirt_path")
+        if path and os.path.isfile(str(path)):
+            from PIL import Image
+            from .data import ToTensor
+            tshirt = ToTensor()(Image.open(str(path)))
+        else:
+            tshirt = forget_image.float() * 0.5 + 0.5
+        tshirt = tshirt.to(device).float()
+        steps = int(((cfg.get("pipeline") or {}).get("num_inference_steps")) or 50)
+        gen = torch.Generator(device=device).manual_seed(self.seed())
+
+        def sample(n, batch_size):
+            ev = Evaluator(cfg)
+            ev.load_model(unet, sched)
+            out = [ev.sample_images(min(batch_size, n - s), num_inference_steps=steps, generator=gen) for s in range(0, n, batch_size)]
+            return torch.from_numpy(np.concatenate(out)).permute(0, 3, 1, 2).to(device)
+
+        inception = None
+        if isc:
+            classifier = hydra_lite.instantiate(m.classifier_cfg, device=device)
+            node = isc.get("class_cfg")
+            inception = ((lambda: hydra_lite.instantiate(node, classifier=classifier)) if node
+                         else (lambda: InceptionScore(classifier)))
+        isc = isc or {}
+        return TShirtMetrics(tshirt, os.path.join(cfg.output_dir, "metrics_rank0.jsonl"), sample,
+                             sampling_steps=cfg.get("sampling_steps") if frac else None,
+                             eval_images=int(cfg.get("eval_images") or 128), eval_batch_size=cfg.get("eval_batch_size"),
+                             inception=inception, is_every=isc.get("step_frequency"),
+                             is_images=int(isc.get("num_imgs_to_generate") or 1024), is_batch_size=isc.get("batch_size"),
+                             generator=torch.Generator().manual_seed(self.seed()))
 
 
 class DeleteSD(_DeleteBase):
