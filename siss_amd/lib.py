@@ -1,129 +1,54 @@
-"""ctypes binding of libsiss_hip.so -- the C-ABI declared in include/siss_hip.h.
+"""ctypes binding of libsiss_hip.so -- the C-ABI declared in include/siss_hip.h: binding, f32-mode routing and launch.
+
+The argument types, parameter names and return types are READ from the header (which tools/gen_header.py generates from the
+extern "C" blocks of csrc/*.hip), so adding an entry point is: write the launcher, run tools/gen_header.py.  What a launch is
+booked as when PROF is on lives in siss_amd/prof.py.
 
 The product path has NO CPU fallback: if the library is missing or a launcher returns a
 non-zero status, a RuntimeError is raised.
 """
 import ctypes as C
 import os
+import re
 import threading
 
 import torch
 
+from . import prof
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SISS_LIB_PATH") or os.path.join(_HERE, "libsiss_hip.so")   # override: A/B two builds
 
-P, I, L, F, D = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double
-IP = C.POINTER(C.c_int)
+P, I, L, D = C.c_void_p, C.c_int, C.c_long, C.c_double      # (the fields of the two structs below)
+HEADER = os.path.join(os.path.dirname(_HERE), "include", "siss_hip.h")
+_SCALARS = {"int": C.c_int, "long": C.c_long, "float": C.c_float, "double": C.c_double}
 
-# name -> argtypes (all launchers return int status unless listed in _RET_LONG)
-SIGNATURES = {
-    "siss_loss_partials_words": [I, L],
-    "siss_mixture_fwd": [P, P, P, I, P, P, P, P, P, F, I, L, P, P, P, P, P, P, P, P, P],
-    "siss_mixture_select": [P, P, P, P, I, P, P, P, P, F, I, L, P, P, P, P, P, P, P, P, P],
-    "siss_ddpm_step": [P, P, P, P, L, F, F, F, F, F, I, P],
-    "siss_cfg_ddim_step": [P, P, P, I, L, F, F, F, F, F, F, P, I, P],
-    "siss_loss_bwd_seed": [P, P, P, P, I, P, P, P, P, F, I, L, P, P, P, P, P, P, P, P],
-    "siss_mse_bwd_seed": [P, P, I, F, I, L, P, P, P, P, P],
-    "siss_opt_partials_words": [],
-    "siss_opt_scalars_words": [],
-    "siss_grad_norms_scale": [P, P, L, I, F, F, F, F, P, P, P],
-    "siss_grad_norm_partials": [P, P, L, P, IP, P],
-    "siss_grad_scalars": [P, I, I, F, F, F, F, P, P],
-    "siss_recombine_clip_adamw": [P, P, P, P, P, P, P, L, F, F, F, F, F, P, P],
-    "siss_cast_f32_bf16": [P, P, L, P],
-    "siss_conv_weight_dgrad_layout": [P, P, I, I, I, P],
-    "siss_conv_weight_dgrad_multi": [P, P, P, I, I, P],
-    "siss_conv_weight_dgrad_multi_bf16": [P, P, P, I, I, P],
-    "siss_gemm_nt": [P, L, P, P, L, P, P, L, P, L, I, I, I, I, IP, IP, I, I, I, F, I, L, L, L, P],
-    "siss_gemm_nt_qstats": [P, L, P, P, L, P, P, L, P, L, I, I, I, I, IP, IP, I, I, I, F, P, IP, P],
-    "siss_gemm_nt_alpha_cols": [P, L, P, P, L, P, P, L, I, I, I, F, I, P],
-    "siss_gemm_nt_geglu_bwd": [P, L, P, P, P, L, I, I, I, P],
-    "siss_gemm_nt_geglu_fwd": [P, L, P, P, P, P, I, I, I, P],
-    "siss_abi_version": [],
-    "siss_conv3x3_sc": [P, L, P, P, L, P, P, L, P, L, P, I, P, I, I, I, IP, IP, I, I, I, P, IP, P],
-    "siss_conv3x3_sc_takes": [I, I, I, I, I, I, L, L, L],
-    "siss_conv3x3_dgrad_sc": [P, L, P, P, L, P, L, P, P, L, I, I, I, I, IP, IP, I, I, I, P],
-    "siss_conv3x3_dgrad_sc_takes": [I, I, I, I, I, I, L, L, L, L],
-    "siss_conv_qstats_words": [L, I],
-    "siss_gemm_nt_d2s": [P, L, P, P, L, P, L, I, I, I, I, IP, IP, I, I, I, I, P],
-    "siss_gemm_nt_d2s_bias": [P, L, P, P, L, P, I, I, I, I, IP, IP, I, I, I, I, P],
-    "siss_gemm_nt_d2s_phases": [P, L, P, P, L, P, P, L, I, I, I, IP, IP, IP, I, I, I, P],
-    "siss_upsample_phase_weights": [P, P, P, I, I, P],
-    "siss_upsample_phase_wgrad_fold": [P, P, L, I, I, I, P],
-    "siss_gemm_nt_set_workspace": [P, L],
-    "siss_gemm_nt_set_c3p_blocks": [I],
-    "siss_dispatch_count": [I],
-    "siss_dispatch_reset": [],
-    "siss_gemm_nt_mulsub": [P, L, P, P, L, P, L, P, I, I, I, F, I, L, L, L, P],
-    "siss_rowdot": [P, P, P, L, L, I, P],
-    "siss_gemm_tn": [P, L, P, L, P, L, I, I, I, IP, IP, I, I, L, I, I, I, P, P, P, P],
-    "siss_gemm_tn_bs": [P, L, P, L, P, L, I, I, I, IP, IP, I, I, L, I, I, I, P, P, P, L, P],
-    "siss_gemm_tn_grouped": [P, I, P],
-    "siss_gemm_tn_grouped_capped": [P, I, I, P],
-    "siss_gemm_tn_pair": [P, P, I, P],
-    "siss_gemm_tn_set_pair_cost": [I],
-    "siss_gemm_tn_overwrite_log": [P, L],
-    "siss_zero_ranges": [P, P, I, L, P],
-    "siss_gn_partial_words": [I, I, I, I, I],
-    "siss_groupnorm_set_slab": [I],
-    "siss_groupnorm_fwd": [P, P, P, P, P, P, P, I, I, I, I, I, F, I, I, P],
-    "siss_groupnorm_fwd_ld": [P, P, P, P, P, P, P, I, I, I, I, I, F, I, I, I, P],
-    "siss_quad_stats": [P, L, I, I, I, P, P],
-    "siss_groupnorm_fwd_qs": [P, P, P, P, P, P, P, P, I, P, I, I, I, I, I, F, I, I, I, P],
-    "siss_groupnorm_bwd": [P, P, P, P, P, P, P, P, P, P, I, I, P, P, P, L, P, I, I, I, L, I, I, I, I, I, I, P],
-    "siss_groupnorm_bwd_ld": [P, P, P, P, P, P, P, P, P, P, I, I, P, P, P, L, P, I, I, I, L, I, I, I, I, I, I, I, P],
-    "siss_groupnorm_bwd_ld_s2d": [P, P, P, P, P, P, P, P, P, P, I, I, P, P, P, L, P, I, I, I, L, I, I, I, I, I, I, I, P],
-    "siss_upsample2x": [P, P, I, I, I, I, P],
-    "siss_upsample2x_bwd": [P, P, I, I, I, I, P],
-    "siss_concat": [P, P, P, I, I, I, I, I, P],
-    "siss_concat_tail": [P, P, I, I, I, I, I, P],
-    "siss_concat_bwd": [P, P, P, I, I, I, I, I, I, P],
-    "siss_add_inplace": [P, P, I, I, I, I, P],
-    "siss_space_to_depth": [P, P, I, I, I, I, P],
-    "siss_space_to_depth_ld": [P, P, I, I, I, I, I, P],
-    "siss_depth_to_space": [P, P, I, I, I, I, I, P],
-    "siss_pad_to_compact": [P, P, I, I, I, I, P],
-    "siss_compact_add_to_pad": [P, P, P, I, I, I, I, P],
-    "siss_transpose_bf16": [P, P, I, I, I, P],
-    "siss_colsum": [P, L, I, I, L, P, P, P],
-    "siss_im2col3x3": [P, I, P, I, I, I, I, I, I, P],
-    "siss_nchw_channel_sums": [P, I, I, I, L, L, P, P],
-    "siss_conv_out_fprop": [P, P, P, P, I, I, I, I, I, P],
-    "siss_conv_out_dgrad": [P, P, P, I, I, I, I, I, P],
-    "siss_conv_out_wgrad": [P, P, P, P, I, I, I, L, L, I, I, I, I, P],
-    "siss_conv_in_dgrad": [P, L, P, I, P, I, I, I, I, I, P],
-    "siss_pflow_drift_div": [P, P, P, P, P, P, P, I, L, I, P],
-    "siss_slab_rowsum_f64": [P, P, I, I, P],
-    "siss_rk_combine": [P, P, D, P, P, L, L, P],
-    "siss_rk_norm": [P, D, P, P, D, D, L, P, I, P],
-    "siss_cls_conv": [P, I, P, P, P, P, P, L, I, I, I, I, I, I, I, I, I, I, I, I, I, I, P],
-    "siss_cls_maxpool": [P, P, I, I, I, I, I, I, P],
-    "siss_mha_small_fwd": [P, P, P, P, P, I, I, I, I, F, P],
-    "siss_mha_small_bwd": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, P],
-    "siss_softmax_fwd": [P, P, L, I, P],
-    "siss_softmax_bwd": [P, P, P, L, L, I, F, P],
-    "siss_layernorm_fwd": [P, P, P, P, P, P, L, I, F, P],
-    "siss_layernorm_bwd": [P, P, P, P, P, P, P, P, P, L, L, L, L, I, P],
-    "siss_geglu_fwd": [P, P, L, I, P],
-    "siss_geglu_bwd": [P, P, P, L, L, I, P],
-    "siss_head_split": [P, P, I, I, I, I, I, I, P],
-    "siss_head_merge": [P, P, I, I, I, I, I, I, P],
-    "siss_flash_attn_fwd": [P, P, P, P, P, I, I, I, I, I, F, P],
-    "siss_flash_attn_bwd": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, P],
-    "siss_flash_attn_fwd_merged": [P, L, P, L, P, L, P, L, P, I, I, I, I, I, F, I, P],
-    "siss_flash_attn_bwd_merged": [P, L, P, L, P, L, P, L, P, L, P, P, P, L, P, L, P, L, I, I, I, I, I, I, F, I, P],
-    "siss_attn1h_takes": [I, I],
-    "siss_attn1h_fwd": [P, P, P, L, P, L, I, P, I, I, I, F, P],
-    "siss_attn1h_bwd": [P, P, P, L, P, L, P, L, I, P, P, P, P, P, L, I, I, I, I, F, P],
-    "siss_softmax_rows_fwd": [P, P, L, I, I, I, P],
-    "siss_quick_gelu": [P, P, L, P],
-    "siss_softmax_rows_bwd": [P, P, P, L, L, I, I, F, P],
-    "siss_timestep_sincos": [P, P, I, I, I, F, P],
-    "siss_linear_small_fwd": [P, P, P, P, I, I, I, I, P],
-    "siss_linear_multi_fwd": [P, P, P, P, P, I, I, I, P],
-    "siss_linear_multi_bwd": [P, P, P, P, P, P, P, P, I, I, I, L, I, I, P],
-    "siss_linear_small_bwd": [P, P, P, P, P, I, P, P, P, I, I, I, L, L, I, I, I, P],
-}
+
+def parse_prototypes(text):
+    """{entry point: (restype, [(ctype, parameter name), ...])} of every `int|long siss_*(...);` in a header's text.  Scalars map
+    to their ctypes, `[const] int*` to POINTER(c_int) (host arrays handed over as int_array), every other pointer to c_void_p;
+    a declaration that is none of these raises with the prototype's name -- there is no default type."""
+    text = " ".join(re.sub(r"/\*.*?\*/", " ", text, flags=re.S).split())
+    out = {}
+    for ret, name, params in re.findall(r"\b(int|long) (siss_\w+) ?\(([^()]*)\) ?;", text):
+        out[name] = (_SCALARS[ret], [])
+        for decl in ([] if params.strip() in ("", "void") else params.split(",")):
+            m = re.fullmatch(r"(?:const )?(\w+)( ?\* ?| )(\w+)", decl.strip())
+            if m and "*" in m.group(2):
+                ctype = C.POINTER(C.c_int) if m.group(1) == "int" else C.c_void_p
+            elif m and m.group(1) in _SCALARS:
+                ctype = _SCALARS[m.group(1)]
+            else:
+                raise TypeError(f"{name}: no ctypes mapping for the parameter `{decl.strip()}`")
+            out[name][1].append((ctype, m.group(3)))
+    return out
+
+
+_PROTOTYPES = parse_prototypes(open(HEADER).read())
+SIGNATURES = {n: [t for t, _ in ps] for n, (_, ps) in _PROTOTYPES.items()}        # name -> argtypes (the stream included)
+PARAMS = {n: tuple(p for _, p in ps) for n, (_, ps) in _PROTOTYPES.items()}       # name -> the header's parameter names
+RESTYPE = {n: r for n, (r, _) in _PROTOTYPES.items()}                             # int status, or long for the *_words / count queries
+
 # ---- the f32 parity mode (csrc/f32_path.hip): same argument lists as the bf16 entry points, f32 tensors.  F32_ENTRY maps a bf16
 # entry point to its f32 form; F32_SAME lists the ones that never see an activation (f32 / index tensors only) and serve both
 # modes.  In f32 mode (f32_mode(True): set by an f32 engine around its launches) call() takes the f32 form and REFUSES an entry
@@ -145,8 +70,9 @@ F32_ENTRY.update({n: n + "_f32" for n in ("siss_gemm_nt_d2s", "siss_gemm_nt_d2s_
 F32_SAME = {"siss_zero_ranges", "siss_upsample_phase_wgrad_fold", "siss_timestep_sincos", "siss_linear_small_fwd", "siss_linear_small_bwd", "siss_linear_multi_fwd", "siss_linear_multi_bwd",
             "siss_nchw_channel_sums", "siss_mixture_fwd", "siss_mixture_select", "siss_loss_bwd_seed", "siss_mse_bwd_seed",
             "siss_ddpm_step", "siss_cfg_ddim_step", "siss_pflow_drift_div", "siss_slab_rowsum_f64", "siss_rk_combine", "siss_rk_norm", "siss_cls_conv", "siss_cls_maxpool", "siss_grad_norms_scale", "siss_grad_norm_partials", "siss_grad_scalars", "siss_recombine_clip_adamw"}
-for _b, _f in F32_ENTRY.items():
-    SIGNATURES[_f] = SIGNATURES[_b]
+for _b, _f in F32_ENTRY.items():          # the header's promise "same argument lists", checked once instead of assumed
+    if SIGNATURES[_b] != SIGNATURES[_f]:
+        raise TypeError(f"{_f} does not have the argument types of {_b} in {HEADER}")
 _MODE = threading.local()        # per thread: autograd runs an engine's backward on its own device thread (siss_amd/model.py)
 
 
@@ -168,9 +94,6 @@ class f32_mode:
         _MODE.f32 = self.prev
         return False
 
-
-_RET_LONG = {"siss_gemm_tn_overwrite_log", "siss_loss_partials_words", "siss_opt_partials_words", "siss_opt_scalars_words",
-             "siss_gn_partial_words", "siss_dispatch_count", "siss_conv_qstats_words"}
 
 # siss_dispatch_count() ids (common.h SissKernelId): which device kernel a launcher call landed on
 KERNEL_IDS = {"gemm_nt_kernel": 0, "gemm_nt_c3p_kernel": 1, "flash_attn_fwd": 2, "flash_attn_bwd": 3,
@@ -235,7 +158,7 @@ def load():
                 continue
             raise
         fn.argtypes = argtypes
-        fn.restype = C.c_long if name in _RET_LONG else C.c_int
+        fn.restype = RESTYPE[name]
     _lib = lib
     if override and abi_version() < MIN_ABI:
         _lib = None
@@ -296,136 +219,10 @@ def stream_ptr():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-# Optional per-launch timing (bench.py): when PROF is a list, every call is bracketed by events on
-# the launch stream and (name, start, end, work) is appended.  work = algorithmic flops of the launch
-# for the two MFMA GEMM kernels, 0 otherwise.
+# Optional per-launch timing (bench.py, tools/step_breakdown.py): when PROF is a list, every call is bracketed by events on the
+# launch stream and (base name, start, end, work, shape key, kernel symbol, hbm bytes) is appended -- the last four and the name
+# folding from siss_amd/prof.py, which reads the arguments by the header's parameter names.
 PROF = None
-
-
-def _work(name, a):
-    """ALGORITHMIC flops of a GEMM launch: the rows that count are the images' TRUE pixels (B * H * W), not the rows of
-    the padded-NHWC layout the kernel walks (halo pixels are layout overhead, 3.3 % at 256 x 256, 13 % at 32 x 32)."""
-    if name == "siss_gemm_nt":      # 2 * M * N * Kp * npanels * batch
-        M, rpi, hp, wp = a[10], a[16], a[17], a[18]
-        if hp > 2 and wp > 2 and M % rpi == 0:
-            M = (M // rpi) * (hp - 2) * (wp - 2)
-        return 2.0 * M * a[11] * a[12] * a[13] * a[20]
-    if name == "siss_conv3x3_sc":   # 2 * M * N * (9 Kp + K2): the 3x3 filter and the folded 1x1 shortcut
-        M, rpi, hp, wp = a[13], a[18], a[19], a[20]
-        if hp > 2 and wp > 2 and M % rpi == 0:
-            M = (M // rpi) * (hp - 2) * (wp - 2)
-        return 2.0 * M * a[14] * (9 * a[15] + a[11])
-    if name == "siss_conv3x3_dgrad_sc":   # 2 * M * Kp * (9 N + Nx): the 3x3 dgrad and the 1x1 shortcut dgrad over the same cotangent
-        M, rpi, hp, wp = a[11], a[16], a[17], a[18]
-        if hp > 2 and wp > 2 and M % rpi == 0:
-            M = (M // rpi) * (hp - 2) * (wp - 2)
-        return 2.0 * M * a[13] * (9 * a[12] + a[10])
-    if name == "siss_gemm_tn":      # 2 * N * C * npanels * nsets * rows
-        rows, rps, rb = a[15] - a[14], a[12], a[14]
-        wp = rb - 1                 # padded layouts reduce over rows [wp + 1, rows_per_set - (wp + 1)); images are square
-        if wp > 2 and rps % (wp * wp) == 0 and rows == rps - 2 * rb:
-            rows = (rps // (wp * wp)) * (wp - 2) * (wp - 2)
-        return 2.0 * a[6] * a[7] * a[8] * a[11] * rows
-    if name in ("siss_gemm_tn_grouped", "siss_gemm_tn_grouped_capped"):
-        return sum(_work("siss_gemm_tn", [None] * 6 + [j.N, j.C, j.npanels, None, None, j.nsets, j.rows_per_set, None,
-                                                       j.row_begin, j.row_end]) for j in a[0])
-    if name == "siss_gemm_tn_pair":     # (byref(job3), byref(job1), max_blocks): both products
-        return sum(_work("siss_gemm_tn", [None] * 6 + [j.N, j.C, j.npanels, None, None, j.nsets, j.rows_per_set, None,
-                                                       j.row_begin, j.row_end]) for j in (a[0]._obj, a[1]._obj))
-    if name == "siss_attn1h_fwd":       # QK^T and PV: 2 products of 2 B S S D
-        return 2.0 * 2 * a[8] * a[9] * a[9] * a[10]
-    if name == "siss_attn1h_bwd":       # algorithmic: S, dP, dQ, dK, dV over the nb cotangent images (7 products run: S and dP twice)
-        return 2.0 * 5 * a[15] * a[17] * a[17] * a[18]
-    if name == "siss_gemm_nt_mulsub":   # 2 * M * N * Kp * batch
-        return 2.0 * a[8] * a[9] * a[10] * a[12]
-    if name == "siss_flash_attn_fwd":   # QK^T and PV over the VALID keys (padded queries / head dim counted as laid out)
-        return 2.0 * 2 * a[5] * a[6] * a[9] * a[8]
-    if name == "siss_flash_attn_bwd":   # algorithmic: S, dP, dQ, dK, dV (the two-kernel form recomputes S and dP: 7 products run)
-        return 2.0 * 5 * a[9] * a[11] * a[14] * a[13]
-    if name == "siss_flash_attn_fwd_merged":   # true head dim, true rows: 2 products over B * H heads
-        return 2.0 * 2 * a[9] * a[10] * a[11] * a[12] * a[13]
-    if name == "siss_flash_attn_bwd_merged":
-        return 2.0 * 5 * a[18] * a[20] * a[21] * a[22] * a[23]
-    return 0.0
-
-
-def hbm_bytes(name, a):
-    """ALGORITHMIC HBM bytes of one launch of the HBM-bound launchers (every operand read once, every
-    result written once), for bench.py's GB/s-vs-HBM-peak figures.  None for the others."""
-    if name in ("siss_groupnorm_fwd", "siss_groupnorm_fwd_ld"):            # read x + write y (bf16)
-        return 2.0 * 2 * a[7] * a[8] * a[9] * a[10]
-    if name in ("siss_groupnorm_bwd", "siss_groupnorm_bwd_ld", "siss_groupnorm_bwd_ld_s2d"):   # read x (nx samples), read dy + write dx (n2 samples) (+ accum reads)
-        px = a[21] * a[22] * a[23]
-        n2, nx = a[17], a[18]
-        extra = (1 if a[7] is not None else 0) + (1 if a[8] is not None else 0)
-        return 2.0 * px * (nx + (2 + extra) * n2)
-    if name == "siss_recombine_clip_adamw":     # read g_x, g_a, theta, m, v; write theta, m, v (f32)
-        return 32.0 * a[7]
-    if name == "siss_mixture_fwd":              # read x0, a0, noise; write x_mix
-        return 4.0 * (2 if a[3] else 4) * a[10] * a[11]
-    if name == "siss_loss_bwd_seed":            # read pred (f32), x_mix, x0, a0; write c_x, c_a (f32)
-        return (4 + 3 * (2 if a[4] else 4) + 8.0) * a[10] * a[11]
-    return None
-
-
-def _shape_key(name, a):
-    """Problem shape of a launch, for per-layer breakdowns (tools/step_breakdown.py)."""
-    if name == "siss_gemm_nt":
-        return ("M", a[10], "N", a[11], "K", a[12], "panels", a[13], "batch", a[20]) + ((a[24],) if len(a) > 24 else ())
-    if name == "siss_conv3x3_sc":
-        return ("M", a[13], "N", a[14], "K", a[15], "panels", 9, "+1x1 K", a[11])
-    if name == "siss_conv3x3_dgrad_sc":
-        return ("M", a[11], "N", a[12], "K", a[13], "panels", 9, "+1x1 N", a[10])
-    if name == "siss_gemm_tn":
-        return ("N", a[6], "C", a[7], "panels", a[8], "sets", a[11], "rows", a[15] - a[14], "splits", a[16])
-    if name == "siss_gemm_tn_pair":
-        j3, j1 = a[0]._obj, a[1]._obj
-        return ("N", j3.N, "C", j3.C, "panels", j3.npanels, "+ N", j1.N, "C", j1.C, "panels", j1.npanels, "rows", j3.row_end - j3.row_begin)
-    if name in ("siss_attn1h_fwd", "siss_attn1h_bwd"):
-        return ("B", a[8] if name.endswith("fwd") else a[15], "S", a[9] if name.endswith("fwd") else a[17], "D", a[10] if name.endswith("fwd") else a[18])
-    if name in ("siss_groupnorm_fwd", "siss_groupnorm_fwd_ld"):
-        return ("n", a[7], "H", a[8], "C", a[10])
-    if name in ("siss_groupnorm_bwd", "siss_groupnorm_bwd_ld", "siss_groupnorm_bwd_ld_s2d"):
-        return ("n2", a[17], "H", a[21], "C", a[23])
-    if name == "siss_flash_attn_fwd":
-        return ("BH", a[5], "Sq", a[6], "Sk", a[9], "D", a[8])
-    if name == "siss_flash_attn_bwd":
-        return ("BH", a[9], "Sq", a[11], "Sk", a[14], "D", a[13])
-    if name == "siss_flash_attn_fwd_merged":
-        return ("BH", a[9] * a[10], "Sq", a[11], "Sk", a[12], "D", a[13])
-    if name == "siss_flash_attn_bwd_merged":
-        return ("BH", a[18] * a[20], "Sq", a[21], "Sk", a[22], "D", a[23])
-    return ()
-
-
-def kernel_symbol(name, a):
-    """Which device kernel a GEMM launcher call lands on (mirrors the dispatch in gemm_nt.hip / gemm_tn.hip), so
-    that bench.py can report the roofline of the dominant KERNEL under the name rocprofv3 lists it by."""
-    def triples(shifts, coffs, n):
-        return n % 3 == 0 and all(shifts[3 * g + 1] == shifts[3 * g] + 1 and shifts[3 * g + 2] == shifts[3 * g] + 2
-                                  and coffs[3 * g] == coffs[3 * g + 1] == coffs[3 * g + 2] for g in range(n // 3))
-    if name == "siss_gemm_nt":
-        M, N, Kp, npan, batch, rpi = a[10], a[11], a[12], a[13], a[20], a[16]
-        tiles = -(-M // 128) * -(-N // 128)
-        if (npan == 9 and batch == 1 and len(a) <= 24 and Kp % 64 == 0 and N % 128 == 0 and rpi >= 256
-                and tiles >= 256
-                and triples(a[14], a[15], 9)):
-            return "gemm_nt_c3p_kernel"
-        return "gemm_nt_kernel"
-    if name in ("siss_conv3x3_sc", "siss_conv3x3_dgrad_sc"):
-        return "gemm_nt_c3p_kernel"
-    if name == "siss_gemm_nt_mulsub":
-        return "gemm_nt_kernel"
-    if name == "siss_gemm_tn_grouped":
-        return "gemm_tn_grouped_kernel"
-    if name == "siss_gemm_tn_grouped_capped":
-        return "gemm_tn_grouped_capped_kernel"
-    if name == "siss_gemm_tn_pair":
-        return "gemm_tn_mixed_kernel"
-    if name == "siss_gemm_tn":
-        rows = a[15] - a[14]
-        return "gemm_tn_kernel<3>" if triples(a[9], a[10], a[8]) and (a[16] > 0 or rows >= 8192) else "gemm_tn_kernel<1>"
-    return name
 
 
 def call(name, *args, refusable=False):
@@ -441,52 +238,15 @@ def call(name, *args, refusable=False):
     fn = getattr(lib, name)
     conv = [ptr(a) if (torch.is_tensor(a) or a is None) else
             (C.cast(a, C.c_void_p) if isinstance(a, C.Array) and a._type_ is not C.c_int else a) for a in args]   # job tables
-    if PROF is not None:
+    if PROF is None:
+        rc = fn(*conv, stream_ptr())
+    else:
         s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         s.record()
         rc = fn(*conv, stream_ptr())
         e.record()
-        # variants that only add operands are booked under their plain form (same work, same shape key)
-        if name == "siss_gemm_nt_qstats":
-            name, args = "siss_gemm_nt", list(args[:20]) + [1, 0, 0, 0]
-        elif name == "siss_gemm_nt_alpha_cols":             # (A, lda, W, C, ldc, bias, R, ldr, M, N, Kp, alpha, alpha_cols)
-            a = args
-            name, args = "siss_gemm_nt", [a[0], a[1], a[2], a[3], a[4], a[5], None, a[9], a[6], a[7], a[8], a[9], a[10], 1,
-                                          int_array([0]), int_array([0]), 1, 0, 0, a[11], 1, 0, 0, 0]
-        elif name == "siss_gemm_nt_geglu_bwd":              # (A, lda, W, dh, h, rows_x, M, N, Kp)
-            a = args
-            name, args = "siss_gemm_nt", [a[0], a[1], a[2], a[3], 2 * a[7], None, None, a[7], None, 0, a[6], a[7], a[8], 1,
-                                          int_array([0]), int_array([0]), 1, 0, 0, 1.0, 1, 0, 0, 0]
-        elif name == "siss_gemm_nt_geglu_fwd":              # (A, lda, W, bias, h, y, M, F, Kp)
-            a = args
-            name, args = "siss_gemm_nt", [a[0], a[1], a[2], a[4], 2 * a[7], a[3], None, 0, None, 0, a[6], 2 * a[7], a[8], 1,
-                                          int_array([0]), int_array([0]), 1, 0, 0, 1.0, 1, 0, 0, 0]
-        elif name == "siss_gemm_tn_bs":
-            name, args = "siss_gemm_tn", list(args[:20])
-        elif name == "siss_gemm_nt_d2s_bias":               # (A, lda, W, C, ldc, bias, M, N, Kp, npanels, shifts, coffs, rpi, Hp, Wp, plane)
-            a = args
-            name, args = "siss_gemm_nt", [a[0], a[1], a[2], a[3], a[4], a[5], None, a[7], None, 0, a[6], a[7], a[8], a[9],
-                                          a[10], a[11], a[12], a[13], a[14], 1.0, 1, 0, 0, 0]
-        elif name == "siss_gemm_nt_d2s_phases":             # (A, lda, W, C, ldc, bias, R, ldr, M, N, Kp, phase_p0, shifts, coffs, rpi, Hp, Wp)
-            a = args
-            name, args = "siss_gemm_nt", [a[0], a[1], a[2], a[3], a[4], a[5], None, a[9], a[6], a[7], a[8], a[9], a[10], a[11][4],
-                                          a[12], a[13], a[14], a[15], a[16], 1.0, 1, 0, 0, 0, "4 planes"]
-        elif name == "siss_gemm_nt_d2s":
-            a = args
-            name, args = "siss_gemm_nt", [a[0], a[1], a[2], a[3], a[4], None, None, a[8], a[5], a[6], a[7], a[8], a[9], a[10],
-                                          a[11], a[12], a[13], a[14], a[15], 1.0, 1, 0, 0, 0]
-        elif name == "siss_groupnorm_fwd_qs":
-            name, args = "siss_groupnorm_fwd_ld", list(args[:7]) + list(args[10:])
-        if name == "siss_groupnorm_bwd_ld_s2d":
-            name = "siss_groupnorm_bwd_ld"
-        base = name[:-3] if name.endswith("_ld") else name          # row-stride variants count as their plain form
-        if base.endswith("_merged"):
-            base = base[:-7]
-        if base in ("siss_conv3x3_sc", "siss_conv3x3_dgrad_sc"):
-            base = "siss_gemm_nt"
-        PROF.append((base, s, e, _work(name, args), _shape_key(name, args), kernel_symbol(name, args), hbm_bytes(name, args)))
-    else:
-        rc = fn(*conv, stream_ptr())
+        base, *fields = prof.account(name, dict(zip(PARAMS[name], args)))
+        PROF.append((base, s, e, *fields))
     if rc == 1 and refusable:
         if PROF is not None:
             PROF.pop()                      # nothing ran

@@ -40,17 +40,79 @@ def test_library_exports_every_declared_symbol():
     assert lib.abi_version() >= lib.MIN_ABI
 
 
-def test_ctypes_table_has_the_arity_of_every_prototype():
-    """siss_amd/lib.py's argument table against include/siss_hip.h: every entry point is bound with as many arguments as its
-    prototype declares (the launchers' trailing `void* stream` included: lib.call appends its VALUE) -- a signature that drifts
-    from the header would otherwise only show as garbage arguments on the GPU."""
+def test_prototype_parser_maps_every_c_form_and_refuses_the_rest():
+    """siss_amd/lib.py derives its ctypes table from include/siss_hip.h (the launchers' trailing `void* stream` included:
+    lib.call appends its VALUE), so the mapper IS the binding: one hand-written prototype per C form the header uses, with the
+    ctypes it must give -- a wrong type here would otherwise only show as garbage arguments on the GPU."""
+    import ctypes as C
     from siss_amd import lib
-    h = open(os.path.join(ROOT, "include", "siss_hip.h")).read()
-    protos = dict(re.findall(r"\b(?:int|long) (siss_\w+)\(([^;{]*?)\)\s*;", h, flags=re.S))
-    assert len(protos) == len(lib.SIGNATURES)
-    for name, args in protos.items():
-        params = [a.strip() for a in args.replace("\n", " ").split(",") if a.strip() and a.strip() != "void"]
-        assert len(lib.SIGNATURES[name]) == len(params), (name, len(lib.SIGNATURES[name]), params)
+    IP = C.POINTER(C.c_int)
+    got = lib.parse_prototypes("""
+        /* a comment with a prototype in it: int siss_not_this(int x); */
+        long siss_words(int B, long chw);
+        int siss_none(void);
+        int siss_scalars(int a, long b, float c, double d, void* stream);
+        int siss_pointers(const void* x, float* y, const float* u, double* p, const double* q, const int64_t* t,
+            siss_tn_job* jobs, const siss_rk_terms* terms, void* stream);
+        int siss_int_arrays(const int* shifts, int* written, const
+            int* coffs);
+    """)
+    want = {"siss_words": (C.c_long, [(C.c_int, "B"), (C.c_long, "chw")]),
+            "siss_none": (C.c_int, []),
+            "siss_scalars": (C.c_int, [(C.c_int, "a"), (C.c_long, "b"), (C.c_float, "c"), (C.c_double, "d"), (C.c_void_p, "stream")]),
+            "siss_pointers": (C.c_int, [(C.c_void_p, n) for n in ("x", "y", "u", "p", "q", "t", "jobs", "terms", "stream")]),
+            "siss_int_arrays": (C.c_int, [(IP, "shifts"), (IP, "written"), (IP, "coffs")])}
+    assert got == want
+    for bad in ("int siss_bad(unsigned n, void* stream);", "int siss_bad(void** rows);", "int siss_bad(size_t n);",
+                "int siss_bad(int n[9]);", "int siss_bad(int);"):
+        with pytest.raises(TypeError, match="siss_bad"):
+            lib.parse_prototypes(bad)
+    # the table of the package is this parser over the committed header, names beside types
+    assert {n: len(v) for n, v in lib.PARAMS.items()} == {n: len(v) for n, v in lib.SIGNATURES.items()}
+    assert lib.PARAMS["siss_gemm_nt"][10:14] == ("M", "N", "Kp", "npanels") and lib.PARAMS["siss_gemm_nt"][-1] == "stream"
+    assert lib.RESTYPE["siss_gn_partial_words"] is C.c_long and lib.RESTYPE["siss_gemm_nt"] is C.c_int
+    # every f32 form is bound with its bf16 sibling's types (also refused at import: the header's "same argument lists")
+    assert len(lib.F32_ENTRY) == 43
+    for b_, f_ in lib.F32_ENTRY.items():
+        assert lib.SIGNATURES[b_] == lib.SIGNATURES[f_], (b_, f_)
+    assert not (lib.F32_SAME & set(lib.F32_ENTRY)) and lib.F32_SAME <= set(lib.SIGNATURES)
+
+
+def test_committed_header_is_the_generated_one():
+    """include/siss_hip.h (what lib.py binds from) against tools/gen_header.py over the sources of THIS tree, byte for byte, and
+    DESIGN.md's export sentence with it: a launcher edited without regenerating fails here, not on the GPU."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    try:
+        import gen_header
+    finally:
+        sys.path.pop(0)
+    text, names = gen_header.generate()
+    assert text == open(os.path.join(ROOT, "include", "siss_hip.h")).read()
+    assert sorted(names) == _header_symbols() and len(set(names)) == len(names)
+    assert "<!--exports-->" + gen_header.export_sentence(names) + "<!--/exports-->" in open(os.path.join(ROOT, "DESIGN.md")).read()
+
+
+def test_hand_written_structs_and_kernel_ids_mirror_the_c_side():
+    """lib.TNJob / lib.RkTerms field for field (name, order, type) against the `typedef struct` bodies of the header, and
+    lib.KERNEL_IDS against enum SissKernelId of csrc/common.h: exactly the values 0 .. SISS_K_COUNT - 1."""
+    import ctypes as C
+    from siss_amd import lib
+    h = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "siss_hip.h")).read(), flags=re.S)
+    scalar = {"int": C.c_int, "long": C.c_long, "float": C.c_float, "double": C.c_double}
+    for cname, cls in (("siss_tn_job", lib.TNJob), ("siss_rk_terms", lib.RkTerms)):
+        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (cname, cname), h, flags=re.S).group(1)
+        fields = []
+        for decl in filter(None, (" ".join(d.split()) for d in body.split(";"))):
+            m = re.fullmatch(r"(?:const )?(\w+)(\*?) (.+)", decl)
+            base = C.c_void_p if m.group(2) else scalar[m.group(1)]
+            for item in m.group(3).split(","):                   # `int N, C, npanels` / `int shifts[9]` / `const double* row[8]`
+                n = re.fullmatch(r"(\w+)(?:\[(\d+)\])?", item.strip())
+                fields.append((n.group(1), base * int(n.group(2)) if n.group(2) else base))
+        assert cls._fields_ == fields, cname
+    enum = re.search(r"enum SissKernelId \{(.*?)\}", open(os.path.join(ROOT, "siss_amd", "csrc", "common.h")).read(), flags=re.S).group(1)
+    ids = [e.split("=")[0].strip() for e in enum.split(",")]
+    assert ids[-1] == "SISS_K_COUNT" and "= 0" in enum.split(",")[0] and enum.count("=") == 1
+    assert sorted(lib.KERNEL_IDS.values()) == list(range(len(ids) - 1))
 
 
 def test_no_cpu_fallback_when_library_missing(monkeypatch, tmp_path):
