@@ -174,6 +174,7 @@ TARGET_REMAP = {
     "metrics.song_likelihood.sde_lib.VPSDE": "siss_amd.likelihood.VPSDE",
     "metrics.song_likelihood.sde_lib.VESDE": "siss_amd.likelihood.VESDE",          # (refused when built)
     "metrics.song_likelihood.sde_lib.subVPSDE": "siss_amd.likelihood.subVPSDE",    # (refused when built)
+    "metrics.class_membership.MembershipLoss": "siss_amd.membership.MembershipLoss",
     "metrics.classifier.Classifier": "siss_amd.classifier.Classifier",
     "metrics.inception_score.InceptionScore": "siss_amd.classifier.InceptionScore",
     "metrics.mnist_resnet.resnet18": "siss_amd.classifier.resnet18",

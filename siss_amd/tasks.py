@@ -210,7 +210,79 @@ class _DeleteBase(Task):
         return freq, lambda global_step: log_likelihood(evaluator, unet, image, global_step, out, gen)
 
     def check_metrics(self):
-        """Refuse, before the first step, a metrics block that cannot run (a host-side check: no GPU needed).  Nothing here."""
+        """Refuse, before the first step, a metrics block that cannot run (a host-side check: no GPU needed)."""
+        self.check_membership()
+
+    membership_supported = True
+
+    def check_membership(self, n_all=None, n_deletion=None):
+        """metrics.membership_loss needs class_cfg, a positive step_frequency (unless plot_params stops the run before the first
+        step), a non-empty timesteps list within [0, num_train_timesteps) and -- once the datasets' lengths are known -- no more
+        num_image_samples than random.sample can draw from either of them (a forget set of length 1 is repeated instead)."""
+        cfg = self.cfg
+        ml = (cfg.get("metrics") or {}).get("membership_loss")
+        if not ml:
+            return None
+        if not self.membership_supported:
+            raise NotImplementedError("metrics.membership_loss: built for the pixel-space tasks (DeleteCeleb, DeleteTShirt) only")
+        cc = ml.get("class_cfg")
+        if not cc:
+            raise ValueError("metrics.membership_loss needs class_cfg (metrics.class_membership.MembershipLoss and its sample counts)")
+        positive = lambda v: isinstance(v, int) and not isinstance(v, bool) and v > 0
+        T = int((cfg.get("scheduler") or {}).get("num_train_timesteps", 1000))
+        plot = ml.get("plot_params")
+        if plot:
+            if not positive(plot.get("time_frequency")):
+                raise ValueError(f"metrics.membership_loss.plot_params.time_frequency={plot.get('time_frequency')!r}: a positive "
+                                 "timestep stride is needed")
+        else:
+            if not positive(ml.get("step_frequency")):
+                raise ValueError(f"metrics.membership_loss.step_frequency={ml.get('step_frequency')!r}: a positive step count is needed")
+            ts = ml.get("timesteps")
+            if not isinstance(ts, list) or len(ts) == 0:
+                raise ValueError(f"metrics.membership_loss.timesteps={ts!r}: a non-empty list of timesteps is needed")
+            bad = [t for t in ts if not (isinstance(t, int) and not isinstance(t, bool) and 0 <= t < T)]
+            if bad:
+                raise ValueError(f"metrics.membership_loss.timesteps: {bad} outside [0, num_train_timesteps = {T})")
+        for key in ("num_image_samples", "num_noise_samples", "eval_batch_size"):
+            if not positive(cc.get(key)):
+                raise ValueError(f"metrics.membership_loss.class_cfg.{key}={cc.get(key)!r}: a positive count is needed")
+        n = cc.get("num_image_samples")
+        for what, have in (("dataset_all", n_all), ("dataset_deletion", n_deletion)):
+            if have is not None and n > have and not (what == "dataset_deletion" and have == 1):
+                raise ValueError(f"metrics.membership_loss.class_cfg.num_image_samples={n} is larger than {what} ({have} images): "
+                                 "random.sample cannot draw that many")
+        return ml
+
+    def membership_metric(self, unet, sched, ds_all, ds_del, device):
+        """`metrics.membership_loss` (class_cfg, timesteps, step_frequency, plot_params) of the reference's configs
+        (delete_celeb.py:438-462, :512-518).  OPT-IN (absent from the repo's configs): None when not configured.  The images and the
+        noises are drawn ONCE, here (the noises from a generator of its own, seeded from random_seed).  Returns
+        (step_frequency, log(global_step)); each evaluation appends {global_step, seconds, all_membership_loss_t=<t>,
+        deletion_membership_loss_t=<t>, membership_ratio_t=<t>} to membership_rank0.jsonl.  With plot_params the kept-group curve over
+        range(0, num_train_timesteps, time_frequency) goes to membership_curve_rank0.json and (None, None) is returned: the run
+        stops there, as the reference's does."""
+        cfg = self.cfg
+        ml = self.check_membership(len(ds_all), len(ds_del))
+        if not ml:
+            return None
+        from .membership import log_membership
+        metric = hydra_lite.instantiate(ml.class_cfg, dataset_all=ds_all, dataset_deletion=ds_del, noise_scheduler=sched, unet=unet,
+                                        device=device)
+        metric.sample_images()
+        metric.sample_noises(generator=torch.Generator(device=device).manual_seed(self.seed()))
+        plot = ml.get("plot_params")
+        if plot:
+            timesteps = list(range(0, int(sched.config.num_train_timesteps), int(plot.time_frequency)))
+            metric.compute_membership_losses(timesteps)
+            means = metric.means.cpu()
+            with open(os.path.join(cfg.output_dir, "membership_curve_rank0.json"), "w") as f:
+                json.dump(dict(timesteps=timesteps, all_membership_loss=means[:, 0].float().tolist(),
+                               deletion_membership_loss=means[:, 1].float().tolist()), f)
+            return None, None
+        timesteps = [int(t) for t in ml.timesteps]
+        out = os.path.join(cfg.output_dir, "membership_rank0.jsonl")
+        return int(ml.step_frequency), lambda global_step: log_membership(metric, timesteps, global_step, out)
 
     def deletion_metrics(self, unet, sched, forget_image, device):
         """The tracker of the configured deletion metrics (a callable of global_step), or None: none here."""
@@ -269,6 +341,13 @@ class _DeleteBase(Task):
         metrics = self.deletion_metrics(unet, sched, ds_del[0], device) if rank == 0 else None
         if metrics is not None:
             metrics(0)
+        membership = self.membership_metric(unet, sched, ds_all, ds_del, device) if rank == 0 else None
+        if ((cfg.get("metrics") or {}).get("membership_loss") or {}).get("plot_params"):
+            it_all.close()                               # the curve is the run (delete_celeb.py:444-462 exits here)
+            log.close()
+            return stepper
+        if membership is not None:
+            membership[1](0)
 
         def write_log(handle, meta):
             st = handle.get()
@@ -306,6 +385,8 @@ class _DeleteBase(Task):
                     likelihood[1](step + 1)
                 if metrics is not None:
                     metrics(step + 1)
+                if membership is not None and (step + 1) % membership[0] == 0:
+                    membership[1](step + 1)
         finally:
             # the last COMPLETED optimizer step reaches the log also when the next one raises or the job is interrupted
             if pending is not None:
@@ -336,6 +417,7 @@ class DeleteTShirt(_DeleteBase):
     def check_metrics(self):
         """metrics.fraction_deletion needs a positive sampling_steps; metrics.inception_score needs metrics.classifier_cfg, a positive
         step_frequency and, when classifier_ckpt is set, that file on disk -- all refused here, before the first step."""
+        super().check_metrics()
         cfg = self.cfg
         m = cfg.get("metrics") or {}
         if m.get("fraction_deletion"):
@@ -413,6 +495,7 @@ class DeleteSD(_DeleteBase):
     the reference's own ``using_augmented_prompt`` branch, delete_sd.py:938) and synthetic otherwise."""
     default_unet = staticmethod(UNet2DConditionConfig.sd15)
     VAE_SCALE = 0.18215            # vae.config.scaling_factor (delete_sd.py:883,888)
+    membership_supported = False   # (delete_sd.py has no membership loss)
     vae = None
     text_encoder = None
 
