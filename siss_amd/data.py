@@ -63,6 +63,58 @@ class CelebAHQ(torch.utils.data.Dataset):
         return self.transform(img) if self.transform else img
 
 
+class SDData(torch.utils.data.Dataset):
+    """Image directory split by a labels file (data/src/sd_dataset.py:8-42): `labels_fpath` is a JSON object file name -> 0 / 1
+    (kmeans_labels.json, 1 = memorized; tools/make_sd_clusters.py writes it), kept in the file's order; filter in {all, deletion
+    (label 1), nondeletion (label 0)}.  Items are (image, label): the image float [3, H, W] in 0..255 (torchvision's read_image
+    cast to float; decoded with PIL here, an RGBA / grey file converted to RGB) through `transform`, the label an int64 scalar.
+    As in the reference the path is `img_dir + name`: img_dir ends in a separator."""
+
+    def __init__(self, img_dir, labels_fpath, filter, transform=None):
+        import json
+        with open(labels_fpath, "r") as f:
+            labels = json.load(f)
+        all_names = list(labels.keys())
+        all_labels = torch.tensor(list(labels.values()), dtype=torch.int64)
+        if filter == "all":
+            idx = torch.arange(all_labels.shape[0])
+        elif filter == "deletion":
+            idx = torch.where(all_labels == 1)[0]
+        elif filter == "nondeletion":
+            idx = torch.where(all_labels == 0)[0]
+        else:
+            raise ValueError("Invalid filter.")
+        self.img_dir = img_dir
+        self.img_names = [all_names[i] for i in idx.tolist()]
+        self.img_labels = all_labels[idx]
+        self.transform = transform
+
+    def __len__(self):
+        return len(self.img_names)
+
+    def __getitem__(self, idx):
+        from PIL import Image
+        with Image.open(str(self.img_dir) + self.img_names[idx]) as im:
+            a = np.array(im.convert("RGB"), dtype=np.uint8)
+        img = torch.from_numpy(a).permute(2, 0, 1).contiguous().to(torch.float)
+        if self.transform:
+            img = self.transform(img)
+        return img, self.img_labels[idx]
+
+
+class ImagesOnly(torch.utils.data.Dataset):
+    """The images of a dataset whose items are (image, label): what the loop stacks into a batch (delete_sd.py takes batch[0])."""
+
+    def __init__(self, dataset):
+        self.dataset = dataset
+
+    def __len__(self):
+        return len(self.dataset)
+
+    def __getitem__(self, i):
+        return self.dataset[i][0]
+
+
 class SyntheticImages(torch.utils.data.Dataset):
     """x ~ U[-1,1] images of a fixed shape (ToTensor+Normalize(0.5,0.5) range), or scale * N(0,1) "latents"
     (normal=True: the SD task's stand-in for VAE latents); deterministic per index."""

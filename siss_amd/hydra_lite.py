@@ -148,7 +148,9 @@ def compose(config_name, config_path="config", overrides=()):
         cur = merged
         parts = key.split(".")
         for p in parts[:-1]:
-            cur = cur.setdefault(p, {})
+            if cur.get(p) is None:            # a null placeholder (metrics.fraction_deletion: null) takes children like an absent key
+                cur[p] = {}
+            cur = cur[p]
         cur[parts[-1]] = yaml.safe_load(val)
     cfg = Cfg(merged)
     object.__setattr__(cfg, "_raw", merged)
@@ -170,6 +172,7 @@ TARGET_REMAP = {
     "torchvision.transforms.ToTensor": "siss_amd.data.ToTensor",
     "torchvision.transforms.Normalize": "siss_amd.data.Normalize",
     "data.src.celeb_dataset.CelebAHQ": "siss_amd.data.CelebAHQ",
+    "data.src.sd_dataset.SDData": "siss_amd.data.SDData",
     "metrics.likelihood.LikelihoodEvaluator": "siss_amd.likelihood.LikelihoodEvaluator",
     "metrics.song_likelihood.sde_lib.VPSDE": "siss_amd.likelihood.VPSDE",
     "metrics.song_likelihood.sde_lib.VESDE": "siss_amd.likelihood.VESDE",          # (refused when built)

@@ -87,14 +87,15 @@ class SDSampler:
                  num_images_per_prompt=1, generator=None, latents=None, output_type="pil", track_noise_norm=True,
                  height=None, width=None, eta=0.0, lp=2):
         """prompt_embeds [B, L, X].  Returns (images, {"uncond_noise_norm", "text_noise_norm"}): images a list of PIL images
-        ("pil"), a uint8 [n, H, W, 3] array ("np") or the final latents ("latent"); the norms per image and denoising step,
-        in step order (empty without guidance)."""
+        ("pil"), a uint8 [n, H, W, 3] array ("np"), the final latents ("latent") or the VAE decoder's raw output [n, 3, H, W] on the
+        device ("decoded": what KMeansClassifier.from_decoded turns into the uint8 images and their labels without leaving it); the
+        norms per image and denoising step, in step order (empty without guidance)."""
         if eta != 0.0:
             raise NotImplementedError(f"eta={eta}: only the deterministic DDIM step (eta = 0) is implemented")
         if lp != 2:
             raise NotImplementedError(f"lp={lp}: only the L2 noise norm is implemented")
-        if output_type not in ("pil", "np", "latent"):
-            raise ValueError(f"output_type={output_type!r}: one of 'pil', 'np', 'latent'")
+        if output_type not in ("pil", "np", "latent", "decoded"):
+            raise ValueError(f"output_type={output_type!r}: one of 'pil', 'np', 'latent', 'decoded'")
         if output_type != "latent" and self.vae is None:
             raise ValueError(f"output_type={output_type!r} needs a VAE decoder")
         unet = self.unet
@@ -141,6 +142,8 @@ class SDSampler:
         if output_type == "latent":
             return x, stats
         img = self.vae.decode(x / self.vae.cfg.scaling_factor)
+        if output_type == "decoded":
+            return img, stats
         u8 = ((img / 2 + 0.5).clamp(0, 1) * 255).round().to(torch.uint8).permute(0, 2, 3, 1).cpu().numpy()
         if output_type == "np":
             return u8, stats

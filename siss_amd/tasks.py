@@ -288,6 +288,9 @@ class _DeleteBase(Task):
         """The tracker of the configured deletion metrics (a callable of global_step), or None: none here."""
         return None
 
+    def fill_cfg(self):
+        """Placeholders of the config that are read from files before anything else (delete_sd.py:342-348): none here."""
+
     # -- the loop ------------------------------------------------------------------------------
     def run(self):
         cfg = self.cfg
@@ -296,6 +299,7 @@ class _DeleteBase(Task):
         torch.cuda.set_device(device)
         seed = self.seed()
         torch.manual_seed(seed + rank)
+        self.fill_cfg()
         self.check_supported()
         self.check_metrics()
         unet = self.load_unet(device)
@@ -577,11 +581,72 @@ class DeleteSD(_DeleteBase):
             lr *= int(c.gradient_accumulation_steps) * int(c.train_batch_size) * world
         return lr, (float(c.adam_beta1), float(c.adam_beta2)), float(c.adam_epsilon), float(c.adam_weight_decay)
 
+    def fill_cfg(self):
+        """delete_sd.py:343-348: with deletion.frac_deletion null and data_files.clustering_info_path on disk (tools/make_sd_clusters.py
+        writes it), frac_deletion and data_files.mem_img_path = img_dir/<images_name>_<mem_idx:03d>.png come from that file.  (The
+        reference fails without the file; here the placeholders then stay null, as they did before.)"""
+        cfg = self.cfg
+        d, df = cfg.get("deletion"), cfg.get("data_files")
+        if d is None or not df or d.get("frac_deletion") is not None:
+            return
+        path = df.get("clustering_info_path")
+        if not path or not os.path.isfile(str(path)):
+            return
+        with open(str(path), "r", encoding="utf-8") as f:
+            info = json.load(f)
+        d.frac_deletion = info["frac_deletion"]
+        name = str(cfg.images_name) + "_" + str(info["mem_idx"]).zfill(3) + ".png"
+        df.mem_img_path = os.path.join(str(df.get("img_dir") or ""), name)
+
+    kmeans = None               # metrics.fraction_deletion's classifier (check_fraction_deletion), its tracker built at the first use
+    fraction = None
+
+    def check_metrics(self):
+        super().check_metrics()
+        self.kmeans = self.check_fraction_deletion()
+
+    def check_fraction_deletion(self):
+        """metrics.fraction_deletion (delete_sd.py:224-225,:269-275; null / absent: nothing) needs classifier_path, that file on disk,
+        a vae/ in the checkpoint directory (the classifier sees decoded images), centres of 3 * resolution^2 features and exactly two
+        clusters (the reference's `preds.mean()` is a fraction only then) -- refused here, before the first step.  Returns the
+        KMeansClassifier, or None."""
+        cfg = self.cfg
+        fd = (cfg.get("metrics") or {}).get("fraction_deletion")
+        if not fd:
+            return None
+        path = fd.get("classifier_path") if isinstance(fd, dict) else None
+        if not path:
+            raise ValueError(f"metrics.fraction_deletion={fd!r}: classifier_path is needed (a scikit-learn KMeans .joblib / .pkl, or "
+                             "the .npz tools/make_sd_clusters.py writes)")
+        if not os.path.isfile(str(path)):
+            raise FileNotFoundError(f"metrics.fraction_deletion.classifier_path {path!r} is not a file on disk")
+        ckpt = str(cfg.get("pretrained_model_name_or_path") or "")
+        if not os.path.isdir(os.path.join(ckpt, "vae")):
+            raise FileNotFoundError(f"metrics.fraction_deletion classifies decoded validation images: no vae/ under {ckpt!r}")
+        from .kmeans import KMeansClassifier
+        clf = KMeansClassifier.load(str(path))
+        res = int(cfg.get("resolution") or 512)
+        if clf.n_features != 3 * res * res:
+            raise ValueError(f"metrics.fraction_deletion: the classifier's centres have {clf.n_features} features, images of "
+                             f"resolution {res} have 3 * {res}^2 = {3 * res * res}")
+        if clf.n_clusters != 2:
+            raise ValueError(f"metrics.fraction_deletion: {clf.n_clusters} clusters; the deletion fraction is the mean label, a "
+                             "fraction only for two (label 1 = memorized)")
+        if not cfg.get("eval_every"):
+            print("[siss_amd] metrics.fraction_deletion is set but eval_every is not: the fraction is taken at evaluations only")
+        return clf
+
     def datasets(self, shape):
         cfg = self.cfg
         la, ld = cfg.get("latents_all"), cfg.get("latents_deletion")
         ia, idl = cfg.get("images_all"), cfg.get("images_deletion")
-        from .data import TensorImages
+        from .data import ImagesOnly, TensorImages
+        df = cfg.get("data_files") or {}
+        img_dir, lp = df.get("img_dir"), df.get("labels_path")
+        if self.vae is not None and img_dir and lp and os.path.isdir(str(img_dir)) and os.path.isfile(str(lp)):
+            # delete_sd.py:656,:681-682: the image directory split by kmeans_labels.json; the loop takes batch[0], the images
+            kw = dict(img_dir=str(img_dir), labels_fpath=str(lp), transform=hydra_lite.instantiate(cfg.get("data_transforms")))
+            return ImagesOnly(hydra_lite.instantiate(cfg.all_data, **kw)), ImagesOnly(hydra_lite.instantiate(cfg.memorized_data, **kw))
         if self.vae is not None and ia and idl and os.path.exists(str(ia)) and os.path.exists(str(idl)):
             return TensorImages(torch.load(ia)), TensorImages(torch.load(idl))     # [N,3,H,W] in [-1,1]: encoded per batch
         if la and ld and os.path.exists(str(la)) and os.path.exists(str(ld)):
@@ -659,7 +724,11 @@ class DeleteSD(_DeleteBase):
         eval_batch_size images (DDIM, pipeline.num_inference_steps or 50 steps, guidance 7.5) from ONE generator seeded from
         cfg.seed per evaluation (:213-218), written as a PNG grid (nrow = int(sqrt(N)), :246), and the per-step text-conditional
         and unconditional noise norms averaged over the images, index 0 = the smallest timestep (:284-291), appended to
-        noise_norms_rank0.jsonl.  Opt-in through eval_every; its own RNG; the engine's weights are only read."""
+        noise_norms_rank0.jsonl.  Opt-in through eval_every; its own RNG; the engine's weights are only read.  With
+        metrics.fraction_deletion the decoder's output goes to the k-means classifier on the device (one fused launch yields the grid's
+        uint8 images and the distances, one more the labels): {global_step, deletion_fraction_<i>} per prompt -- the mean label over
+        the eval_batches x eval_batch_size images (:271-273) -- is appended to metrics_rank0.jsonl, with deletion_steps_<i> on the
+        first evaluation whose fraction is 0 (:274-275)."""
         import numpy as np
         cfg = self.cfg
         sampler = self.pipeline or self._validation_pipeline(unet, device)
@@ -668,17 +737,30 @@ class DeleteSD(_DeleteBase):
         vp = cfg.get("validation_prompts") or [None]
         g = torch.Generator(device=device).manual_seed(self.seed())
         out_type = "np" if sampler.vae is not None else "latent"
+        if self.kmeans is not None:
+            from .kmeans import DeletionFraction
+            if sampler.vae is None:
+                raise FileNotFoundError("metrics.fraction_deletion: the validation pipeline has no VAE decoder")
+            out_type = "decoded"
+            if self.fraction is None:
+                self.fraction = DeletionFraction(self.kmeans, os.path.join(cfg.output_dir, "metrics_rank0.jsonl"))
         with sampler.holding_graphs():
             for i, p in enumerate(vp):
                 e = self._prompt_embedding(p, device)
-                imgs, text_n, uncond_n = [], [], []
+                imgs, text_n, uncond_n, labels = [], [], [], []
                 for _ in range(nb):
                     im, st = sampler(e, negative_prompt_embeds=self._negative_embeds, num_inference_steps=steps,
                                      guidance_scale=7.5, num_images_per_prompt=bs, generator=g, output_type=out_type)
-                    if out_type == "np":
+                    if out_type == "decoded":
+                        im, lab, _ = self.kmeans.from_decoded(im)       # uint8 [n, H, W, 3] + labels, still on the device
+                        labels.append(lab)
+                        imgs.extend(list(im.cpu().numpy()))
+                    elif out_type == "np":
                         imgs.extend(list(im))
                     text_n.extend(st["text_noise_norm"])
                     uncond_n.extend(st["uncond_noise_norm"])
+                if labels:
+                    self.fraction.record(i, torch.cat(labels).cpu(), step)
                 if imgs:
                     _grid(imgs, int(np.sqrt(len(imgs)))).save(os.path.join(cfg.output_dir, f"validation_p{i}_step{step}.png"))
                 rec = {"step": step, "prompt": i, "prompt_text": None if p is None else str(p),

@@ -21,11 +21,12 @@ DOCS = {
     'transformer.hip': "Token-space pieces of the SD UNet's Transformer2DModel (diffusers BasicTransformerBlock: LayerNorm,\n * GEGLU feed-forward, multi-head self / cross attention reshapes and softmax).  Call site: delete_sd.py:977-985\n * -> losses/ddpm_deletion_loss.py:24 with conditioning['encoder_hidden_states'].",
     'likelihood.hip': "The forget-set likelihood metric (metrics/likelihood.py + metrics/song_likelihood of the reference): the probability-flow\n * drift of the VP-SDE with its Hutchinson divergence (get_div_fn) and the f64 stage / error-norm arithmetic of scipy's RK45\n * (solve_ivp) over the joint state [x ; delta log p].",
     'membership.hip': "The membership-loss metric (metrics/class_membership.py of the reference, MembershipLoss.compute_membership_losses):\n * the (image, noise, timestep) work items of an evaluation noised straight into the forward's input and their squared errors\n * summed per pair, both driven by one device index table -- replaces the three expanded I x J tensors, add_noise x2 and\n * torch.sum((out - noise) ** 2) of :77-110.",
+    'kmeans.hip': "The SD deletion fraction (delete_sd.py:224-225,:269-275: joblib's scikit-learn KMeans.predict on 255 * ToTensor(PIL) of the\n * validation images, on the CPU) and the fit that produces that classifier: the decoder's output to uint8 with its distances to the\n * centres in one pass, Lloyd's assignment and update over uint8 rows; f64 / integer sums in fixed orders, no atomics.",
     'classifier.hip': "The MNIST ResNet-18 of the quality metrics (metrics/mnist_resnet.py behind metrics/classifier.py and\n * metrics/inception_score.py), f32: one implicit-GEMM convolution (NHWC gather with zero fill, folded-BN bias, residual, ReLU,\n * deterministic split-K) for every layer and fc, and nn.MaxPool2d(3, 2, 1).",
     'timeemb.hip': "Sinusoidal timestep embedding (diffusers Timesteps/get_timestep_embedding), TimestepEmbedding MLP and\n * ResnetBlock2D.time_emb_proj linears (M = batch rows), forward and backward.",
 }
 ORDER = ['siss_loss.hip', 'gemm_nt.hip', 'gemm_tn.hip', 'groupnorm.hip', 'conv_small.hip', 'attention.hip', 'attn1h.hip', 'flash_attn.hip', 'transformer.hip',
-         'timeemb.hip', 'elementwise.hip', 'optimizer.hip', 'likelihood.hip', 'membership.hip', 'classifier.hip', 'f32_path.hip']
+         'timeemb.hip', 'elementwise.hip', 'optimizer.hip', 'likelihood.hip', 'membership.hip', 'classifier.hip', 'kmeans.hip', 'f32_path.hip']
 HEAD = '''/* siss_hip.h -- C ABI of libsiss_hip.so: the MI355X (gfx950) kernels of the SISS unlearning step.
  *
  * GENERATED by tools/gen_header.py from the .hip sources under siss_amd/csrc -- edit the sources, then regenerate.
