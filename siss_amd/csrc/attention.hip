@@ -185,11 +185,21 @@ int siss_softmax_bwd(const void* p, const void* dp, void* ds, long rows, long p_
         default: return SISS_ERR_ARG;    \
     }
 
+// 1 when the siss_mha_small_* kernels cover S tokens at head dim D: D in {8, 16, 32} and the block's f32 LDS image within 64 KiB.
+// training = 0: the forward alone (K and V: 8 S D bytes).  training = 1: the backward as well (Q, K, V, dO, delta and lse:
+// 16 S D + 8 S bytes), i.e. S <= 481 / 248 / 126 at D = 8 / 16 / 32 where the forward alone goes to 1024 / 512 / 256 -- an engine
+// that is to train asks with training = 1 BEFORE its first launch (UNetEngine.check_trainable), so that no step fails in its backward.
+int siss_mha_small_takes(int S, int D, int training) {
+    if (S <= 0 || !(D == 8 || D == 16 || D == 32)) return 0;
+    const long fwd = (long)S * D * 2 * 4, bwd = ((long)S * D * 4 + 2 * S) * 4;
+    return (training ? bwd : fwd) <= 64 * 1024;
+}
+
 // o = softmax(q k^T * scale) v per (sample, head); q/k/v/o compact [N][S][C] bf16, C = heads * D; lse [N][heads][S] f32
 int siss_mha_small_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int N, int S, int C, int D,
                        float scale, void* stream) {
     SISS_CHECK_ARG(q && k && v && o && lse && N > 0 && S > 0 && C > 0 && D > 0 && C % D == 0);
-    SISS_CHECK_ARG((long)S * D * 2 * 4 <= 64 * 1024 && N <= 65535);
+    SISS_CHECK_ARG(siss_mha_small_takes(S, D, 0) && N <= 65535);
     dim3 grid(C / D, N);
     const size_t smem = (size_t)S * D * 2 * sizeof(float);
     hipStream_t st = (hipStream_t)stream;
@@ -201,7 +211,7 @@ int siss_mha_small_fwd(const void* q, const void* k, const void* v, void* o, flo
 int siss_mha_small_bwd(const void* q, const void* k, const void* v, const void* o, const float* lse, const void* dout,
                        void* dq, void* dk, void* dv, int n2, int nx, int S, int C, int D, float scale, void* stream) {
     SISS_CHECK_ARG(q && k && v && o && lse && dout && dq && dk && dv && n2 > 0 && nx > 0 && S > 0 && C % D == 0);
-    SISS_CHECK_ARG(((long)S * D * 4 + 2 * S) * 4 <= 64 * 1024 && n2 <= 65535);
+    SISS_CHECK_ARG(siss_mha_small_takes(S, D, 1) && n2 <= 65535);
     dim3 grid(C / D, n2);
     const size_t smem = ((size_t)S * D * 4 + 2 * S) * sizeof(float);
     hipStream_t st = (hipStream_t)stream;
@@ -214,7 +224,7 @@ int siss_mha_small_bwd(const void* q, const void* k, const void* v, const void* 
 int siss_mha_small_fwd_f32(const void* q, const void* k, const void* v, void* o, float* lse, int N, int S, int C, int D,
                            float scale, void* stream) {
     SISS_CHECK_ARG(q && k && v && o && lse && N > 0 && S > 0 && C > 0 && D > 0 && C % D == 0);
-    SISS_CHECK_ARG((long)S * D * 2 * 4 <= 64 * 1024 && N <= 65535);
+    SISS_CHECK_ARG(siss_mha_small_takes(S, D, 0) && N <= 65535);
     dim3 grid(C / D, N);
     const size_t smem = (size_t)S * D * 2 * sizeof(float);
     hipStream_t st = (hipStream_t)stream;
@@ -224,7 +234,7 @@ int siss_mha_small_fwd_f32(const void* q, const void* k, const void* v, void* o,
 int siss_mha_small_bwd_f32(const void* q, const void* k, const void* v, const void* o, const float* lse, const void* dout,
                            void* dq, void* dk, void* dv, int n2, int nx, int S, int C, int D, float scale, void* stream) {
     SISS_CHECK_ARG(q && k && v && o && lse && dout && dq && dk && dv && n2 > 0 && nx > 0 && S > 0 && C % D == 0);
-    SISS_CHECK_ARG(((long)S * D * 4 + 2 * S) * 4 <= 64 * 1024 && n2 <= 65535);
+    SISS_CHECK_ARG(siss_mha_small_takes(S, D, 1) && n2 <= 65535);
     dim3 grid(C / D, n2);
     const size_t smem = ((size_t)S * D * 4 + 2 * S) * sizeof(float);
     hipStream_t st = (hipStream_t)stream;

@@ -43,6 +43,8 @@ class SISSStepper:
                  grad_accum=1, max_grad_norm=1.0, loss_fn=SISS, inf_guard=False, process_group=None,
                  mixed_precision="bf16", superfactor=1.0, superfactor_decay=None):
         self.e = engine
+        if hasattr(engine, "check_trainable"):
+            engine.check_trainable()                # a site without a backward kernel is refused here, not inside the first step
         dev = engine.device
         ac = alphas_cumprod.to(device=dev, dtype=torch.float32).contiguous()
         self.ac = ac

@@ -264,6 +264,49 @@ class UNetEngine:
         self._fill_key, self._fill_plan, self._fill_plans, self._fill_tables = None, None, {}, []
         self._up_w = {}
         self._vjp, self._dx, self._vjp_sums = False, None, None
+        self._mha_sites = []
+
+    # ------------------------------------------------------------------ small-head attention: which shapes train
+    @staticmethod
+    def _mha_check(S, D, training):
+        """Refuse a small-head attention site (S tokens, head dim D) that csrc/attention.hip does not take.  The forward keeps K and
+        V of a head in LDS, the backward Q, K, V and dO: the backward's limit on S is less than half the forward's
+        (siss_mha_small_takes), so a site may serve inference and still not train."""
+        if not lib.has("siss_mha_small_takes") or lib.query("siss_mha_small_takes", S, D, int(training)):
+            return
+        if training and lib.query("siss_mha_small_takes", S, D, 0):
+            raise ValueError(f"small-head attention at S = {S} tokens, D = {D}: siss_mha_small_fwd takes the shape (inference), "
+                             f"siss_mha_small_bwd does not (Q, K, V and dO of a head exceed 64 KiB of LDS): it cannot train")
+        raise ValueError(f"small-head attention at S = {S} tokens, D = {D} is not covered by siss_mha_small_fwd")
+
+    def mha_small_sites(self, sample_size=None):
+        """(S, D) of every attention site of the configuration that runs on the small-head kernels, at square samples of
+        sample_size (default: the configuration's) -- the resolution walk of forward()."""
+        cfg = self.cfg
+        res, sites = int(sample_size or cfg.sample_size), []
+
+        def site(c):
+            D = cfg.head_dim(c)
+            if D != c:
+                sites.append((res * res, D))
+        for (i, cin_b, cout_b, attn, down) in self.plan_down:
+            if attn:
+                site(cout_b)
+            if down:
+                res //= 2
+        site(cfg.block_out_channels[-1])
+        for (i, cout_b, attn, up, rs) in self.plan_up:
+            if attn:
+                site(cout_b)
+            if up:
+                res *= 2
+        return sorted(set(sites))
+
+    def check_trainable(self, sample_size=None):
+        """Raise ValueError, naming S and D, when a small-head attention site of the configuration has no backward kernel at this
+        sample size.  The stepper asks when it is built: a step that cannot finish is refused before its first launch."""
+        for S, D in self.mha_small_sites(sample_size):
+            self._mha_check(S, D, training=True)
 
     # ------------------------------------------------------------------ parameters
     def _early_blocks(self):
@@ -946,6 +989,9 @@ class UNetEngine:
             return self._attention_fused(x, pre)
         small = D != C
         assert not small or D in (8, 16, 32), f"attention_head_dim {D} is not covered by the HIP kernels"
+        if small:
+            self._mha_check(S, D, training=False)
+            self._mha_sites.append((S, D))          # backward() / input_vjp() ask about these before their first launch
         scale = D ** -0.5
         rows = B * S
         nm = self._name(pre)
@@ -1367,6 +1413,7 @@ class UNetEngine:
         self._pair1 = []
         self._wq_post = []
         self._qs_cache = {}
+        self._mha_sites = []
         if self._wT_stale:                             # the dgrad weight copies of the last optimizer step: beside this forward pass
             st = self._side_stream()
             st.wait_stream(torch.cuda.current_stream())
@@ -1598,6 +1645,8 @@ class UNetEngine:
         forward (SISS) nb = 2*N: rows [0,N) seed g_x and rows [N,2N) seed g_a.  Gradients are
         ACCUMULATED into ps.grads[grad_base_set + set] (call zero_grad() at the start of a step).
         dx: [nb, Cin, H, W] f32, also receives the cotangent of the input image (the weight gradients are unchanged)."""
+        for S, D in self._mha_sites:                 # before the first launch of the pass, not inside an attention site's bwd()
+            self._mha_check(S, D, training=True)
         with lib.f32_mode(self.f32):
             self._dx = self._check_dx(dx, cot)
             try:
@@ -1622,6 +1671,8 @@ class UNetEngine:
         assert cot.is_cuda and cot.dtype == torch.float32 and cot.is_contiguous()
         N = cot.shape[0]
         assert N == self.nf, "input_vjp: one cotangent per sample of the last forward()"
+        for S, D in self._mha_sites:
+            self._mha_check(S, D, training=True)
         if out is None:
             out = torch.empty(N, self.cfg.in_channels, *cot.shape[2:], dtype=torch.float32, device=self.device)
         ps = self.ps

@@ -54,6 +54,9 @@ class UNetCondEngine(UNetEngine):
         # kernels are bf16-only)
         self.flash = not self.f32
 
+    def mha_small_sites(self, sample_size=None):
+        return []                  # every attention site here is a transformer block (csrc/flash_attn.hip, csrc/transformer.hip)
+
     # ------------------------------------------------------------------ parameters
     def _declare_transformer(self, pre, ch):
         a, X = self.ps.add, self.cfg.cross_attention_dim

@@ -85,10 +85,11 @@ def test_groupnorm_wide_two_sets(dev, C, H, silu, split):
         _close(grads[k, 4096:4096 + C].cpu(), refs[k][2], 5e-3, f"gn dbeta set {k}")
 
 
-@pytest.mark.parametrize("C,H,W,CO", [(320, 16, 16, 4), (128, 12, 28, 3), (64, 28, 28, 1), (40, 9, 9, 4)])
+@pytest.mark.parametrize("C,H,W,CO", [(320, 16, 16, 4), (128, 12, 28, 3), (64, 28, 28, 1), (40, 9, 9, 4), (8, 9, 9, 2), (16, 12, 28, 3)])
 def test_conv_out_fprop_any_channels(dev, C, H, W, CO):
     """conv_out forward: the MFMA kernel (C % 32 == 0; weights rounded to bf16 like every conv of the path; ragged
-    16-pixel segments at W = 28) and the one-wave-per-pixel f32 kernel for other channel counts."""
+    16-pixel segments at W = 28), the one-wave-per-pixel f32 kernel for other channel counts, and the C / 8-lanes-per-pixel f32 kernel
+    for C = 8 and 16 (one and two lanes: no butterfly step, and one)."""
     from siss_amd import lib
     from siss_amd.layout import Act
     g = torch.Generator().manual_seed(5 + C)
