@@ -182,6 +182,7 @@ TARGET_REMAP = {
     "metrics.inception_score.InceptionScore": "siss_amd.classifier.InceptionScore",
     "metrics.mnist_resnet.resnet18": "siss_amd.classifier.resnet18",
     "metrics.tshirt.TShirtClassifier": "siss_amd.classifier.TShirtClassifier",
+    "metrics.fid.FIDEvaluator": "siss_amd.fid.FIDEvaluator",
     "hydra.utils.get_object": "siss_amd.hydra_lite.get_object",        # classifier: {_target_: hydra.utils.get_object, path: ...}
 }
 # the reference's other classifiers: not built (no CIFAR ResNet-56 kernels here, no network for torch.hub)

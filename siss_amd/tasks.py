@@ -410,6 +410,73 @@ class _DeleteBase(Task):
 class DeleteCeleb(_DeleteBase):
     """config/delete_celeb.yaml -- CelebA-HQ 256, forget set = listed jpgs repeated (RepeatedSampler)."""
 
+    def check_metrics(self):
+        """metrics.fid (delete_celeb.py:469-471,:532-542) needs class_cfg, a positive integer step_frequency, at least 2 images to
+        generate (a covariance needs two), a positive batch_size, a 3-channel UNet, the Inception checkpoint on disk (unless
+        class_cfg.allow_random_init) and the real-image directory (or an existing class_cfg.real_stats_path) -- all refused here,
+        before the first step."""
+        super().check_metrics()
+        cfg = self.cfg
+        fid = (cfg.get("metrics") or {}).get("fid")
+        if not fid:
+            return
+        from .fid import DEFAULT_CKPT
+        cc = fid.get("class_cfg")
+        if not cc:
+            raise ValueError("metrics.fid needs class_cfg (metrics.fid.FIDEvaluator and its inception_batch_size)")
+        positive = lambda v: isinstance(v, int) and not isinstance(v, bool) and v > 0
+        if not positive(fid.get("step_frequency")):
+            raise ValueError(f"metrics.fid.step_frequency={fid.get('step_frequency')!r}: a positive step count is needed")
+        n = fid.get("num_imgs_to_generate")
+        if not positive(n) or n < 2:
+            raise ValueError(f"metrics.fid.num_imgs_to_generate={n!r}: at least 2 images are needed (the covariance of one is undefined)")
+        if not positive(fid.get("batch_size")):
+            raise ValueError(f"metrics.fid.batch_size={fid.get('batch_size')!r}: a positive batch size is needed")
+        ch = (cfg.get("unet") or {}).get("in_channels", 3)
+        if ch != 3:
+            raise ValueError(f"metrics.fid: the Inception-v3 takes 3-channel images, the UNet has in_channels={ch!r}")
+        ckpt = str(cc.get("inception_ckpt") or DEFAULT_CKPT)
+        if not cc.get("allow_random_init") and not os.path.isfile(ckpt):
+            raise FileNotFoundError(f"metrics.fid.class_cfg.inception_ckpt {ckpt!r} is not a file on disk (pass "
+                                    "metrics.fid.class_cfg.allow_random_init=true for random-init weights of the same architecture)")
+        stats = cc.get("real_stats_path")
+        data = str(cc.get("data_path") or "data/examples/celeba_hq_256")
+        if not (stats and os.path.isfile(str(stats))) and not os.path.isdir(data):
+            raise FileNotFoundError(f"metrics.fid.class_cfg.data_path {data!r} (the real images of the FID) is not a directory on disk")
+
+    def deletion_metrics(self, unet, sched, forget_image, device):
+        """`metrics.fid` (class_cfg, step_frequency, num_imgs_to_generate, batch_size), OPT-IN: None when not configured.  The
+        evaluator is built and its real side loaded here, once, before step 0; at step 0 and every step_frequency steps
+        num_imgs_to_generate samples (`pipeline.num_inference_steps` steps, batches of batch_size, a generator of its own seeded from
+        random_seed) go through add_fake_images batch by batch (each batch comes back from Evaluator.sample_images as a host array and
+        is copied to the device again: one round trip per batch, negligible next to its sampling), and {global_step, fid, fake_images, real_images, seconds} is
+        appended to fid_rank0.jsonl (fid.FIDTracker)."""
+        cfg = self.cfg
+        fid = (cfg.get("metrics") or {}).get("fid")
+        if not fid:
+            return None
+        from .fid import FIDTracker
+        from .sampler import Evaluator
+        evaluator = hydra_lite.instantiate(fid.class_cfg, device=device)
+        evaluator.load_celeb()
+        steps = int(((cfg.get("pipeline") or {}).get("num_inference_steps")) or 50)
+        gen = torch.Generator(device=device).manual_seed(self.seed())
+        held = {}
+
+        def begin():                                     # one sampler (and its captured forward) per evaluation, as evaluate() has
+            held["ev"] = Evaluator(cfg)
+            held["ev"].load_model(unet, sched)
+
+        def end():                                       # ... dropped with its graphs and static buffers before training goes on
+            held.clear()
+
+        def sample(n):
+            imgs = held["ev"].sample_images(n, num_inference_steps=steps, generator=gen)
+            return torch.from_numpy(imgs).permute(0, 3, 1, 2).to(device)
+
+        return FIDTracker(evaluator, os.path.join(cfg.output_dir, "fid_rank0.jsonl"), sample, fid.step_frequency,
+                          fid.num_imgs_to_generate, fid.batch_size, begin=begin, end=end)
+
 
 class DeleteTShirt(_DeleteBase):
     """config/delete_tshirt.yaml -- MNIST + T-shirt: t ~ U{0..999} (delete_tshirt.py:535-540) and the

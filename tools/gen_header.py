@@ -23,10 +23,11 @@ DOCS = {
     'membership.hip': "The membership-loss metric (metrics/class_membership.py of the reference, MembershipLoss.compute_membership_losses):\n * the (image, noise, timestep) work items of an evaluation noised straight into the forward's input and their squared errors\n * summed per pair, both driven by one device index table -- replaces the three expanded I x J tensors, add_noise x2 and\n * torch.sum((out - noise) ** 2) of :77-110.",
     'kmeans.hip': "The SD deletion fraction (delete_sd.py:224-225,:269-275: joblib's scikit-learn KMeans.predict on 255 * ToTensor(PIL) of the\n * validation images, on the CPU) and the fit that produces that classifier: the decoder's output to uint8 with its distances to the\n * centres in one pass, Lloyd's assignment and update over uint8 rows; f64 / integer sums in fixed orders, no atomics.",
     'classifier.hip': "The MNIST ResNet-18 of the quality metrics (metrics/mnist_resnet.py behind metrics/classifier.py and\n * metrics/inception_score.py), f32: one implicit-GEMM convolution (NHWC gather with zero fill, folded-BN bias, residual, ReLU,\n * deterministic split-K) for every layer and fc, and nn.MaxPool2d(3, 2, 1).",
+    'inception.hip': "The FID metric (metrics/fid.py of the reference: torchmetrics' FrechetInceptionDistance on the FID Inception-v3 of\n * torch-fidelity), f32: the preprocessing (uint8 truncation, TF1 bilinear resize to 299 x 299, (x - 128) / 128) in one launch, one\n * implicit-GEMM convolution for all 94 BasicConv2d layers (independent KH / KW / padding, folded-BN bias + ReLU, written into a channel\n * slice of the Mixed block's output, deterministic split-K), the pools, and the f64 feature statistics sum / cov_sum.",
     'timeemb.hip': "Sinusoidal timestep embedding (diffusers Timesteps/get_timestep_embedding), TimestepEmbedding MLP and\n * ResnetBlock2D.time_emb_proj linears (M = batch rows), forward and backward.",
 }
 ORDER = ['siss_loss.hip', 'gemm_nt.hip', 'gemm_tn.hip', 'groupnorm.hip', 'conv_small.hip', 'attention.hip', 'attn1h.hip', 'flash_attn.hip', 'transformer.hip',
-         'timeemb.hip', 'elementwise.hip', 'optimizer.hip', 'likelihood.hip', 'membership.hip', 'classifier.hip', 'kmeans.hip', 'f32_path.hip']
+         'timeemb.hip', 'elementwise.hip', 'optimizer.hip', 'likelihood.hip', 'membership.hip', 'classifier.hip', 'inception.hip', 'kmeans.hip', 'f32_path.hip']
 HEAD = '''/* siss_hip.h -- C ABI of libsiss_hip.so: the MI355X (gfx950) kernels of the SISS unlearning step.
  *
  * GENERATED by tools/gen_header.py from the .hip sources under siss_amd/csrc -- edit the sources, then regenerate.
