@@ -14,7 +14,7 @@
 // Backward takes n2 = sets * B cotangent samples against B saved samples (x index = n2 % Bx):
 // the dual-cotangent backward of the SISS step.
 // Output / cotangent rows may be "compact" ([N][H*W][C], no halo) for the attention block.
-#include "common.h"
+#include "nt_common.h"
 
 namespace {
 
@@ -440,6 +440,23 @@ __global__ __launch_bounds__(kThreads) void gn_bwd_stats_kernel(
     }
 }
 
+// The per-element arithmetic of the backward apply, shared by gn_bwd_apply_kernel and gn_bwd_sc_kernel: xhat and SiLU'(z) gamma of one
+// saved element, then t = rstd (dz SiLU' gamma - S1 / cnt - xhat S2 / cnt); the callers add what x already carries in the order
+// accum, accum2, old dx2.  Every contraction is WRITTEN (fmaf) and none is left to the compiler (contract(off)): left to it, the
+// two-set apply kernel had two of its sixteen element slots multiply and add where the others fused, an accident of how the
+// vectoriser paired them -- and two kernels that must give the same bits cannot each depend on such accidents.  The product with
+// rstd is rounded on its own and never joins the first addition behind it.
+template <bool SILU>
+__device__ __forceinline__ void gn_bwd_xhat(float v, float rs, float mr, float ga, float be, float& xh, float& dsl) {
+#pragma clang fp contract(off)
+    xh = fmaf(v, rs, -mr);
+    dsl = (SILU ? dsilu_f(fmaf(xh, ga, be)) : 1.f) * ga;
+}
+__device__ __forceinline__ float gn_bwd_t(float d, float dsl, float xh, float rs, float m1, float m2) {
+#pragma clang fp contract(off)
+    return rs * fmaf(-xh, m2, fmaf(d, dsl, -m1));
+}
+
 // S2D (with a split target, dx2 != null): the FIRST part of the split (channels [0, split_c)) is written in SPACE-TO-DEPTH layout --
 // pixel (y, x) goes to row (y / 2, x / 2) of a (H / 2) x (W / 2) padded tensor of 4 split_c channels, columns [plane * split_c, ...),
 // plane = 2 (y & 1) + (x & 1) -- which is how a sub-pixel upsample convolution's backward wants its cotangent (unet.py
@@ -545,17 +562,14 @@ __global__ __launch_bounds__(kThreads) void gn_bwd_apply_kernel(
             float v[8], xh[8], dsl[8];
             unpack8(cur.x, v);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                xh[e] = v[e] * rs[e] - mr[e];
-                dsl[e] = (SILU ? dsilu_f(xh[e] * ga[e] + be[e]) : 1.f) * ga[e];
-            }
+            for (int e = 0; e < 8; ++e) gn_bwd_xhat<SILU>(v[e], rs[e], mr[e], ga[e], be[e], xh[e], dsl[e]);
 #pragma unroll
             for (int k = 0; k < SETS; ++k) {
                 float d[8], o[8];
                 unpack8(cur.d[k], d);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
-                    const float t = rs[e] * (d[e] * dsl[e] - m1[k][e] - xh[e] * m2[k][e]);
+                    const float t = gn_bwd_t(d[e], dsl[e], xh[e], rs[e], m1[k][e], m2[k][e]);
                     cs[k][e] += t;
                     o[e] = t;
                 }
@@ -588,6 +602,248 @@ __global__ __launch_bounds__(kThreads) void gn_bwd_apply_kernel(
             reduce_slots(cs[k], active, slot, cc, s, red, chs);
             for (int i = tid; i < s.C; i += kThreads) atomicAdd(colsum + (long)(k * nx + n) * colsum_ld + c0 + i, chs[i]);
             __syncthreads();
+        }
+    }
+}
+
+// ---------------------------------------------------------------- backward apply in the epilogue of the shortcut's dgrad
+// A resnet that changes width: norm1's backward adds the cotangent its input receives through conv_shortcut, dout . W_sc -- an
+// [M x C] tensor that a product would write and the apply pass read back, and that nothing else needs.  Here the product IS the
+// apply pass: a one-panel NT product (128 x 128 tile, BK = 64: gemm_nt_kernel's single-buffered staging and MFMA loop, same
+// accumulation order) whose epilogue rounds the tile to bf16 through LDS exactly as nt_epilogue does and then, per 16-B chunk of a
+// row (8 channels: the layout the kernels above walk in), loads the saved x and the cotangent dy of that row, forms t, adds the
+// staged product and the running cotangents and stores dx.  Rows are the flat padded rows; tiles are cut PER GRADIENT SET, so that
+// tile t of both sets covers the same saved x rows, and a row tile's column tiles and its two sets are adjacent blocks of one XCD
+// (x and dout come from HBM once).  Halo rows store zeros.  The per-(sample, group) constants (rstd, mean rstd, S1 / cnt, S2 / cnt)
+// come from gn_bwd_sc_finalize_kernel: a tile takes the <= 3 images it spans into LDS.
+struct GNSCParams {
+    const bf16_t* A; const bf16_t* Wt;     // dout [sets * Mset][lda], W_sc^T [C][K]
+    const bf16_t* x; const bf16_t* dy; const bf16_t* accum2;
+    const float* gamma; const float* beta; const f32x4_t* gconst;    // [n2][G] (rstd, mean * rstd, S1 / cnt, S2 / cnt)
+    bf16_t* dx; bf16_t* dx2;
+    long lda, ldx;
+    int K, C, G, cpg, Mset, nx, sets, rpi, H, W, split_c, accumulate2;
+    float inv_wp;
+};
+constexpr int kScTileBytes = 128 * kCRow;              // the bf16 epilogue tile (>= one 32-KiB stage)
+constexpr int kScSmemBytes = kScTileBytes + 3 * kMaxG * 16;
+
+__global__ __launch_bounds__(kThreads) void gn_bwd_sc_finalize_kernel(const float* __restrict__ partial, int pchunks,
+                                                                      const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                                      int G, int nx, double cnt, f32x4_t* __restrict__ gconst) {
+    __shared__ float fr[4][64];
+    const int n2 = blockIdx.x, tid = threadIdx.x;
+    fold_slab(partial + (long)n2 * pchunks * 2 * G, pchunks, G, fr);
+    if (tid < G) {
+        const int n = n2 % nx;
+        const float s1 = (float)(((double)fr[0][2 * tid] + fr[1][2 * tid] + fr[2][2 * tid] + fr[3][2 * tid]) / cnt);
+        const float s2 = (float)(((double)fr[0][2 * tid + 1] + fr[1][2 * tid + 1] + fr[2][2 * tid + 1] + fr[3][2 * tid + 1]) / cnt);
+        const float r = rstd[(long)n * G + tid];
+        gconst[(long)n2 * G + tid] = f32x4_t{r, mean[(long)n * G + tid] * r, s1, s2};
+    }
+}
+
+// EXTRA: the site has running cotangents to add (accum2, or an accumulated dx2) -- rare, and their loads would cost the common form
+// the registers of two more operands per row in flight.
+template <bool SILU, bool S2D, bool EXTRA>
+__global__ __launch_bounds__(kThreads, 3) void gn_bwd_sc_kernel(const GNSCParams p) {
+    constexpr int BM = 128, kPieces = BM / 8 / 4;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = w >> 1, wn = w & 1;
+    const int tiles_n = (p.C + BN - 1) / BN, tiles_m = (p.Mset + BM - 1) / BM;
+    const int nwg = tiles_n * tiles_m * p.sets;
+    int bid = blockIdx.x;
+    {   // every XCD a contiguous run of tiles (blocks b, b + 8, ... share an L2): (row tile, set, column tile), column tile fastest
+        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, k = bid >> 3;
+        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
+    }
+    const int tn = bid % tiles_n, ts = bid / tiles_n;
+    const int kset = ts % p.sets, tm = ts / p.sets;
+    const int m0 = tm * BM, n0 = tn * BN;
+    const long set_row0 = (long)kset * p.Mset;           // first flat row of this gradient set in dout / dy / dx
+    const bf16_t* A = p.A + set_row0 * p.lda;
+
+    const bf16_t* asrc[kPieces];
+    const bf16_t* wsrc[kPieces];
+#pragma unroll
+    for (int j = 0; j < kPieces; ++j) {
+        const int row = (w * kPieces + j) * 8 + (lane >> 3);
+        const int lc = (lane & 7) ^ ((row >> 1) & 7);
+        int gr = m0 + row; gr = gr < p.Mset ? gr : p.Mset - 1;
+        asrc[j] = A + (long)gr * p.lda + lc * 8;
+        int gn = n0 + row; gn = gn < p.C ? gn : p.C - 1;
+        wsrc[j] = p.Wt + (long)gn * p.K + lc * 8;
+    }
+    // the constants of the images this tile's rows lie in (at most three: rows_per_image >= 64), beside the tile in LDS
+    const int rpi = p.rpi;
+    const int img0 = m0 / rpi;
+    f32x4_t* cst = reinterpret_cast<f32x4_t*>(smem + kScTileBytes);
+    if (tid < 3 * p.G) {
+        const int slot = tid / p.G, g = tid - slot * p.G;
+        int img = img0 + slot; img = img < p.nx ? img : p.nx - 1;
+        cst[tid] = p.gconst[(long)(kset * p.nx + img) * p.G + g];
+    }
+    // this thread's 16-B chunk of the tile's rows: 8 channels, their affine parameters in registers
+    const int chunk = tid & 15, trow = tid >> 4;
+    const int nc = n0 + chunk * 8;
+    const bool cols = nc < p.C;
+    float ga[8], be[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { ga[e] = cols ? p.gamma[nc + e] : 0.f; be[e] = cols ? p.beta[nc + e] : 0.f; }
+
+    f32x4_t acc[4][4];   // [n-tile][m-tile]
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    const int frow = lane & 15, fq = lane >> 4;
+    int a_off[4], w_off[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int ra = wm * 64 + i * 16 + frow;
+        a_off[i] = ra * 128 + ((fq ^ ((ra >> 1) & 7)) << 4);
+        const int rw = wn * 64 + i * 16 + frow;
+        w_off[i] = BM * 128 + rw * 128 + ((fq ^ ((rw >> 1) & 7)) << 4);
+    }
+    const unsigned smem_a = lds_addr(smem);
+    const int steps = p.K / BK;
+    for (int s = 0; s < steps; ++s) {
+        // single buffer, two barriers per step: the other resident blocks hide the latency (gemm_nt_kernel, STAGES = 1)
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+#pragma unroll
+        for (int j = 0; j < kPieces; ++j) glds16_asm(asrc[j] + s * BK, smem_a + (w * kPieces + j) * 1024);
+#pragma unroll
+        for (int j = 0; j < kPieces; ++j) glds16_asm(wsrc[j] + s * BK, smem_a + BM * 128 + (w * kPieces + j) * 1024);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+            bf16x8_t af[4], wf[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) af[i] = *reinterpret_cast<const bf16x8_t*>(smem + (a_off[i] ^ (kk << 6)));
+#pragma unroll
+            for (int i = 0; i < 4; ++i) wf[i] = *reinterpret_cast<const bf16x8_t*>(smem + (w_off[i] ^ (kk << 6)));
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[i], af[j], acc[i][j], 0, 0, 0);
+        }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    // the product rounded to bf16, staged as nt_epilogue stages it: acc[i][j][r] = channel wn*64 + i*16 + fq*4 + r of row wm*64 + j*16 + frow
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int m = wm * 64 + j * 16 + frow;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int nl = wn * 64 + i * 16 + fq * 4;
+            const f32x4_t v = acc[i][j];
+            *reinterpret_cast<u32x2_t*>(smem + m * kCRow + nl * 2) = u32x2_t{pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])};
+        }
+    }
+    __syncthreads();
+    if (!cols) return;
+
+    // ---- the GroupNorm-backward apply over this thread's chunk of rows trow, trow + 16, ... ----
+    const int b1 = (img0 + 1) * rpi - m0, b2 = b1 + rpi;      // tile rows >= b1 / b2 lie in the next image / the one after
+    const int g0 = nc / p.cpg, rem0 = nc - g0 * p.cpg;
+    float rs[8], mr[8], m1[8], m2[8];
+    auto load_consts = [&](int slot) {
+        const f32x4_t* c = cst + slot * p.G;
+        int g = g0, rm = rem0;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {                         // (a chunk may span groups: cpg = 12 at C = 384, 3 at C = 96)
+            const f32x4_t v = c[g];
+            rs[e] = v[0]; mr[e] = v[1]; m1[e] = v[2]; m2[e] = v[3];
+            if (++rm == p.cpg) { rm = 0; ++g; }
+        }
+    };
+    int cur_slot = (trow >= b1) + (trow >= b2);
+    load_consts(cur_slot);
+    const int Wp = p.W + 2, Hp = p.H + 2;
+    const int C = p.C;
+    const bool second = p.dx2 != nullptr && nc >= p.split_c;
+    const int ostride = p.dx2 ? (second ? C - p.split_c : p.split_c) : C;
+    const bool oacc = EXTRA && second && p.accumulate2;
+    const bool any_oacc = EXTRA && p.dx2 != nullptr && p.accumulate2;
+    const bool s2d_lane = S2D && !second;
+    bf16_t* const obase = second ? p.dx2 + (nc - p.split_c) : p.dx + nc;
+    const int wl2 = (p.W >> 1) + 2;
+    const long img2 = (long)((p.H >> 1) + 2) * wl2;           // S2D: padded rows per image of the half-resolution target
+    const bf16_t* const xb = p.x + nc;
+    const bf16_t* const db = p.dy + set_row0 * C + nc;
+    const bf16_t* const bb = (EXTRA && p.accum2) ? p.accum2 + set_row0 * C + nc : nullptr;
+    constexpr int kBatch = EXTRA ? 2 : 4;                                // rows whose loads are in flight together
+    for (int it0 = 0; it0 < BM / 16; it0 += kBatch) {
+        u32x4_t vx[kBatch], vd[kBatch], vb[EXTRA ? kBatch : 1], vc[EXTRA ? kBatch : 1];
+        bf16_t* dst[kBatch];
+        int state[kBatch];                                    // 0: no store (past the last row, or a halo row of the S2D part), 1: zeros, 2: a pixel
+        int slot_of[kBatch];
+#pragma unroll
+        for (int q = 0; q < kBatch; ++q) {
+            const int row = (it0 + q) * 16 + trow;
+            const int r = m0 + row;                           // row within the set = row of the saved x
+            const int slot = (row >= b1) + (row >= b2);
+            slot_of[q] = slot;
+            const int img = img0 + slot;
+            const int rem = r - img * rpi;
+            const int y = (int)(((float)rem + 0.5f) * p.inv_wp), xq = rem - y * Wp;       // exact: see nt_common.h
+            const bool halo = (y == 0) | (y == Hp - 1) | (xq == 0) | (xq == Wp - 1);
+            state[q] = r >= p.Mset ? 0 : (halo ? (s2d_lane ? 0 : 1) : 2);
+            vx[q] = vd[q] = u32x4_t{0u, 0u, 0u, 0u};
+            if (EXTRA) vb[q] = vc[q] = u32x4_t{0u, 0u, 0u, 0u};
+            if (s2d_lane) {
+                const int yy = y - 1, xx = xq - 1;
+                dst[q] = p.dx + nc + (((long)(kset * p.nx + img) * img2 + ((yy >> 1) + 1) * wl2 + (xx >> 1) + 1) * 4 + (((yy & 1) << 1) | (xx & 1))) * p.split_c;
+            } else {
+                dst[q] = obase + (set_row0 + r) * ostride;
+            }
+            if (state[q] == 2) {
+                vx[q] = *reinterpret_cast<const u32x4_t*>(xb + (long)r * p.ldx);
+                vd[q] = *reinterpret_cast<const u32x4_t*>(db + (long)r * C);
+                if (EXTRA && bb) vb[q] = *reinterpret_cast<const u32x4_t*>(bb + (long)r * C);
+                if (EXTRA && oacc) vc[q] = *reinterpret_cast<const u32x4_t*>(dst[q]);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < kBatch; ++q) {
+            if (state[q] == 0) continue;
+            u32x4_t out = u32x4_t{0u, 0u, 0u, 0u};
+            if (state[q] == 2) {
+                if (slot_of[q] != cur_slot) { cur_slot = slot_of[q]; load_consts(cur_slot); }
+                const int row = (it0 + q) * 16 + trow;
+                float v[8], d[8], pr[8], o[8];
+                unpack8(vx[q], v);
+                unpack8(vd[q], d);
+                unpack8(*reinterpret_cast<const u32x4_t*>(smem + row * kCRow + chunk * 16), pr);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    float xh, dsl;
+                    gn_bwd_xhat<SILU>(v[e], rs[e], mr[e], ga[e], be[e], xh, dsl);
+                    o[e] = gn_bwd_t(d[e], dsl, xh, rs[e], m1[e], m2[e]);
+                }
+#pragma unroll
+                for (int e = 0; e < 8; ++e) o[e] += pr[e];
+                if (EXTRA && bb) {
+                    float r8[8];
+                    unpack8(vb[q], r8);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) o[e] += r8[e];
+                }
+                if (EXTRA && any_oacc) {
+                    float r8[8];
+                    unpack8(vc[q], r8);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) o[e] += r8[e];
+                }
+                out = pack8(o);
+            }
+            *reinterpret_cast<u32x4_t*>(dst[q]) = out;
         }
     }
 }
@@ -811,6 +1067,64 @@ int siss_groupnorm_bwd(const void* dy, const void* x, const float* gamma, const 
     return siss_groupnorm_bwd_ld(dy, x, gamma, beta, mean, rstd, dx, accum, accum2, dx2, split_c, accumulate2, dgamma, dbeta,
                                  colsum, colsum_ld, partial, n2, nx, set_images, set_stride, H, W, C, G, silu, dy_compact, 0,
                                  stream);
+}
+
+// siss_groupnorm_bwd_ld / _s2d for the norm1 of a resnet with a 1x1 conv_shortcut, with the shortcut's dgrad formed INSIDE the apply pass:
+// dx = GroupNorm-backward(dy; x) + dout . wsc (+ accum2, + old dx2), where dout (n2 padded samples of K channels, row stride ldo) is the
+// resnet's output cotangent and wsc the transposed shortcut weight [C][K] bf16 (K % 64 == 0).  Equal, bit for bit, to siss_gemm_nt
+// (one panel, halo mask, no split-K) into an [n2 rows][C] tensor followed by siss_groupnorm_bwd_ld with that tensor as `accum` -- the
+// product is rounded to bf16 where that tensor was -- without the tensor's write and read.  Three launches: the statistics pass of
+// siss_groupnorm_bwd_ld (dgamma / dbeta as there), a finalize kernel that leaves (rstd, mean rstd, S1 / cnt, S2 / cnt) per (sample,
+// group) in gconst (4 n2 G floats, 16-B aligned), and the product.  dy is padded (never compact); halo rows of the target are stored as
+// zeros (the space-to-depth part has no place for them); colsum must be null (norm1 has no use for it); C <= 1024; bf16 only.
+int siss_groupnorm_bwd_sc(const void* dy, const void* x, const float* gamma, const float* beta, const float* mean,
+                          const float* rstd, void* dx, const void* dout, long ldo, const void* wsc, int K, const void* accum2,
+                          void* dx2, int split_c, int accumulate2, float* dgamma, float* dbeta, float* colsum, float* partial,
+                          float* gconst, int n2, int nx, int set_images, long set_stride, int H, int W, int C, int G, int silu,
+                          int s2d, int ldx, void* stream) {
+    GNShape ss;
+    SISS_CHECK_ARG(!colsum);
+    SISS_CHECK_ARG(dy && x && gamma && beta && mean && rstd && dx && dout && wsc && dgamma && dbeta && partial && gconst);
+    SISS_CHECK_ARG(!s2d || (dx2 && H % 2 == 0 && W % 2 == 0));
+    SISS_CHECK_ARG(n2 > 0 && nx > 0 && set_images > 0 && n2 % set_images == 0 && (n2 == nx || n2 == 2 * nx));
+    SISS_CHECK_ARG(K > 0 && K % BK == 0 && ldo >= K && ldo % 8 == 0);
+    SISS_CHECK_ARG(make_shape(H, W, C, G, ss, nx, kBlocksBwdStats) && ss.nslices == 1);
+    SISS_CHECK_ARG(((uintptr_t)dy | (uintptr_t)x | (uintptr_t)dx | (uintptr_t)dout | (uintptr_t)wsc | (uintptr_t)accum2 | (uintptr_t)dx2 |
+                    (uintptr_t)partial | (uintptr_t)gconst) % 16 == 0);
+    SISS_CHECK_ARG(!dx2 || (split_c > 0 && split_c < C && split_c % 8 == 0));
+    SISS_CHECK_ARG(ldx == 0 || (ldx >= C && ldx % 8 == 0));
+    const long rpi = (long)(H + 2) * (W + 2);
+    SISS_CHECK_ARG(rpi >= 64 && nx * rpi < (1L << 31) - 256);          // <= 3 images per 128-row tile; rows of a set in an int
+    if (ldx) ss.ldx = ldx;
+    hipStream_t st = (hipStream_t)stream;
+    static unsigned char attr_set[2][2][2][kMaxDevices];
+    const bool extra = accum2 != nullptr || (dx2 && accumulate2);
+    const bf16_t* dyp = (const bf16_t*)dy; const bf16_t* xp = (const bf16_t*)x;
+    dim3 grid_s(ss.nchunks, nx, 1);
+#define GN_SC_STATS(SILU, SETS) \
+    gn_bwd_stats_kernel<SILU, SETS><<<grid_s, kThreads, 0, st>>>(dyp, xp, gamma, beta, mean, rstd, ss, nx, 0, set_images, set_stride, partial, dgamma, dbeta)
+    if (n2 == nx) { if (silu) { GN_SC_STATS(true, 1); } else { GN_SC_STATS(false, 1); } }
+    else          { if (silu) { GN_SC_STATS(true, 2); } else { GN_SC_STATS(false, 2); } }
+#undef GN_SC_STATS
+    gn_bwd_sc_finalize_kernel<<<n2, kThreads, 0, st>>>(partial, ss.nchunks, mean, rstd, G, nx, (double)H * W * ss.cpg, (f32x4_t*)gconst);
+    GNSCParams p;
+    p.A = (const bf16_t*)dout; p.Wt = (const bf16_t*)wsc; p.x = xp; p.dy = dyp; p.accum2 = (const bf16_t*)accum2;
+    p.gamma = gamma; p.beta = beta; p.gconst = (const f32x4_t*)gconst; p.dx = (bf16_t*)dx; p.dx2 = (bf16_t*)dx2;
+    p.lda = ldo; p.ldx = ss.ldx; p.K = K; p.C = C; p.G = G; p.cpg = ss.cpg; p.Mset = (int)(nx * rpi); p.nx = nx; p.sets = n2 / nx;
+    p.rpi = (int)rpi; p.H = H; p.W = W; p.split_c = split_c; p.accumulate2 = accumulate2; p.inv_wp = 1.0f / (float)(W + 2);
+    const unsigned blocks = (unsigned)(cdiv(p.Mset, 128) * cdiv(C, BN) * p.sets);
+#define GN_SC_(SILU, S2D_, EX)                                                                                                \
+    do {                                                                                                                      \
+        if (siss_ensure_smem((const void*)gn_bwd_sc_kernel<SILU, S2D_, EX>, kScSmemBytes, attr_set[SILU][S2D_][EX]) != SISS_OK) return SISS_ERR_LAUNCH; \
+        gn_bwd_sc_kernel<SILU, S2D_, EX><<<blocks, kThreads, kScSmemBytes, st>>>(p);                                           \
+    } while (0)
+#define GN_SC(SILU, S2D_) do { if (extra) GN_SC_(SILU, S2D_, true); else GN_SC_(SILU, S2D_, false); } while (0)
+    if (silu) { if (s2d) GN_SC(true, true); else GN_SC(true, false); }
+    else      { if (s2d) GN_SC(false, true); else GN_SC(false, false); }
+#undef GN_SC
+#undef GN_SC_
+    siss_count_dispatch(SISS_K_GN_SC);
+    SISS_LAUNCH_RET();
 }
 
 }  // extern "C"

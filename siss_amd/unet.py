@@ -160,6 +160,13 @@ class UNetEngine:
     d2s_epilogue = True    # downsample dgrad: depth-to-space in the plane GEMMs' epilogue (no dz tensor, no scatter pass)
     direct_cat = True      # convs that feed a concat write into the concat buffer directly (False: copy both parts)
     fold_shortcut = True   # a resnet's 1x1 conv_shortcut rides in its conv2's 3x3 product (False: own product + residual add)
+    # ... and the shortcut's DGRAD (dout . W_sc, a cotangent of the resnet's input) is formed inside norm1's GroupNorm backward
+    # (siss_groupnorm_bwd_sc: a one-panel product whose epilogue is the apply pass) instead of as extra column tiles of conv2's
+    # dgrad that write an [M x Cin] tensor the apply pass reads back -- at the sites of at least sc_in_gn_min_px pixels per image.
+    # Per site, same box: 256 x 256 (256 -> 128) 846 + 990 us -> 489 + 1096 us; the fold costs 24 us at 128 x 128, where it stays
+    # (docs/experiments.md).  bf16 only; an older library loaded for an A/B (bench.py --lib) that lacks the launcher runs the fold.
+    sc_in_gn = True
+    sc_in_gn_min_px = 65536
     subpixel_up = True     # Upsample2D as four 2x2-tap phase convolutions on the low-resolution input (False: upsample copy + 3x3 conv)
     # ... at the sites of at least this many low-resolution pixels.  Same-box sweep (CelebA-HQ B = 16, ms per step): off 55.84 / 56.10,
     # every site 55.68, from 32 x 32 up 55.29, from 64 x 64 up 55.84 / 55.61 -- below 32 x 32 the phase products are latency-bound
@@ -235,7 +242,7 @@ class UNetEngine:
         # attention kernels, slab GroupNorm, side streams.
         self.f32_fused = bool(f32_fused) and self.f32
         if self.f32:
-            self.epi_stats = False
+            self.epi_stats = self.sc_in_gn = False
             if not self.f32_fused:
                 self.d2s_epilogue = self.fold_shortcut = False
                 self.group_rows = 0
@@ -699,10 +706,13 @@ class UNetEngine:
                      self._gn_partial(x.n, x.h, x.w, x.c), x.n, x.h, x.w, x.c, G, float(eps), int(silu), int(compact_out),
                      0 if ldx == x.c else ldx)
 
-        def bwd(dy, colsum=None, accum: Act = None, colsum_ld=0, accum2: Act = None, split=None):
+        def bwd(dy, colsum=None, accum: Act = None, colsum_ld=0, accum2: Act = None, split=None, sc=None):
             """dy: Act (padded) or compact tensor, nb samples.  Returns dx Act (nb samples).
             accum / accum2: cotangents already known for x (added; accum is overwritten in place).
-            split = (da, db, accumulate_b): x was concat(a, b) -- write the two halves straight into da / db."""
+            split = (da, db, accumulate_b): x was concat(a, b) -- write the two halves straight into da / db.
+            sc = (dout, wT): the cotangent dout . wT that x receives through a 1x1 conv_shortcut (dout: the resnet's output cotangent,
+            wT: the shortcut's dgrad weight copy [C][K]) is formed inside this launch and added where `accum` would be."""
+            assert sc is None or (accum is None and colsum is None and isinstance(dy, Act))
             nb = self.nb
             # accum is normally overwritten in place; not while a queued (grouped) wgrad still reads it: fresh output then
             held = accum is not None and self._is_held(accum.buf)
@@ -718,6 +728,14 @@ class UNetEngine:
                 dx = accum if (accum is not None and not held) else self._get(nb, x.h, x.w, x.c)
                 dx2p, split_c, accb = None, 0, False
             dyp = dy.data if isinstance(dy, Act) else dy
+            if sc is not None:
+                dout, wsc = sc
+                lib.call("siss_groupnorm_bwd_sc", dyp, x.data, ps.p(pre + ".weight"), ps.p(pre + ".bias"), mean, rstd, dx.data,
+                         dout.data, getattr(dout, "ld", dout.c), wsc, dout.c, accum2.data if accum2 is not None else None, dx2p,
+                         split_c, int(accb), ps.g(pre + ".weight", self.gbase), ps.g(pre + ".bias", self.gbase), None,
+                         self._gn_partial(nb, x.h, x.w, x.c), self._buf("gn_sc_const", (nb * G * 4,)), nb, x.n, self.set_images,
+                         ps.total, x.h, x.w, x.c, G, int(silu), int(s2d), 0 if ldx == x.c else ldx)
+                return dx
             lib.call("siss_groupnorm_bwd_ld_s2d" if s2d else "siss_groupnorm_bwd_ld", dyp, x.data, ps.p(pre + ".weight"), ps.p(pre + ".bias"), mean, rstd,
                      dx.data, accum.data if accum is not None else None,
                      accum2.data if accum2 is not None else None, dx2p, split_c, int(accb),
@@ -935,7 +953,14 @@ class UNetEngine:
             # conv2 (its bias gradient equals the shortcut conv's bias gradient: same pre-activation).  With a shortcut, its dgrad
             # (dout . W_sc, HBM-bound on its own) rides in conv2's 3x3 dgrad over the same cotangent where that kernel takes it
             acc_sc = None
-            if has_sc:
+            # ... or, at the widest sites, inside norm1's backward below (sc_in_gn): conv2's dgrad is then a plain 3x3 product, the
+            # [rows x cin] cotangent never exists, and dout stays alive until that launch has read it
+            sc_gn = (has_sc and self.sc_in_gn and not self.f32 and x.h * x.w >= self.sc_in_gn_min_px and cout % 64 == 0
+                     and cin % 8 == 0 and cin <= 1024 and lib.has("siss_groupnorm_bwd_sc"))
+            if sc_gn:
+                sc_b(dout, bias_grad=False, need_dx=False)
+                da2 = c2_b(dout, bias_grad2=ps.g(pre + ".conv_shortcut.bias", gb))
+            elif has_sc:
                 # the shortcut's weight gradient first: it reduces over the same cotangent as conv2's, and at the top resolution it is
                 # queued for the NEXT 3-tap weight-gradient launch -- conv2's, two lines down (pair_top)
                 sc_b(dout, bias_grad=False, need_dx=False)
@@ -950,7 +975,10 @@ class UNetEngine:
             da1 = c1_b(dh, bias_grad=False)
             self._put(dh)
             prior = self.gmap.pop(id(x), None)          # cotangent x already received from another consumer
-            if has_sc:
+            sc = None
+            if sc_gn:
+                acc, sc = None, (dout, self.wT[pre + ".conv_shortcut.weight"][0])
+            elif has_sc:
                 acc = acc_sc if acc_sc is not None else sc_b(dout, bias_grad=False, wgrad=False)    # (dgrad only: see above)
                 self._put(dout)
             else:
@@ -964,14 +992,16 @@ class UNetEngine:
                 da = self._get(nb, a.h // 2, a.w // 2, 4 * a.c) if s2d else self._get(nb, a.h, a.w, a.c)
                 accb = self.gmap.get(id(b))
                 db = accb if accb is not None else self._get(nb, b.h, b.w, b.c)
-                gn1_b(da1, accum=acc, accum2=prior, split=(da, db, accb is not None, s2d))
+                gn1_b(da1, accum=acc, accum2=prior, split=(da, db, accb is not None, s2d), sc=sc)
                 self.gmap[id(b)] = db
-                self._put(acc)
+                self._put(dout if sc_gn else acc)
                 self._give(a, da)
                 x.cat_done = True
             else:
-                dx = gn1_b(da1, accum=acc, accum2=prior)
+                dx = gn1_b(da1, accum=acc, accum2=prior, sc=sc)
                 self.gmap[id(x)] = dx
+                if sc_gn:
+                    self._put(dout)
             self._put(prior)
             self._put(da1)
         self.tape.append(bwd)
@@ -1589,7 +1619,8 @@ class UNetEngine:
         fill()
 
     def _wgrad_sig(self):
-        return (self.group_rows, self.group_max, self.group_attn, self.pair_top, self.pair_min_rows, self.fold_shortcut, self.subpixel_up,
+        return (self.group_rows, self.group_max, self.group_attn, self.pair_top, self.pair_min_rows, self.fold_shortcut, self.sc_in_gn,
+                self.sc_in_gn_min_px, self.subpixel_up,
                 self.subpixel_min_px, self.subpixel_queue, self.fused_attn, self.sparse_min_floats, self.wgrad_side, self.side_follow,
                 self.on_early_grads_final is not None)
 
