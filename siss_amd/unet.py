@@ -25,6 +25,7 @@ import torch
 from . import lib, ops
 from .config import UNet2DConfig
 from .layout import Act, ActView
+from .wgrad import WgradQueue
 
 ALIGN = 64  # floats; keeps every bf16 shadow slice 128-B aligned
 
@@ -253,23 +254,18 @@ class UNetEngine:
         self.ps.relayout(self._grads_final_early)
         self.ps.allocate(self.device, f32=self.f32)
         self._build_temb_tables()
-        self.wT = {}
-        self._wds = {}
-        self._acts = {}
-        self._bufs = {}
-        self._pool = {}
-        self.tape = []
-        self.gmap = {}
-        self._uid = 0
+        self._init_runtime_state()
+
+    def _init_runtime_state(self):
+        """What an engine keeps between launches besides its parameters (the forward-only VAE halves start from the same)."""
+        self.wT, self._wds, self._up_w = {}, {}, {}
+        self._acts, self._bufs, self._pool = {}, {}, {}
+        self.tape, self.gmap, self._uid = [], {}, 0
         self.on_early_grads_final = None
-        self._wq, self._held, self._held_release = [], {}, []
-        self._pair1 = []
-        self._wq_post = []
-        self._side, self._side_busy, self._side_held, self._side_release, self._side_mark = None, False, {}, [], None
-        self._side_phase = False
+        self._side, self._side_mark = None, None
+        self.wgrads = WgradQueue(self)
         self._prep_pending, self._wT_stale = False, False
         self._fill_key, self._fill_plan, self._fill_plans, self._fill_tables = None, None, {}, []
-        self._up_w = {}
         self._vjp, self._dx, self._vjp_sums = False, None, None
         self._mha_sites = []
 
@@ -534,98 +530,11 @@ class UNetEngine:
     def _get(self, n, h, w, c):
         lst = self._pool.setdefault((n, h, w, c), [])
         a = lst.pop() if lst else Act(n, h, w, c, self.device, dtype=self.adt)
-        self._wsync(a)
+        self.wgrads.before_write(a)
         return a
 
-    def _wsync(self, a):
-        """`a` is about to be overwritten: a queued (grouped) wgrad that still reads it must run first."""
-        if a is None:
-            return
-        key = id(getattr(a, "base", a).buf)
-        if self._held and key in self._held:
-            self._flush_wgrads()
-        if self._side_held and key in self._side_held:
-            self._join_side()
-
-    def _is_held(self, buf):
-        return bool((self._held and id(buf) in self._held) or (self._side_held and id(buf) in self._side_held))
-
-    def _join_side(self):
-        """The launches on the side stream have to be complete before what follows on this stream; their operands return to the pool."""
-        if not self._side_busy:
-            return
-        torch.cuda.current_stream().wait_stream(self._side)
-        self._side_busy, self._side_held = False, {}
-        rel, self._side_release = self._side_release, []
-        for a in rel:
-            self._put(a)
-
-    def _flush_wgrads_side(self):
-        """The queued weight-gradient products as CAPPED grouped launches on the side stream (behind everything issued so far)."""
-        if not self._wq:
-            return
-        if not (self.wgrad_side and self.side_blocks >= 8) or self.f32:
-            return self._flush_wgrads()
-        if self._side is None:
-            self._side = torch.cuda.Stream(device=self.device)
-        self._side.wait_stream(torch.cuda.current_stream())
-        jobs = (lib.TNJob * len(self._wq))(*[j for j, _ in self._wq])
-        with torch.cuda.stream(self._side):
-            lib.call("siss_gemm_tn_grouped_capped", jobs, len(self._wq), int(self.side_blocks) & ~7)
-            post, self._wq_post = self._wq_post, []
-            for fn in post:                              # launches that consume a queued product (the sub-pixel upsample's tap fold)
-                fn()
-        for _, (dy, _x) in self._wq:                     # their cotangent operands stay out of the pool until the join
-            buf = getattr(dy, "buf", None)
-            if buf is not None and id(buf) in self._held:
-                self._side_held[id(buf)] = self._held.pop(id(buf))
-        keep = []
-        for a in self._held_release:
-            (self._side_release if id(a.buf) in self._side_held else keep).append(a)
-        self._held_release = keep
-        self._wq = []
-        self._side_busy = True
-
-    def _flush_wgrads(self):
-        """Run the queued weight-gradient products as grouped launches and give their operands back to the pool."""
-        if self._wq:
-            jobs = (lib.TNJob * len(self._wq))(*[j for j, _ in self._wq])
-            lib.call("siss_gemm_tn_grouped", jobs, len(self._wq))
-            self._wq = []
-        post, self._wq_post = self._wq_post, []
-        for fn in post:                                  # launches that consume a queued product (the sub-pixel upsample's tap fold)
-            fn()
-        for job, _ in self._pair1:                      # one-panel top-resolution products that found no 3-tap partner: on their own
-            self._launch_tn_job(job)
-        self._pair1 = []
-        self._held = {}
-        rel, self._held_release = self._held_release, []
-        for a in rel:
-            self._put(a)
-
-    def _ns_auto(self):
-        return -2 if (self.wgrad_overwrite and not self.f32) else 0
-
-    def _launch_tn_job(self, job):
-        lib.call("siss_gemm_tn", job.Y, job.ldy, job.X, job.ldx, job.dW, job.set_stride, job.N, job.C, job.npanels,
-                 lib.int_array(list(job.shifts)[:job.npanels]), lib.int_array(list(job.coffs)[:job.npanels]), job.nsets,
-                 job.rows_per_set, job.x_set_rows, job.row_begin, job.row_end, 0, job.zero_page, job.dbias, job.dbias2)
-
-    def _unhold(self, dy):
-        """A queued product that read `dy` has been launched: give the buffer back if its owner already released it."""
-        self._held.pop(id(dy.buf), None)
-        for a in [a for a in self._held_release if a.buf is dy.buf]:
-            self._held_release.remove(a)
-            self._put(a)
-
     def _put(self, a):
-        if a is not None:
-            if self._held and id(a.buf) in self._held:   # still the operand of a queued wgrad: back to the pool after the flush
-                self._held_release.append(a)
-                return
-            if self._side_held and id(a.buf) in self._side_held:     # ... or of one running on the side stream: after the join
-                self._side_release.append(a)
-                return
+        if a is not None and not self.wgrads.defer_release(a):
             self._pool.setdefault((a.n, a.h, a.w, a.c), []).append(a)
 
     def _name(self, base):
@@ -638,7 +547,7 @@ class UNetEngine:
         if cur is None:
             self.gmap[id(act)] = g
         else:
-            self._wsync(cur)
+            self.wgrads.before_write(cur)
             lib.call("siss_add_inplace", cur.data, g.data, cur.n, cur.h, cur.w, cur.c)
             self._put(g)
 
@@ -715,15 +624,15 @@ class UNetEngine:
             assert sc is None or (accum is None and colsum is None and isinstance(dy, Act))
             nb = self.nb
             # accum is normally overwritten in place; not while a queued (grouped) wgrad still reads it: fresh output then
-            held = accum is not None and self._is_held(accum.buf)
+            held = accum is not None and self.wgrads.is_held(accum.buf)
             if accum is not None and not held:
-                self._wsync(accum)                      # written in place
+                self.wgrads.before_write(accum)                      # written in place
             s2d = False
             if split is not None:
                 da, db, accb = split[:3]
                 s2d = len(split) > 3 and bool(split[3])   # da is a half-resolution, 4x-channel Act: the first part in space-to-depth layout
                 dx, dx2p, split_c = da, db.data, (da.c // 4 if s2d else da.c)
-                self._wsync(db)
+                self.wgrads.before_write(db)
             else:
                 dx = accum if (accum is not None and not held) else self._get(nb, x.h, x.w, x.c)
                 dx2p, split_c, accb = None, 0, False
@@ -812,7 +721,7 @@ class UNetEngine:
             if not need_dx:
                 return None
             if accum is not None:
-                self._wsync(accum)
+                self.wgrads.before_write(accum)
             dx = accum if accum is not None else self._get(dy.n, x.h, x.w, x.c)
             if sc_dgrad is not None:
                 pre2, c2, get_out2 = sc_dgrad
@@ -835,7 +744,6 @@ class UNetEngine:
         """dW_view: grads[gbase:, off:] -- a strided view whose [0,0] element is the target."""
         if self._vjp:                                   # input_vjp(): data gradients only
             return
-        ps = self.ps
         if shifts is None:
             if ksize == 3:
                 from .layout import conv3x3_panels
@@ -848,46 +756,21 @@ class UNetEngine:
         x_set_rows = rows_per_set if x.n == dy.n else 0      # 0: every set reads the same saved rows
         rb, re = dy.wp + 1, rows_per_set - (dy.wp + 1)
         tiles = (-(-co // 128)) * (-(-ci // 128))
-        ns = ops._nsplits(tiles, t, self.nsets, re - rb, ops.is_conv3_panels(shifts, coffs))
-        sh, cf, zp = lib.int_array(shifts), lib.int_array(coffs), ops.zero_page(self.device)
-        nsets = self.nsets
+        conv3 = ops.is_conv3_panels(shifts, coffs)
+        wq = self.wgrads
+        job = wq.job(dy.data, dy.c, x.data, ldx or getattr(x, "ld", x.c), dW_view, co, ci, shifts, coffs, nsets=self.nsets,
+                     rows_per_set=rows_per_set, row_begin=rb, row_end=re, x_set_rows=x_set_rows, dbias=dbias, dbias2=dbias2)
         if self.group_rows and re - rb <= self.group_rows and isinstance(dy, Act):
-            job = lib.TNJob(Y=dy.data.data_ptr(), ldy=dy.c, X=x.data.data_ptr(), ldx=ldx or getattr(x, "ld", x.c),
-                            dW=dW_view.data_ptr(), set_stride=ps.total, N=co, C=ci, npanels=t, nsets=nsets,
-                            rows_per_set=rows_per_set, row_begin=rb, row_end=re, nsplits=self._ns_auto(), x_set_rows=x_set_rows,
-                            zero_page=zp.data_ptr(), dbias=dbias.data_ptr() if dbias is not None else None,
-                            dbias2=dbias2.data_ptr() if dbias2 is not None else None,
-                            shifts=(lib.I * 9)(*shifts, *([0] * (9 - t))), coffs=(lib.I * 9)(*coffs, *([0] * (9 - t))))
-            self._wq.append((job, (dy, x)))
-            self._held[id(dy.buf)] = dy
-            if len(self._wq) >= self.group_max:
-                self._flush_wgrads_side() if (self._side_phase and self.side_follow) else self._flush_wgrads()
+            wq.queue(job, hold=dy)
+            wq.flush_if_full()
             return
-        if (self.pair_top and not self.f32 and isinstance(dy, Act) and re - rb >= self.pair_min_rows
-                and (t == 1 or (ops.is_conv3_panels(shifts, coffs) and self._pair1))):
-            job = lib.TNJob(Y=dy.data.data_ptr(), ldy=dy.c, X=x.data.data_ptr(), ldx=ldx or getattr(x, "ld", x.c),
-                            dW=dW_view.data_ptr(), set_stride=ps.total, N=co, C=ci, npanels=t, nsets=nsets,
-                            rows_per_set=rows_per_set, row_begin=rb, row_end=re, nsplits=self._ns_auto(), x_set_rows=x_set_rows,
-                            zero_page=zp.data_ptr(), dbias=dbias.data_ptr() if dbias is not None else None,
-                            dbias2=dbias2.data_ptr() if dbias2 is not None else None,
-                            shifts=(lib.I * 9)(*shifts, *([0] * (9 - t))), coffs=(lib.I * 9)(*coffs, *([0] * (9 - t))))
+        if self.pair_top and not self.f32 and isinstance(dy, Act) and re - rb >= self.pair_min_rows:
             if t == 1:                                  # waits for the next 3-tap product (or the end of the backward pass)
-                self._pair1.append((job, dy))
-                self._held[id(dy.buf)] = dy
+                wq.wait_for_partner(job, dy)
                 return
-            # the partner: a waiting product over the SAME cotangent (the resnet's own conv_shortcut: its Y tiles are in L2), else the oldest
-            same = [i for i, (_, d) in enumerate(self._pair1) if d is dy]
-            j1, dy1 = self._pair1.pop(same[0] if same else 0)
-            # (the launcher refuses a pair it cannot split over the device -- fewer CUs than the 3-tap product's base grid needs, no
-            # room for a one-tap block: status 1 -- the two products then run as launches of their own)
-            if lib.call("siss_gemm_tn_pair", lib.C.byref(job), lib.C.byref(j1), 0, refusable=True):
-                self._launch_tn_job(job)
-                self._launch_tn_job(j1)
-            if not any(d is dy1 for _, d in self._pair1):
-                self._unhold(dy1)
-            return
-        lib.call("siss_gemm_tn", dy.data, dy.c, x.data, ldx or getattr(x, "ld", x.c), dW_view, ps.total, co, ci, t,
-                 sh, cf, nsets, rows_per_set, x_set_rows, rb, re, ns, zp, dbias, dbias2)
+            if conv3 and wq.pair(job, dy):
+                return
+        wq.launch(job, ops._nsplits(tiles, t, self.nsets, re - rb, conv3))
 
     # ------------------------------------------------------------------ time embedding
     def time_embed(self, t):
@@ -1068,20 +951,13 @@ class UNetEngine:
                 """dyt [rows2,C] cotangent of y = xin W^T + b (xin has B*S rows shared by the sets)."""
                 dW = ps.grads[gb:, ps.specs[wname + ".weight"].off:]
                 tiles = (-(-C // 128)) ** 2
-                if self._vjp:
-                    pass
-                elif self.group_attn and self.group_rows:
-                    z9 = (lib.I * 9)(*([0] * 9))
-                    self._wq.append((lib.TNJob(Y=dyt.data_ptr(), ldy=C, X=xin.data_ptr(), ldx=C, dW=dW.data_ptr(),
-                                               set_stride=ps.total, N=C, C=C, npanels=1, nsets=ns, rows_per_set=si * S,
-                                               row_begin=0, row_end=si * S, nsplits=self._ns_auto(),
-                                               x_set_rows=si * S if B == nb else 0, zero_page=zp.data_ptr(),
-                                               dbias=ps.g(wname + ".bias", gb).data_ptr(), dbias2=None, shifts=z9, coffs=z9),
-                                     (dyt, xin)))
-                else:
-                    lib.call("siss_gemm_tn", dyt, C, xin, C, dW, ps.total, C, C, 1, lib.int_array([0]),
-                             lib.int_array([0]), ns, si * S, si * S if B == nb else 0,
-                             0, si * S, ops._nsplits(tiles, 1, ns, si * S, False), zp, ps.g(wname + ".bias", gb), None)
+                if not self._vjp:
+                    job = self.wgrads.job(dyt, C, xin, C, dW, C, C, nsets=ns, rows_per_set=si * S, row_begin=0, row_end=si * S,
+                                          x_set_rows=si * S if B == nb else 0, dbias=ps.g(wname + ".bias", gb))
+                    if self.group_attn and self.group_rows:
+                        self.wgrads.queue(job)          # (its operands are buffers of this site's own: `own` above)
+                    else:
+                        self.wgrads.launch(job, ops._nsplits(tiles, 1, ns, si * S, False))
                 if dx_out is not None:
                     ops.gemm_nt(lib.ptr(dyt), C, self.wT[wname + ".weight"], lib.ptr(dx_out), C, rows2, C, C,
                                 [0], [0], res_ptr=lib.ptr(dx_out) if accumulate else None, ldr=C)
@@ -1171,22 +1047,14 @@ class UNetEngine:
             self._put(do)
             # [dWq ; dWk ; dWv] = dqkv^T hn and the three bias gradients: ONE product with N = 3C
             dW = ps.grads[gb:, sq.off:]
-            zp = ops.zero_page(self.device)
-            xsr = si * S if B == nb else 0
-            if self._vjp:
-                pass
-            elif grouped:
-                z9 = (lib.I * 9)(*([0] * 9))
-                self._wq.append((lib.TNJob(Y=dqkv.data_ptr(), ldy=3 * C, X=hn.data_ptr(), ldx=C, dW=dW.data_ptr(),
-                                           set_stride=ps.total, N=3 * C, C=C, npanels=1, nsets=ns, rows_per_set=si * S,
-                                           row_begin=0, row_end=si * S, nsplits=self._ns_auto(), x_set_rows=xsr, zero_page=zp.data_ptr(),
-                                           dbias=ps.g(pre + ".to_q.bias", gb).data_ptr(), dbias2=None, shifts=z9, coffs=z9),
-                                 (dqkv, hn)))
-                if len(self._wq) >= self.group_max:
-                    self._flush_wgrads_side() if (self._side_phase and self.side_follow) else self._flush_wgrads()
-            else:
-                lib.call("siss_gemm_tn", dqkv, 3 * C, hn, C, dW, ps.total, 3 * C, C, 1, lib.int_array([0]), lib.int_array([0]),
-                         ns, si * S, xsr, 0, si * S, 0, zp, ps.g(pre + ".to_q.bias", gb), None)
+            if not self._vjp:
+                job = self.wgrads.job(dqkv, 3 * C, hn, C, dW, 3 * C, C, nsets=ns, rows_per_set=si * S, row_begin=0, row_end=si * S,
+                                      x_set_rows=si * S if B == nb else 0, dbias=ps.g(pre + ".to_q.bias", gb))
+                if grouped:
+                    self.wgrads.queue(job)
+                    self.wgrads.flush_if_full()
+                else:
+                    self.wgrads.launch(job)
             # dhn = dq Wq + dk Wk + dv Wv: three panels (column windows of dqkv) against the three consecutive transposed copies
             wq, wk, wv = (self.wT[pre + n + ".weight"] for n in (".to_q", ".to_k", ".to_v"))
             esz = wq.element_size()
@@ -1236,7 +1104,7 @@ class UNetEngine:
             dW = ps.grads[gb:, ps.specs[pre + ".conv.weight"].off:]
             self._wgrad(dy, z, dW, C, C, 3, shifts=shifts, coffs=coffs, ldx=4 * C, dbias=ps.g(pre + ".conv.bias", gb))
             acc = self.gmap.get(id(x))
-            self._wsync(acc)
+            self.wgrads.before_write(acc)
             dx = acc if acc is not None else self._get(nb, x.h, x.w, C)
             pos = 0
             if self.d2s_epilogue:
@@ -1331,7 +1199,6 @@ class UNetEngine:
             # weight gradient: per plane, Y = the plane's columns of z, X = the four shifted low-resolution panels
             rows_per_set = self.set_images * z.rows_per_image
             rb, re = z.wp + 1, rows_per_set - (z.wp + 1)
-            zp = ops.zero_page(self.device)
             assert x.n in (nb, self.set_images)
             queued = bool(self.subpixel_queue and self.group_rows and re - rb <= self.group_rows)
             # (queued: the scratch must survive until the grouped launch has run -- one per site, not the shared one)
@@ -1340,27 +1207,18 @@ class UNetEngine:
             fold = lambda: lib.call("siss_upsample_phase_wgrad_fold", dW4, dWt, ps.total, nsets_, C, C)
             if not self._vjp:
                 dW4.zero_()
-            for plane in range(4 if not self._vjp else 0):                       # (the scratch's set stride is 16 C^2, the bias gradient's the flat buffer's)
-                if queued:
-                    sh4 = phase_shifts(plane)
-                    self._wq.append((lib.TNJob(Y=z.data[:, plane * C:].data_ptr(), ldy=4 * C, X=x.data.data_ptr(), ldx=ldx,
-                                               dW=dW4[:, plane].data_ptr(), set_stride=dW4[0].numel(), N=C, C=C, npanels=4,
-                                               nsets=self.nsets, rows_per_set=rows_per_set, row_begin=rb, row_end=re, nsplits=0,
-                                               x_set_rows=rows_per_set if x.n == nb else 0, zero_page=zp.data_ptr(),
-                                               dbias=ps.g(pre + ".conv.bias", gb).data_ptr(), dbias2=None,
-                                               shifts=(lib.I * 9)(*sh4, *([0] * 5)), coffs=(lib.I * 9)(*([0] * 9)),
-                                               bias_set_stride=ps.total), (z, x)))
+                # (the scratch's set stride is 16 C^2, the bias gradient's the flat buffer's)
+                jobs = [self.wgrads.job(z.data[:, plane * C:], 4 * C, x.data, ldx, dW4[:, plane], C, C, phase_shifts(plane), [0] * 4,
+                                        nsets=self.nsets, rows_per_set=rows_per_set, row_begin=rb, row_end=re, nsplits=0,
+                                        x_set_rows=rows_per_set if x.n == nb else 0, dbias=ps.g(pre + ".conv.bias", gb),
+                                        set_stride=dW4[0].numel(), bias_set_stride=ps.total) for plane in range(4)]
+                if queued:                               # the nine-tap fold follows the grouped launch that forms the 16 phase-tap gradients
+                    self.wgrads.queue(*jobs, hold=z)
+                    self.wgrads.after_launch(fold)
                 else:
-                    lib.call("siss_gemm_tn_bs", z.data[:, plane * C:], 4 * C, x.data, ldx, dW4[:, plane], dW4[0].numel(), C, C, 4,
-                             lib.int_array(phase_shifts(plane)), z4, self.nsets, rows_per_set, rows_per_set if x.n == nb else 0,
-                             rb, re, 0, zp, ps.g(pre + ".conv.bias", gb), None, ps.total)
-            if self._vjp:
-                pass
-            elif queued:                                 # the nine-tap fold follows the grouped launch that forms the 16 phase-tap gradients
-                self._held[id(z.buf)] = z
-                self._wq_post.append(fold)
-            else:
-                fold()
+                    for job in jobs:
+                        self.wgrads.launch(job)
+                    fold()
             # dgrad: dx[Y, X] = sum over (plane, tap) of z_plane[Y - dy_tap, X - dx_tap] . W_plane,tap^T
             dx = self._get(nb, lo_h, lo_w, C)
             sh = [-s_ for plane in range(4) for s_ in phase_shifts(plane)]
@@ -1418,7 +1276,7 @@ class UNetEngine:
             dcat = self._take(out)
             da = self._get(nb, a.h, a.w, a.c)
             accb = self.gmap.get(id(b))
-            self._wsync(accb)
+            self.wgrads.before_write(accb)
             db = accb if accb is not None else self._get(nb, b.h, b.w, b.c)
             lib.call("siss_concat_bwd", dcat.data, da.data, db.data, int(accb is not None), nb, a.h, a.w, a.c, b.c)
             self.gmap[id(b)] = db
@@ -1439,9 +1297,7 @@ class UNetEngine:
         N, cin, H, W = x.shape
         assert cin == cfg.in_channels
         self.tape, self.gmap, self._uid = [], {}, 0
-        self._wq, self._held, self._held_release = [], {}, []
-        self._pair1 = []
-        self._wq_post = []
+        self.wgrads.reset()
         self._qs_cache = {}
         self._mha_sites = []
         if self._wT_stale:                             # the dgrad weight copies of the last optimizer step: beside this forward pass
@@ -1559,22 +1415,15 @@ class UNetEngine:
                          ps.g("conv_out.bias", gb))
             rows_per_set = self.set_images * col.rows_per_image
             rb, re = col.wp + 1, rows_per_set - (col.wp + 1)
-            ns = ops._nsplits(1, 1, self.nsets, re - rb, False)
-            if self._vjp:
-                pass
-            elif self.pair_top and not self.f32 and re - rb >= self.pair_min_rows:
-                zp = ops.zero_page(self.device)
-                z9 = (lib.I * 9)(*([0] * 9))
-                self._pair1.append((lib.TNJob(Y=col.data.data_ptr(), ldy=kc, X=a.data.data_ptr(), ldx=c0,
-                                              dW=ps.grads[gb:, ps.specs["conv_out.weight"].off:].data_ptr(), set_stride=ps.total,
-                                              N=9 * co, C=c0, npanels=1, nsets=self.nsets, rows_per_set=rows_per_set, row_begin=rb,
-                                              row_end=re, nsplits=0, x_set_rows=rows_per_set if a.n == nb else 0,
-                                              zero_page=zp.data_ptr(), dbias=None, dbias2=None, shifts=z9, coffs=z9), col))
-                self._held[id(col.buf)] = col
-            else:
-                lib.call("siss_gemm_tn", col.data, kc, a.data, c0, ps.grads[gb:, ps.specs["conv_out.weight"].off:], ps.total,
-                         9 * co, c0, 1, lib.int_array([0]), lib.int_array([0]), self.nsets, rows_per_set,
-                         rows_per_set if a.n == nb else 0, rb, re, ns, ops.zero_page(self.device), None, None)
+            if not self._vjp:
+                # (waiting for a partner it carries split count 0, not the automatic one)
+                job = self.wgrads.job(col.data, kc, a.data, c0, ps.grads[gb:, ps.specs["conv_out.weight"].off:], 9 * co, c0,
+                                      nsets=self.nsets, rows_per_set=rows_per_set, row_begin=rb, row_end=re, nsplits=0,
+                                      x_set_rows=rows_per_set if a.n == nb else 0)
+                if self.pair_top and not self.f32 and re - rb >= self.pair_min_rows:
+                    self.wgrads.wait_for_partner(job, col)
+                else:
+                    self.wgrads.launch(job, ops._nsplits(1, 1, self.nsets, re - rb, False))
             da = self._get(nb, H, W, c0)
             ops.gemm_nt(lib.ptr(col.data), kc, self._wd_out, lib.ptr(da.data), c0, col.rows, c0, kc, [0], [0],
                         rows_per_image=col.rows_per_image, hp=col.hp, wp=col.wp)
@@ -1734,7 +1583,7 @@ class UNetEngine:
         self.dtp_all.zero_()
         for idx in range(len(self.tape) - 1, -1, -1):
             self.tape[idx]()
-        assert not (self._wq or self._pair1 or self._wq_post or self._held or self._side_busy), "input_vjp queued a weight gradient"
+        assert self.wgrads.idle, "input_vjp queued a weight gradient"
         assert not self.gmap, f"{len(self.gmap)} dangling cotangents"
 
     def _backward(self, cot, nsets, grad_base_set):
@@ -1757,15 +1606,12 @@ class UNetEngine:
         side_at = (self._side_mark or 0) - 1 if (self.wgrad_side and not self.f32 and self.nf <= self.side_max_batch) else -1
         for idx in range(len(self.tape) - 1, -1, -1):
             if idx == side_at:
-                self._side_phase = True
-                self._flush_wgrads_side()               # the weight gradients queued so far run beside the low-resolution blocks
+                self.wgrads.begin_side_phase()          # the weight gradients queued so far run beside the low-resolution blocks
             self.tape[idx]()
             if idx == mark and self.on_early_grads_final is not None:
-                self._flush_wgrads()                    # queued low-resolution wgrads belong to the early-final tail
-                self._join_side()
+                self.wgrads.drain()                     # queued low-resolution wgrads belong to the early-final tail
                 self.on_early_grads_final()         # grads[:, ps.split:] are complete (data-parallel overlap hook)
-        self._side_phase = False
-        self._flush_wgrads()
-        self._join_side()
+        self.wgrads.end_side_phase()
+        self.wgrads.drain()
         self._check_sparse_fill()
         assert not self.gmap, f"{len(self.gmap)} dangling cotangents"

@@ -155,22 +155,14 @@ class UNetCondEngine(UNetEngine):
         rps = rows2 // ns
         dW = ps.grads[gb:, ps.specs[wname + ".weight"].off:]
         tiles = (-(-n_out // 128)) * (-(-k_in // 128))
-        zp = ops.zero_page(self.device)
+        job = self.wgrads.job(dy, n_out, xin, k_in, dW, n_out, k_in, nsets=ns, rows_per_set=rps, row_begin=0, row_end=rps,
+                              x_set_rows=rps if rows_x == rows2 else 0, dbias=ps.g(wname + ".bias", gb) if bias else None)
         if self.group_attn and self.group_rows:
-            # queued for a grouped launch (UNetEngine._flush_wgrads): dy lives in a per-site buffer (see transformer())
-            z9 = (lib.I * 9)(*([0] * 9))
-            self._wq.append((lib.TNJob(Y=dy.data_ptr(), ldy=n_out, X=xin.data_ptr(), ldx=k_in, dW=dW.data_ptr(),
-                                       set_stride=ps.total, N=n_out, C=k_in, npanels=1, nsets=ns, rows_per_set=rps,
-                                       row_begin=0, row_end=rps, nsplits=self._ns_auto(), x_set_rows=rps if rows_x == rows2 else 0,
-                                       zero_page=zp.data_ptr(),
-                                       dbias=ps.g(wname + ".bias", gb).data_ptr() if bias else None, dbias2=None,
-                                       shifts=z9, coffs=z9), (dy, xin)))
-            if len(self._wq) >= self.group_max:
-                self._flush_wgrads()
+            # queued for a grouped launch: dy lives in a per-site buffer (see transformer())
+            self.wgrads.queue(job)
+            self.wgrads.flush_if_full()
         else:
-            lib.call("siss_gemm_tn", dy, n_out, xin, k_in, dW, ps.total, n_out, k_in, 1, lib.int_array([0]),
-                     lib.int_array([0]), ns, rps, rps if rows_x == rows2 else 0, 0, rps,
-                     ops._nsplits(tiles, 1, ns, rps, False), zp, ps.g(wname + ".bias", gb) if bias else None, None)
+            self.wgrads.launch(job, ops._nsplits(tiles, 1, ns, rps, False))
         if dx_out is not None:
             ops.gemm_nt(lib.ptr(dy), n_out, self.wT[wname + ".weight"], lib.ptr(dx_out), k_in, rows2, k_in, n_out,
                         [0], [0], res_ptr=lib.ptr(dx_out) if accumulate else None, ldr=k_in)

@@ -60,17 +60,8 @@ class _VAEHalf(UNetEngine):
         self.ps = ParamStore()
         self._declare_params()
         self.ps.allocate(self.device, nsets=1)
-        self.wT, self._wds, self._acts, self._bufs, self._pool = {}, {}, {}, {}, {}
-        self.tape, self.gmap, self._uid = [], {}, 0
-        self.on_early_grads_final = None
         self.adt, self.f32 = torch.bfloat16, False         # (forward-only front end: the bf16 path)
-        self._wq, self._held, self._held_release = [], {}, []
-        self._pair1 = []
-        self._wq_post = []
-        self._side, self._side_busy, self._side_held, self._side_release, self._side_mark = None, False, {}, [], None
-        self._side_phase = False
-        self._prep_pending, self._wT_stale = False, False
-        self._up_w = {}
+        self._init_runtime_state()
 
     def _declare_enc_resnet(self, pre, cin, cout):
         a = self.ps.add

@@ -317,6 +317,45 @@ def test_side_stream_weight_gradients_equal_the_main_stream_schedule(setup):
         eng.wgrad_side, eng.side_max_px, eng.side_blocks, eng.group_max, eng.side_follow = saved
 
 
+def test_paired_top_resolution_weight_gradients_equal_the_separate_launches(setup):
+    """UNetEngine.pair_top: a one-panel weight gradient at the top resolution (a resnet's conv_shortcut, conv_out, conv_in) waits
+    for the next three-tap weight gradient and rides in its launch (siss_gemm_tn_pair); its cotangent stays out of the buffer pool
+    until then (siss_amd/wgrad.py).  The engine reaches that path at 256 x 256, B = 16 by default; here the thresholds are lowered
+    so that the toy network's 16 x 16 level (1258 reduction rows per set at B = 4) pairs while its 8 x 8 level (378) stays
+    grouped.  Same products, same operands, float atomics: both gradient sets equal the unpaired schedule's to 1e-5 of scale."""
+    from siss_amd import lib
+    eng, _, sd = _fresh(setup)
+    g = torch.Generator().manual_seed(22)
+    B = 4
+    x = torch.randn(B, 3, 16, 16, generator=g).cuda()
+    t = torch.tensor([999, 10, 700, 999]).cuda()
+    cot = torch.randn(2 * B, 3, 16, 16, generator=g).cuda().contiguous()
+
+    def run(pair):
+        eng.pair_top = pair
+        calls = []
+        orig = lib.call
+        lib.call = lambda name, *a, _o=orig, _c=calls, **k: (_c.append(name), _o(name, *a, **k))[1]
+        try:
+            eng.forward(x, t)
+            eng.zero_grad()
+            eng.backward(cot, nsets=2)
+            torch.cuda.synchronize()
+        finally:
+            lib.call = orig
+        return eng.ps.grads.clone(), calls
+    saved = (eng.pair_top, eng.group_rows, eng.pair_min_rows)
+    try:
+        eng.group_rows = eng.pair_min_rows = 1000
+        ref, calls_off = run(False)
+        got, calls_on = run(True)
+        assert calls_on.count("siss_gemm_tn_pair") >= 1 and calls_off.count("siss_gemm_tn_pair") == 0
+        scale = float(ref.abs().max())
+        assert float((got - ref).abs().max()) <= 1e-5 * scale
+    finally:
+        eng.pair_top, eng.group_rows, eng.pair_min_rows = saved
+
+
 def test_mnist_tshirt_config_step_matches_oracle():
     """BASELINE config 1 on the HIP path: MNIST 28x28 UNet (64/128/256 channels, 16/32-head attention with
     head_dim 8, downsample_padding=1, flip_sin_to_cos), t ~ U{0..999}, inf guard (delete_tshirt.py)."""

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Where in the backward pass does the main stream wait for the side stream?  Logs every `_join_side` that actually waits and every
+"""Where in the backward pass does the main stream wait for the side stream?  Logs every `WgradQueue.join` that actually waits and every
 side flush of ONE eager CelebA-HQ step (call stack + the sequence number of the launch it precedes)."""
 import os
 import sys
@@ -31,26 +31,27 @@ for _ in range(2):
 torch.cuda.synchronize()
 
 log = []
-join0, flush0 = eng._join_side, eng._flush_wgrads_side
+wq = eng.wgrads
+join0, flush0 = wq.join, wq.flush_side
 
 
 def where():
     fr = traceback.extract_stack()[:-2]
-    return " <- ".join(f"{f.name}:{f.lineno}" for f in reversed(fr) if f.filename.endswith("unet.py"))[:200]
+    return " <- ".join(f"{f.name}:{f.lineno}" for f in reversed(fr) if f.filename.endswith(("unet.py", "wgrad.py")))[:200]
 
 
 def join():
-    if eng._side_busy:
+    if wq.side_busy:
         log.append((len(lib.PROF), "JOIN ", where()))
     join0()
 
 
 def flush():
-    log.append((len(lib.PROF), f"FLUSH {len(eng._wq)} jobs", where()))
+    log.append((len(lib.PROF), f"FLUSH {len(wq.jobs)} jobs", where()))
     flush0()
 
 
-eng._join_side, eng._flush_wgrads_side = join, flush
+wq.join, wq.flush_side = join, flush
 lib.PROF = []
 st.step(x0, a0, noise, t, u)
 torch.cuda.synchronize()
