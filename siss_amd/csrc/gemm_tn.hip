@@ -779,6 +779,11 @@ extern "C" {
 // nsplits == -1: one split per tile and dW is OVERWRITTEN with the product (no accumulation: the caller needs no zero
 // fill; attention dK / dV).
 // nsplits == -2: as 0, but a product that lands on one split overwrites its tiles (the first product into a zeroed dW: no read).
+// nsplits > 0: that many splits of ceil(rows / nsplits) rows rounded up to 64, added with float atomics; splits past row_end are empty.
+// The bias gradients ALWAYS accumulate (float atomics from the blocks of panel 0 / c-tile 0), under -1 and -2 too: dbias / dbias2 must
+// hold zeros or the running sum, and they are never in the overwrite log.  The result depends on rows [row_begin, row_end) of Y in
+// columns [0, N) and on the X rows / column windows the panels meet there, on nothing else: what lies around them (the columns
+// [N, ldy) included) may be anything, NaN too.
 int siss_gemm_tn(const void* Y, long ldy, const void* X, long ldx, float* dW, long set_stride, int N, int C,
                  int npanels, const int* shifts, const int* coffs, int nsets, int rows_per_set,
                  long x_set_rows, int row_begin, int row_end, int nsplits, const void* zero_page,
