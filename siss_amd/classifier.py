@@ -37,6 +37,59 @@ def _convs(in_ch):
     return out
 
 
+def fold_bn(sd, conv, bn, eps=BN_EPS):
+    """(w', b') in f64 of the convolution `conv` followed by the eval-mode BatchNorm `bn` of the state dict `sd`:
+    w' = w gamma / sqrt(var + eps), b' = beta - mean gamma / sqrt(var + eps)."""
+    w = sd[conv + ".weight"].double()
+    scale = sd[bn + ".weight"].double() / torch.sqrt(sd[bn + ".running_var"].double() + eps)
+    b = sd[bn + ".bias"].double() - sd[bn + ".running_mean"].double() * scale
+    return w * scale.view(-1, 1, 1, 1), b
+
+
+def pack_conv(w, b, stride, pad, device):
+    """A layer of siss_cls_conv from f64 weights [Cout, Cin, k, k] and bias [Cout], each rounded once to f32: the weights as
+    [Cout][Kp] in (kh, kw, ci) order, zero-padded to Kp % 32 == 0."""
+    cout, cin, kh, kw = w.shape
+    K = kh * kw * cin
+    Kp = -(-K // BK) * BK
+    wp = torch.zeros(cout, Kp, dtype=torch.float32)
+    wp[:, :K] = w.permute(0, 2, 3, 1).reshape(cout, K).float()
+    return dict(w=wp.to(device), b=b.float().to(device), cin=cin, cout=cout, k=kh, stride=stride, pad=pad, Kp=Kp)
+
+
+def conv_out(L, H, W):
+    k, s, p = L["k"], L["stride"], L["pad"]
+    return (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+
+
+def conv_splits(M, cout, Kp):
+    """Split-K where the grid is small (the late layers / fc at small N): up to one block per CU, >= 4 K steps per split."""
+    steps = Kp // BK
+    blocks = -(-M // 64) * -(-cout // 64)
+    return 1 if blocks >= 128 else max(1, min(steps // 4, -(-256 // blocks)))
+
+
+def run_conv(L, x, N, H, W, relu, res=None, nchw_in=False):
+    """One siss_cls_conv launch of the packed layer L on x (NHWC [N, H, W, Cin], or the NCHW image when nchw_in): (y NHWC, Ho, Wo)."""
+    k, s, p = L["k"], L["stride"], L["pad"]
+    Ho, Wo = conv_out(L, H, W)
+    M, cout = N * Ho * Wo, L["cout"]
+    y = torch.empty(N, Ho, Wo, cout, device=x.device, dtype=torch.float32)
+    splits = conv_splits(M, cout, L["Kp"])
+    ws = torch.empty(splits * M * cout, device=x.device, dtype=torch.float32) if splits > 1 else None
+    lib.call("siss_cls_conv", x, int(nchw_in), L["w"], L["b"], res, y, ws, 0 if ws is None else ws.numel(),
+             N, H, W, L["cin"], Ho, Wo, cout, k, k, s, p, L["Kp"], int(relu), splits)
+    return y, Ho, Wo
+
+
+def max_pool(x, N, H, W, C):
+    """nn.MaxPool2d(3, 2, 1) on NHWC (siss_cls_maxpool): (y, Ho, Wo)."""
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    y = torch.empty(N, Ho, Wo, C, device=x.device, dtype=torch.float32)
+    lib.call("siss_cls_maxpool", x, y, N, H, W, C, Ho, Wo)
+    return y, Ho, Wo
+
+
 class ResNet18:
     """metrics/mnist_resnet.py's resnet18(num_classes, grayscale) on the HIP kernels: `[N, C, H, W]` f32 images -> `[N, num_classes]`
     logits (the reference disables avgpool, so fc reads the flattened 512 x 1 x 1 map: H, W <= 32).  The parameters live on the host
@@ -119,35 +172,13 @@ class ResNet18:
         sd = self._sd
         layers = {}
         for name, cin, cout, k, s, p, bn in _convs(self.in_ch):
-            w = sd[name + ".weight"].double()
-            scale = sd[bn + ".weight"].double() / torch.sqrt(sd[bn + ".running_var"].double() + BN_EPS)
-            b = sd[bn + ".bias"].double() - sd[bn + ".running_mean"].double() * scale
-            layers[name] = self._layer(w * scale.view(-1, 1, 1, 1), b, s, p)
-        layers["fc"] = self._layer(sd["fc.weight"].double().view(self.num_classes, 512, 1, 1), sd["fc.bias"].double(), 1, 0)
+            layers[name] = pack_conv(*fold_bn(sd, name, bn), s, p, self.device)
+        layers["fc"] = pack_conv(sd["fc.weight"].double().view(self.num_classes, 512, 1, 1), sd["fc.bias"].double(), 1, 0, self.device)
         self._packed = layers
-
-    def _layer(self, w, b, stride, pad):
-        cout, cin, kh, kw = w.shape
-        K = kh * kw * cin
-        Kp = -(-K // BK) * BK
-        wp = torch.zeros(cout, Kp, dtype=torch.float32)
-        wp[:, :K] = w.permute(0, 2, 3, 1).reshape(cout, K).float()
-        return dict(w=wp.to(self.device), b=b.float().to(self.device), cin=cin, cout=cout, k=kh, stride=stride, pad=pad, Kp=Kp)
 
     # -- forward ---------------------------------------------------------------------------------
     def _conv(self, L, x, N, H, W, relu, res=None, nchw_in=False):
-        k, s, p = L["k"], L["stride"], L["pad"]
-        Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
-        M, cout = N * Ho * Wo, L["cout"]
-        y = torch.empty(N, Ho, Wo, cout, device=self.device, dtype=torch.float32)
-        steps = L["Kp"] // BK
-        blocks = -(-M // 64) * -(-cout // 64)
-        # split-K where the grid is small (layer3 / layer4 / fc at small N): up to one block per CU, >= 4 K steps per split
-        splits = 1 if blocks >= 128 else max(1, min(steps // 4, -(-256 // blocks)))
-        ws = torch.empty(splits * M * cout, device=self.device, dtype=torch.float32) if splits > 1 else None
-        lib.call("siss_cls_conv", x, int(nchw_in), L["w"], L["b"], res, y, ws, 0 if ws is None else ws.numel(),
-                 N, H, W, L["cin"], Ho, Wo, cout, k, k, s, p, L["Kp"], int(relu), splits)
-        return y, Ho, Wo
+        return run_conv(L, x, N, H, W, relu, res, nchw_in)
 
     @torch.no_grad()
     def __call__(self, x):
@@ -164,10 +195,7 @@ class ResNet18:
             return torch.empty(0, self.num_classes, device=self.device)
         P = self._packed
         h, H, W = self._conv(P["conv1"], x, N, H, W, relu=True, nchw_in=True)
-        Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-        pooled = torch.empty(N, Ho, Wo, 64, device=self.device, dtype=torch.float32)
-        lib.call("siss_cls_maxpool", h, pooled, N, H, W, 64, Ho, Wo)
-        h, H, W = pooled, Ho, Wo
+        h, H, W = max_pool(h, N, H, W, 64)
         for i in range(1, 5):
             for j in range(2):
                 pre = f"layer{i}.{j}."

@@ -13,6 +13,7 @@
 // no atomics anywhere, every result bit-reproducible.  Built with -ffp-contract=off (build.py EXACT): the uint8 image is a bitwise claim.
 // 1 <= K <= 16; a launch is instantiated for the tile KT in {1, 2, 3, 4, 8, 16} that holds K.
 #include "common.h"
+#include "decoded_u8.h"      // to_u8: torch's chain on one decoded element, shared with sscd.hip
 
 namespace {
 
@@ -28,21 +29,6 @@ template <int KT> struct Lane { static constexpr int F = KT <= 4 ? 16 : 4; };
 __device__ __forceinline__ void sq_acc(double& acc, float x, float c) {
     const float d = __fsub_rn(x, c);
     acc += (double)__fmul_rn(d, d);
-}
-
-// torch's chain on one element, every operation rounded where torch rounds it.  f32: /2 is exact, +0.5, clamp, *255, rint.
-__device__ __forceinline__ uint8_t to_u8(float x) {
-    float a = __fadd_rn(__fmul_rn(x, 0.5f), 0.5f);
-    a = fminf(fmaxf(a, 0.f), 1.f);                       // (a NaN pixel becomes 0 here; torch leaves its uint8 cast undefined)
-    return (uint8_t)rintf(__fmul_rn(a, 255.f));
-}
-// bf16: each torch operation computes in f32 and rounds its result to bf16
-__device__ __forceinline__ uint8_t to_u8(bf16_t xb) {
-    float a = bfround(__fmul_rn(bf2f(xb), 0.5f));
-    a = bfround(__fadd_rn(a, 0.5f));
-    a = fminf(fmaxf(a, 0.f), 1.f);
-    a = bfround(__fmul_rn(a, 255.f));
-    return (uint8_t)bfround(rintf(a));
 }
 
 // acc[r][k] of every lane -> slab[(row0 + r) * k + kk][blk]; one barrier.  Wave sums by xor butterfly, the waves left to right.

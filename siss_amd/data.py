@@ -23,8 +23,8 @@ class Normalize:
         self.mean, self.std = list(mean), list(std)
 
     def __call__(self, x):
-        m = torch.tensor(self.mean, dtype=x.dtype).view(-1, 1, 1)
-        s = torch.tensor(self.std, dtype=x.dtype).view(-1, 1, 1)
+        m = torch.tensor(self.mean, dtype=x.dtype, device=x.device).view(-1, 1, 1)
+        s = torch.tensor(self.std, dtype=x.dtype, device=x.device).view(-1, 1, 1)
         return (x - m) / s
 
 

@@ -667,10 +667,59 @@ class DeleteSD(_DeleteBase):
 
     kmeans = None               # metrics.fraction_deletion's classifier (check_fraction_deletion), its tracker built at the first use
     fraction = None
+    sscd = None                 # metrics.sscd's tracker (check_sscd): the network on the host until the first evaluation
 
     def check_metrics(self):
         super().check_metrics()
         self.kmeans = self.check_fraction_deletion()
+        self.sscd = self.check_sscd()
+
+    def check_sscd(self):
+        """metrics.sscd (delete_sd.py:226-228,:277-283; null / absent: nothing) needs model_path on disk (or allow_random_init=true:
+        a random-init network of the same architecture, loudly), a checkpoint the loader accepts, a vae/ in the checkpoint directory
+        (the network sees decoded images), data_files.mem_img_path on disk, and data_transforms null or a Compose of exactly one
+        Normalize with one or three means and stds (the ToTensor in front of it is part of the fused preprocessing) -- refused
+        here, before the first step.  Returns the sscd.SSCDScore, or None."""
+        cfg = self.cfg
+        sc = (cfg.get("metrics") or {}).get("sscd")
+        if not sc:
+            return None
+        from .data import Compose, Normalize
+        from .sscd import SSCDModel, SSCDScore
+        path = sc.get("model_path") if isinstance(sc, dict) else None
+        if not path:
+            raise ValueError(f"metrics.sscd={sc!r}: model_path is needed (sscd_disc_mixup.torchscript.pt, or a state dict of it)")
+        node = sc.get("data_transforms")
+        mean, std = [0.0], [1.0]
+        if node is not None:
+            tf = hydra_lite.instantiate(node) if isinstance(node, dict) and "_target_" in node else node
+            ts = tf.transforms if isinstance(tf, Compose) else None
+            if ts is None or len(ts) != 1 or not isinstance(ts[0], Normalize):
+                raise ValueError(f"metrics.sscd.data_transforms={node!r}: null or a Compose of exactly one Normalize is needed "
+                                 "(ToTensor and the normalisation run fused on the device)")
+            mean, std = list(ts[0].mean), list(ts[0].std)
+            if len(mean) not in (1, 3) or len(std) not in (1, 3) or not all(float(v) != 0 for v in std):
+                raise ValueError(f"metrics.sscd.data_transforms: Normalize(mean={mean}, std={std}) needs one or three means and "
+                                 "non-zero stds")
+        ckpt = str(cfg.get("pretrained_model_name_or_path") or "")
+        if not os.path.isdir(os.path.join(ckpt, "vae")):
+            raise FileNotFoundError(f"metrics.sscd embeds decoded validation images: no vae/ under {ckpt!r}")
+        mem = (cfg.get("data_files") or {}).get("mem_img_path")
+        if not mem or not os.path.isfile(str(mem)):
+            raise FileNotFoundError(f"metrics.sscd: data_files.mem_img_path {mem!r} (the memorized image; set from "
+                                    "clustering_info_path when deletion.frac_deletion is null) is not a file on disk")
+        if os.path.isfile(str(path)):
+            model = SSCDModel.load(str(path))
+        elif not (sc.get("allow_random_init") or cfg.get("allow_random_init")):
+            raise FileNotFoundError(f"metrics.sscd.model_path {path!r} is not a file on disk (pass allow_random_init=true for "
+                                    "random-init weights of the same architecture)")
+        else:
+            model = SSCDModel()
+            print(f"[siss_amd] allow_random_init: SSCD checkpoint {path!r} not on disk, RANDOM-INIT ResNet-50: the SSCD figures are "
+                  "NOT comparable with published ones")
+        if not cfg.get("eval_every"):
+            print("[siss_amd] metrics.sscd is set but eval_every is not: the score is taken at evaluations only")
+        return SSCDScore(model, str(mem), os.path.join(str(cfg.output_dir), "metrics_rank0.jsonl"), mean, std)
 
     def check_fraction_deletion(self):
         """metrics.fraction_deletion (delete_sd.py:224-225,:269-275; null / absent: nothing) needs classifier_path, that file on disk,
@@ -795,7 +844,10 @@ class DeleteSD(_DeleteBase):
         metrics.fraction_deletion the decoder's output goes to the k-means classifier on the device (one fused launch yields the grid's
         uint8 images and the distances, one more the labels): {global_step, deletion_fraction_<i>} per prompt -- the mean label over
         the eval_batches x eval_batch_size images (:271-273) -- is appended to metrics_rank0.jsonl, with deletion_steps_<i> on the
-        first evaluation whose fraction is 0 (:274-275)."""
+        first evaluation whose fraction is 0 (:274-275).  With metrics.sscd the same uint8 images go through the SSCD network
+        (sscd.SSCDScore: from the classifier's bytes when the fraction is on too, else bytes and embeddings in one pass from the
+        decoder's output) and {global_step, sscd_<i>} -- the mean cosine with the memorized image's embedding (:277-283) -- is appended
+        to the same file; only the scores, the labels and the grid's bytes leave the device."""
         import numpy as np
         cfg = self.cfg
         sampler = self.pipeline or self._validation_pipeline(unet, device)
@@ -811,16 +863,26 @@ class DeleteSD(_DeleteBase):
             out_type = "decoded"
             if self.fraction is None:
                 self.fraction = DeletionFraction(self.kmeans, os.path.join(cfg.output_dir, "metrics_rank0.jsonl"))
+        if self.sscd is not None:
+            if sampler.vae is None:
+                raise FileNotFoundError("metrics.sscd: the validation pipeline has no VAE decoder")
+            out_type = "decoded"
         with sampler.holding_graphs():
             for i, p in enumerate(vp):
                 e = self._prompt_embedding(p, device)
-                imgs, text_n, uncond_n, labels = [], [], [], []
+                imgs, text_n, uncond_n, labels, scores = [], [], [], [], []
                 for _ in range(nb):
                     im, st = sampler(e, negative_prompt_embeds=self._negative_embeds, num_inference_steps=steps,
                                      guidance_scale=7.5, num_images_per_prompt=bs, generator=g, output_type=out_type)
                     if out_type == "decoded":
-                        im, lab, _ = self.kmeans.from_decoded(im)       # uint8 [n, H, W, 3] + labels, still on the device
-                        labels.append(lab)
+                        if self.kmeans is not None:
+                            im, lab, _ = self.kmeans.from_decoded(im)   # uint8 [n, H, W, 3] + labels, still on the device
+                            labels.append(lab)
+                            if self.sscd is not None:
+                                scores.append(self.sscd.score_u8(im))   # the same bytes through the network
+                        else:
+                            sc, im = self.sscd.score_decoded(im)        # bytes and embeddings in one pass
+                            scores.append(sc)
                         imgs.extend(list(im.cpu().numpy()))
                     elif out_type == "np":
                         imgs.extend(list(im))
@@ -828,6 +890,8 @@ class DeleteSD(_DeleteBase):
                     uncond_n.extend(st["uncond_noise_norm"])
                 if labels:
                     self.fraction.record(i, torch.cat(labels).cpu(), step)
+                if scores:
+                    self.sscd.record(i, torch.cat(scores).cpu(), step)
                 if imgs:
                     _grid(imgs, int(np.sqrt(len(imgs)))).save(os.path.join(cfg.output_dir, f"validation_p{i}_step{step}.png"))
                 rec = {"step": step, "prompt": i, "prompt_text": None if p is None else str(p),
