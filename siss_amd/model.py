@@ -41,6 +41,11 @@ class _UNetFn(torch.autograd.Function):
             # torch.autograd.grad(..., sample): the image's cotangent only -- no parameter gradient is formed or touched
             grads[2] = eng.input_vjp(gout.contiguous().float()).to(sample.dtype)
             return tuple(grads)
+        if (len(ctx.inputs) > 2 and ctx.needs_input_grad[4] and hasattr(eng, "context_vjp")
+                and not torch._C._will_engine_execute_node(m._anchor_node())):
+            # torch.autograd.grad(..., encoder_hidden_states): the text's cotangent only, the same test as for the sample
+            grads[4] = eng.context_vjp(gout.contiguous().float()).to(ctx.inputs[2].dtype)
+            return tuple(grads)
         dx = torch.empty(sample.shape, dtype=torch.float32, device=sample.device) if want_dx else None
         eng.ps.grads[0].zero_()
         eng.backward(gout.contiguous().float(), nsets=1, **({"dx": dx} if want_dx else {}))

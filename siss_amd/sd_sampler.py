@@ -149,3 +149,25 @@ class SDSampler:
             return u8, stats
         from PIL import Image
         return [Image.fromarray(a) for a in u8], stats
+
+    def aug_prompt(self, prompt=None, height=None, width=None, num_inference_steps=50, guidance_scale=7.5, negative_prompt=None,
+                   num_images_per_prompt=1, eta=0.0, generator=None, latents=None, prompt_embeds=None, negative_prompt_embeds=None,
+                   target_steps=(0,), lr=0.1, optim_iters=10, target_loss=None, print_optim=False, optim_epsilon=None, alpha=0.5,
+                   return_trace=False):
+        """The reference's LocalStableDiffusionPipeline.aug_prompt (data/src/local_sd_pipeline.py:474-663), its argument names and
+        defaults: the prompt embedding [1, L, X] optimised (AdamW, row 0's gradient masked) so that the text-conditional noise norm
+        at the first target step goes down -- what validation_prompts[0] takes under using_augmented_prompt.  siss_amd/prompt_aug.py."""
+        from . import prompt_aug
+        return prompt_aug.aug_prompt(self, prompt, height, width, num_inference_steps, guidance_scale, negative_prompt,
+                                     num_images_per_prompt, eta, generator, latents, prompt_embeds, negative_prompt_embeds,
+                                     target_steps, lr, optim_iters, target_loss, print_optim, optim_epsilon, alpha, return_trace)
+
+    def get_text_cond_grad(self, prompt=None, height=None, width=None, num_inference_steps=50, guidance_scale=7.5,
+                           negative_prompt=None, num_images_per_prompt=1, eta=0.0, generator=None, latents=None, prompt_embeds=None,
+                           negative_prompt_embeds=None, target_steps=(0,), return_trace=False):
+        """The reference's get_text_cond_grad (:325-445): per-token L2 norms [L] of the noise norm's gradient with respect to the TEXT
+        embedding, averaged over the target steps.  siss_amd/prompt_aug.py."""
+        from . import prompt_aug
+        return prompt_aug.get_text_cond_grad(self, prompt, height, width, num_inference_steps, guidance_scale, negative_prompt,
+                                             num_images_per_prompt, eta, generator, latents, prompt_embeds, negative_prompt_embeds,
+                                             target_steps, return_trace)

@@ -49,6 +49,7 @@ class UNetCondEngine(UNetEngine):
     def __init__(self, cfg: UNet2DConditionConfig, device="cuda", dtype=torch.bfloat16):
         super().__init__(cfg, device, dtype=dtype)
         self.ctx = None
+        self._ctx_slabs, self._ctx_site = None, 0          # context_vjp(): the per-site f32 slabs of the text gradient, the next site
         # fused attention (csrc/flash_attn.hip) for the transformer blocks; False: batched GEMMs + row softmax with the
         # S x S matrices in HBM (the round-1 form: the parity tests compare the two; the f32 parity mode runs it -- the fused
         # kernels are bf16-only)
@@ -150,7 +151,11 @@ class UNetCondEngine(UNetEngine):
 
     def _linear_bwd(self, dy, xin, wname, rows2, rows_x, n_out, k_in, dx_out=None, accumulate=False, bias=True):
         """dy [rows2, n_out]: cotangent of y = xin W^T + b, xin [rows_x, k_in] shared by the sets when
-        rows_x < rows2.  dW (+ db) for every set; dx_out (+)= dy W."""
+        rows_x < rows2.  dW (+ db) for every set; dx_out (+)= dy W.  Under _vjp (context_vjp): the data gradient only."""
+        if self._vjp:
+            if dx_out is not None:
+                self._linear_dgrad(dy, wname, rows2, n_out, k_in, dx_out, accumulate)
+            return
         ps, gb, ns = self.ps, self.gbase, self.nsets
         rps = rows2 // ns
         dW = ps.grads[gb:, ps.specs[wname + ".weight"].off:]
@@ -164,8 +169,20 @@ class UNetCondEngine(UNetEngine):
         else:
             self.wgrads.launch(job, ops._nsplits(tiles, 1, ns, rps, False))
         if dx_out is not None:
-            ops.gemm_nt(lib.ptr(dy), n_out, self.wT[wname + ".weight"], lib.ptr(dx_out), k_in, rows2, k_in, n_out,
-                        [0], [0], res_ptr=lib.ptr(dx_out) if accumulate else None, ldr=k_in)
+            self._linear_dgrad(dy, wname, rows2, n_out, k_in, dx_out, accumulate)
+
+    def _linear_dgrad(self, dy, wname, rows2, n_out, k_in, dx_out, accumulate):
+        ops.gemm_nt(lib.ptr(dy), n_out, self.wT[wname + ".weight"], lib.ptr(dx_out), k_in, rows2, k_in, n_out,
+                    [0], [0], res_ptr=lib.ptr(dx_out) if accumulate else None, ldr=k_in)
+
+    def _ctx_site_grad(self, dk, dv, ldd, pre, rows, C, Ckv):
+        """context_vjp(): this cross-attention site's text gradient dK W_k + dV W_v (the [Ckv][C] dgrad copies), f32, into the
+        site's own slab -- the sites are summed in a fixed order afterwards (siss_ctx_reduce), never through bf16."""
+        slab = self._ctx_slabs[self._ctx_site]
+        assert slab.shape == (rows, Ckv), "context_vjp: one text row per key of the last forward()"
+        self._ctx_site += 1
+        lib.call("siss_ctx_dgrad", dk, dv, ldd, self.wT[pre + ".to_k.weight"], self.wT[pre + ".to_v.weight"], slab, rows, C, Ckv,
+                 int(self.f32))
 
     def _layernorm(self, x, pre, nm, rows, C):
         ps = self.ps
@@ -258,7 +275,7 @@ class UNetCondEngine(UNetEngine):
         def bwd(dout, rows2, dxq, dxkv):
             """dout [rows2, C] cotangent of `out` (the residual branch is the caller's).  dxq = dq W_q (+ for
             self-attention: dk W_k + dv W_v) is written to dxq; dxkv None: the keys / values come from the text
-            embedding, which takes no gradient."""
+            embedding, whose gradient is formed only under context_vjp() (_ctx_site_grad: into the site's f32 slab)."""
             nb = rows2 // Sq
             nBH = nb * Hh
             zp = ops.zero_page(self.device)
@@ -313,6 +330,9 @@ class UNetCondEngine(UNetEngine):
                 lib.call("siss_head_merge", dqh, dq, nb, Sq, Hh, D, Sqp, Dp)
                 lib.call("siss_head_merge", dkh, dk, nb, Sk, Hh, D, Skp, Dp)
                 lib.call("siss_head_merge", dvh, dv, nb, Sk, Hh, D, Skp, Dp)
+            if self._ctx_slabs is not None and xq is not xkv:
+                # dK and dV are data gradients, formed above whatever the mode: here they become the text's
+                self._ctx_site_grad(dk, dv, 2 * C if fused_kv else C, pre, nb * Sk, C, Ckv)
             if fused_qkv:
                 # one weight-gradient product for the [3C][C] matrix (cotangent rows [rows2, 3C]) and one three-panel product
                 # dx = dq W_q + dk W_k + dv W_v (panel p: cotangent columns [pC, (p+1)C) against the p-th transposed copy)
@@ -417,3 +437,38 @@ class UNetCondEngine(UNetEngine):
         ctx.copy_(e.reshape(-1, e.shape[2]))
         self.ctx = ctx
         return super().forward(x, t)
+
+    def context_vjp(self, cot, out=None, reduce=False):
+        """The vector-Jacobian product of the last forward(x, t, encoder_hidden_states=e) with respect to the TEXT e: cot
+        [N, Cout, H, W] f32 -> [N, L, X] f32, or with reduce [L, X] summed over the samples (what e.repeat(N, 1, 1) turns into under
+        autograd).  UNetEngine.input_vjp's replay -- one cotangent set, no weight-gradient product of any kind, the per-channel sums
+        of the norm kernels in the one-set scratch -- with every cross-attention site's dK W_k + dV W_v stored as f32 in a slab of
+        its own and the slabs summed in a fixed order by one finishing launch: no float atomics, the same bits on every call.  The
+        weights, the gradient buffers, the optimizer's moments, the sparse-fill state and the overwrite log are left as they were."""
+        assert cot.is_cuda and cot.dtype == torch.float32 and cot.is_contiguous()
+        N = cot.shape[0]
+        assert N == self.nf, "context_vjp: one cotangent per sample of the last forward()"
+        assert self.ctx is not None, "context_vjp: no forward() to differentiate"
+        for S, D in self._mha_sites:
+            self._mha_check(S, D, training=True)
+        L, X = self.ctx_len, self.cfg.cross_attention_dim
+        shape = (L, X) if reduce else (N, L, X)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape
+        ps = self.ps
+        nsites = sum(n.endswith(".attn2.to_k.weight") for n in ps.specs)
+        slabs = self._buf("ctxgrad.slabs", (nsites, N * L, X))
+        if self._vjp_sums is None:
+            self._vjp_sums = torch.zeros(1, ps.total, dtype=torch.float32, device=self.device)
+        with lib.f32_mode(self.f32):
+            grads, ps.grads = ps.grads, self._vjp_sums
+            self._vjp, self._ctx_slabs, self._ctx_site = True, slabs, 0
+            try:
+                self._input_vjp(cot)
+                assert self._ctx_site == nsites, f"context_vjp: {self._ctx_site} of {nsites} cross-attention sites ran"
+                lib.call("siss_ctx_reduce", slabs, out, nsites, N, L * X, int(reduce))
+            finally:
+                ps.grads = grads
+                self._vjp, self._ctx_slabs, self._ctx_site = False, None, 0
+        return out
