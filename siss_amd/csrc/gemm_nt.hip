@@ -553,6 +553,10 @@ int siss_gemm_nt_qstats(const void* A, long lda, const void* W, void* C, long ld
 // launch) whether a product of this shape lands there; when it does not, run the 1x1 product and pass its result as R to siss_gemm_nt.
 // qstats / written: as siss_gemm_nt_qstats (both may be null).  Each term is accumulated in f32 and rounded ONCE (the two-launch form
 // rounds the shortcut's output to bf16 first).
+// What the persistent kernel READS beyond what a stored value depends on (tests/test_hip_nt.py fills it with NaN): rows -1 and M of A2
+// (the shortcut operand is staged from the row above the tile; A2 needs one addressable row on each side, as every padded activation
+// has) and, in every launch with a residual, R at halo rows (loaded, then replaced by zero with a select).  Their content never
+// reaches C.  A is read at rows [min shift, M - 1 + max shift] of the panels' column windows and nowhere else.
 int siss_conv3x3_sc_takes(int M, int N, int Kp, int K2, int rows_per_image, int Wp, long lda, long ldc, long lda2) {
     return lda2 > 0 && c3p_eligible(M, N, Kp, rows_per_image, Wp, lda, ldc, 0, lda2, K2, 0, 0) ? 1 : 0;
 }
