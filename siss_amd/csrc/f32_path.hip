@@ -363,6 +363,10 @@ __global__ __launch_bounds__(256) void softmax_bwd_f32_kernel(const float* __res
     for (int k = lane; k < S; k += 64) ds[r * S + k] = scale * pr[k] * (dp[r * S + k] - dot);
 }
 __global__ void copy_f32_kernel(const float* __restrict__ a, float* __restrict__ o, long n) { FOR_ELEMS(n) o[i] = a[i]; }
+// x sigmoid(1.702 x) with an IEEE division and expf: the f32 mode is an instrument
+__global__ void quick_gelu_f32_kernel(const float* __restrict__ x, float* __restrict__ y, long n) {
+    FOR_ELEMS(n) { const float v = x[i]; y[i] = v / (1.f + expf(-1.702f * v)); }
+}
 // [taps][co][ci] f32 master slices -> [taps][ci][co] f32 with the tap order reversed (the dgrad operand copies; job table as
 // optimizer.hip's conv_weight_dgrad_multi: one block per 64 x 64 tile)
 struct WtJobF { long src, dst; int taps, co, ci, tile0; };
@@ -685,6 +689,12 @@ int siss_geglu_fwd_f32(const void* h, void* out, long rows, int F, void* stream)
 int siss_geglu_bwd_f32(const void* dout, const void* h, void* dh, long rows2, long rows_x, int F, void* stream) {
     SISS_CHECK_ARG(dout && h && dh && rows2 > 0 && rows_x > 0 && F > 0);
     geglu_bwd_f32_kernel<<<ew_grid(rows2 * F), 256, 0, (hipStream_t)stream>>>((const float*)dout, (const float*)h, (float*)dh, rows2, rows_x, F);
+    SISS_LAUNCH_RET();
+}
+// siss_quick_gelu with f32 rows (CLIP's text tower in f32: the anchors of the CLIP-IQA score), in place allowed, any n
+int siss_quick_gelu_f32(const void* x, void* y, long n, void* stream) {
+    SISS_CHECK_ARG(x && y && n > 0);
+    quick_gelu_f32_kernel<<<ew_grid(n), 256, 0, (hipStream_t)stream>>>((const float*)x, (float*)y, n);
     SISS_LAUNCH_RET();
 }
 int siss_head_split_f32(const void* src, void* dst, int B, int S, int H, int D, int Sp, int Dp, void* stream) {

@@ -668,11 +668,64 @@ class DeleteSD(_DeleteBase):
     kmeans = None               # metrics.fraction_deletion's classifier (check_fraction_deletion), its tracker built at the first use
     fraction = None
     sscd = None                 # metrics.sscd's tracker (check_sscd): the network on the host until the first evaluation
+    clip_iqa = None             # metrics.clip_iqa's tracker (check_clip_iqa): likewise
 
     def check_metrics(self):
         super().check_metrics()
         self.kmeans = self.check_fraction_deletion()
         self.sscd = self.check_sscd()
+        self.clip_iqa = self.check_clip_iqa()
+
+    def check_clip_iqa(self):
+        """metrics.clip_iqa (delete_sd.py:222-223,:264-267; null / absent / false: nothing; bare true: the mapping with no keys) needs
+        model_path (OpenAI's RN50.pt, or a state dict of it) on disk -- or allow_random_init=true: a random-init network of the same
+        architecture, loudly --, a checkpoint the loader accepts, a vae/ in the checkpoint directory (the network sees decoded
+        images), and the anchor prompts' token ids: prompt_ids_path (a .pt of ids [2, L]: "Good photo." / "Bad photo."), else a CLIP
+        tokenizer directory at tokenizer_path (default <pretrained_model_name_or_path>/tokenizer) -- refused here, before the first
+        step.  Returns the clip_iqa.CLIPIQAScore, or None."""
+        cfg = self.cfg
+        ci = (cfg.get("metrics") or {}).get("clip_iqa")
+        if not ci:
+            return None
+        ci = ci if isinstance(ci, dict) else {}
+        from .clip_iqa import PROMPTS, CLIPIQAModel, CLIPIQAScore, tokenize
+        path = ci.get("model_path")
+        if not path:
+            raise ValueError("metrics.clip_iqa: model_path is needed (OpenAI's CLIP RN50.pt, or a state dict of it)")
+        ckpt = str(cfg.get("pretrained_model_name_or_path") or "")
+        if not os.path.isdir(os.path.join(ckpt, "vae")):
+            raise FileNotFoundError(f"metrics.clip_iqa scores decoded validation images: no vae/ under {ckpt!r}")
+        bs = int(ci.get("batch_size") or 16)
+        if os.path.isfile(str(path)):
+            model = CLIPIQAModel.load(str(path), batch_size=bs)
+        elif not (ci.get("allow_random_init") or cfg.get("allow_random_init")):
+            raise FileNotFoundError(f"metrics.clip_iqa.model_path {path!r} is not a file on disk (pass allow_random_init=true for "
+                                    "random-init weights of the same architecture)")
+        else:
+            model = CLIPIQAModel(batch_size=bs)
+            print(f"[siss_amd] allow_random_init: CLIP checkpoint {path!r} not on disk, RANDOM-INIT CLIP RN50: the CLIP-IQA figures "
+                  "are NOT comparable with published ones")
+        ids_path = ci.get("prompt_ids_path")
+        tok_dir = str(ci.get("tokenizer_path") or os.path.join(ckpt, "tokenizer"))
+        if ids_path:
+            if not os.path.isfile(str(ids_path)):
+                raise FileNotFoundError(f"metrics.clip_iqa.prompt_ids_path {ids_path!r} is not a file on disk")
+            ids = torch.as_tensor(torch.load(str(ids_path), map_location="cpu"))
+            if ids.is_floating_point() or ids.dim() != 2 or ids.shape[0] != 2:
+                raise ValueError(f"metrics.clip_iqa.prompt_ids_path {ids_path!r}: integer token ids [2, L] are needed (the rows of "
+                                 f"{PROMPTS['quality'][0]!r} and {PROMPTS['quality'][1]!r}), got {ids.dtype} {tuple(ids.shape)}")
+        elif os.path.isdir(tok_dir):
+            ids = tokenize(PROMPTS["quality"], tok_dir, model.context_length)
+        else:
+            raise FileNotFoundError(f"metrics.clip_iqa needs the anchor prompts' token ids: neither prompt_ids_path nor a CLIP "
+                                    f"tokenizer directory at tokenizer_path ({tok_dir!r})")
+        if ids.shape[1] > model.context_length or int(ids.min()) < 0 or int(ids.max()) >= model.vocab_size:
+            raise ValueError(f"metrics.clip_iqa: prompt ids [2, {ids.shape[1]}] reaching {int(ids.max())} do not fit the text tower "
+                             f"({model.context_length} positions, vocabulary {model.vocab_size}): prompt_ids_path / tokenizer_path "
+                             "belong to another model")
+        if not cfg.get("eval_every"):
+            print("[siss_amd] metrics.clip_iqa is set but eval_every is not: the score is taken at evaluations only")
+        return CLIPIQAScore(model, ids, os.path.join(str(cfg.output_dir), "metrics_rank0.jsonl"))
 
     def check_sscd(self):
         """metrics.sscd (delete_sd.py:226-228,:277-283; null / absent: nothing) needs model_path on disk (or allow_random_init=true:
@@ -847,7 +900,10 @@ class DeleteSD(_DeleteBase):
         first evaluation whose fraction is 0 (:274-275).  With metrics.sscd the same uint8 images go through the SSCD network
         (sscd.SSCDScore: from the classifier's bytes when the fraction is on too, else bytes and embeddings in one pass from the
         decoder's output) and {global_step, sscd_<i>} -- the mean cosine with the memorized image's embedding (:277-283) -- is appended
-        to the same file; only the scores, the labels and the grid's bytes leave the device."""
+        to the same file.  With metrics.clip_iqa the same uint8 images go through the CLIP RN50 (clip_iqa.CLIPIQAScore: from the bytes
+        the other two metrics made when one of them is on, else bytes and scores in one pass) and {global_step, clip_iqa_<i>} -- the
+        mean probability of "Good photo." against "Bad photo." (:264-267) -- is appended as well; only the scores, the labels and
+        the grid's bytes leave the device."""
         import numpy as np
         cfg = self.cfg
         sampler = self.pipeline or self._validation_pipeline(unet, device)
@@ -867,10 +923,14 @@ class DeleteSD(_DeleteBase):
             if sampler.vae is None:
                 raise FileNotFoundError("metrics.sscd: the validation pipeline has no VAE decoder")
             out_type = "decoded"
+        if self.clip_iqa is not None:
+            if sampler.vae is None:
+                raise FileNotFoundError("metrics.clip_iqa: the validation pipeline has no VAE decoder")
+            out_type = "decoded"
         with sampler.holding_graphs():
             for i, p in enumerate(vp):
                 e = self._prompt_embedding(p, device)
-                imgs, text_n, uncond_n, labels, scores = [], [], [], [], []
+                imgs, text_n, uncond_n, labels, scores, iqa = [], [], [], [], [], []
                 for _ in range(nb):
                     im, st = sampler(e, negative_prompt_embeds=self._negative_embeds, num_inference_steps=steps,
                                      guidance_scale=7.5, num_images_per_prompt=bs, generator=g, output_type=out_type)
@@ -880,9 +940,14 @@ class DeleteSD(_DeleteBase):
                             labels.append(lab)
                             if self.sscd is not None:
                                 scores.append(self.sscd.score_u8(im))   # the same bytes through the network
-                        else:
+                        elif self.sscd is not None:
                             sc, im = self.sscd.score_decoded(im)        # bytes and embeddings in one pass
                             scores.append(sc)
+                        else:
+                            sc, im = self.clip_iqa.score_decoded(im)    # bytes and probabilities in one pass
+                            iqa.append(sc)
+                        if self.clip_iqa is not None and (self.kmeans is not None or self.sscd is not None):
+                            iqa.append(self.clip_iqa.score_u8(im))      # the same bytes through the CLIP RN50
                         imgs.extend(list(im.cpu().numpy()))
                     elif out_type == "np":
                         imgs.extend(list(im))
@@ -892,6 +957,8 @@ class DeleteSD(_DeleteBase):
                     self.fraction.record(i, torch.cat(labels).cpu(), step)
                 if scores:
                     self.sscd.record(i, torch.cat(scores).cpu(), step)
+                if iqa:
+                    self.clip_iqa.record(i, torch.cat(iqa).cpu(), step)
                 if imgs:
                     _grid(imgs, int(np.sqrt(len(imgs)))).save(os.path.join(cfg.output_dir, f"validation_p{i}_step{step}.png"))
                 rec = {"step": step, "prompt": i, "prompt_text": None if p is None else str(p),

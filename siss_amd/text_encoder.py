@@ -7,7 +7,12 @@ Forward only (the module is frozen: ``requires_grad_(False)``, delete_sd.py:476-
 (q/k/v/out projections, QK^T, PV, fc1, fc2) runs on the MFMA NT GEMM with bias and residual fused in its epilogue.
 Weights are kept as bf16 operand copies (f32 biases and LayerNorm parameters), keyed by the transformers state-dict
 names (``text_model.`` prefix optional, as it differs between transformers 4.x and 5.x).
+
+``dtype=torch.float32`` keeps f32 operands and buffers and runs the same loop under ``lib.f32_mode(True)`` (the ``_f32`` forms of
+the same launchers): the text tower of the CLIP-IQA anchors (siss_amd/clip_iqa.py), an instrument, not a fast path.
 """
+import contextlib
+
 import torch
 
 from . import lib, ops
@@ -18,7 +23,10 @@ def _up(n, m):
 
 
 class CLIPTextEncoder:
-    def __init__(self, state_dict, num_attention_heads=12, layer_norm_eps=1e-5, device="cuda"):
+    def __init__(self, state_dict, num_attention_heads=12, layer_norm_eps=1e-5, device="cuda", dtype=torch.bfloat16):
+        if dtype not in (torch.bfloat16, torch.float32):
+            raise TypeError(f"CLIPTextEncoder(dtype={dtype}): torch.bfloat16 or torch.float32")
+        self.dtype, self.f32 = dtype, dtype == torch.float32
         lib.load()
         self.device = torch.device(device)
         lib.ensure_workspace(self.device)
@@ -35,7 +43,7 @@ class CLIPTextEncoder:
             if k.startswith("embeddings."):
                 continue
             if k.endswith("_proj.weight") or k.endswith("fc1.weight") or k.endswith("fc2.weight"):
-                self.w[k] = v.to(self.device, torch.bfloat16).contiguous()          # GEMM operand copy [out][in]
+                self.w[k] = v.to(self.device, self.dtype).contiguous()              # GEMM operand copy [out][in]
             else:
                 self.f[k] = v.to(self.device, torch.float32).contiguous()           # biases, LayerNorm gamma / beta
         self.inner = self.w["encoder.layers.0.mlp.fc1.weight"].shape[0]
@@ -53,7 +61,8 @@ class CLIPTextEncoder:
         return cls(load_file(os.path.join(d, "model.safetensors")), cfg.get("num_attention_heads", 12),
                    cfg.get("layer_norm_eps", 1e-5), device)
 
-    def _buf(self, name, shape, dtype=torch.bfloat16):
+    def _buf(self, name, shape, dtype=None):
+        dtype = dtype or self.dtype
         k = (name, tuple(shape), dtype)
         b = self._bufs.get(k)
         if b is None:
@@ -82,7 +91,7 @@ class CLIPTextEncoder:
         D = C // Hh
         Dp, Sp = _up(D, 64), _up(S, 64)
         rows, BH = B * S, B * Hh
-        bb = lambda n, shape, dt=torch.bfloat16: self._buf(n, shape, dt)
+        bb = lambda n, shape, dt=None: self._buf(n, shape, dt)
         x, y = bb("x", (rows, C)), bb("y", (rows, C))
         x.copy_((self.tok[ids] + self.pos[:S]).reshape(rows, C))          # embedding gather: plumbing
         h = bb("h", (rows, C))
@@ -91,25 +100,26 @@ class CLIPTextEncoder:
         vT, sc, p = bb("vT", (BH, Dp, Sp)), bb("sc", (BH, Sp, Sp)), bb("p", (BH, Sp, Sp))
         oh, o = bb("oh", (BH, Sp, Dp)), bb("o", (rows, C))
         f1 = bb("f1", (rows, self.inner))
-        for i in range(self.n_layers):
-            pre = f"encoder.layers.{i}"
-            self._ln(x, pre + ".layer_norm1", h, rows)
-            for nm, dst, hd in (("q_proj", q, qh), ("k_proj", k, kh), ("v_proj", v, vh)):
-                self._linear(h, f"{pre}.self_attn.{nm}", dst, rows, C, C)
-                lib.call("siss_head_split", dst, hd, B, S, Hh, D, Sp, Dp)
-            lib.call("siss_transpose_bf16", vh, vT, BH, Sp, Dp)
-            ops.gemm_nt(lib.ptr(qh), Dp, kh, lib.ptr(sc), Sp, Sp, Sp, Dp, [0], [0], alpha=D ** -0.5, batch=BH,
-                        stride_a=Sp * Dp, stride_w=Sp * Dp, stride_c=Sp * Sp)
-            lib.call("siss_softmax_rows_fwd", sc, p, BH * Sp, S, Sp, Sp)         # causal: key <= query
-            ops.gemm_nt(lib.ptr(p), Sp, vT, lib.ptr(oh), Dp, Sp, Dp, Sp, [0], [0], batch=BH,
-                        stride_a=Sp * Sp, stride_w=Dp * Sp, stride_c=Sp * Dp)
-            lib.call("siss_head_merge", oh, o, B, S, Hh, D, Sp, Dp)
-            self._linear(o, pre + ".self_attn.out_proj", y, rows, C, C, residual=x)       # y = x + attn
-            self._ln(y, pre + ".layer_norm2", h, rows)
-            self._linear(h, pre + ".mlp.fc1", f1, rows, self.inner, C)
-            lib.call("siss_quick_gelu", f1, f1, f1.numel())
-            self._linear(f1, pre + ".mlp.fc2", x, rows, C, self.inner, residual=y)        # x = y + mlp
-        self._ln(x, "final_layer_norm", h, rows)
+        with lib.f32_mode(True) if self.f32 else contextlib.nullcontext():
+            for i in range(self.n_layers):
+                pre = f"encoder.layers.{i}"
+                self._ln(x, pre + ".layer_norm1", h, rows)
+                for nm, dst, hd in (("q_proj", q, qh), ("k_proj", k, kh), ("v_proj", v, vh)):
+                    self._linear(h, f"{pre}.self_attn.{nm}", dst, rows, C, C)
+                    lib.call("siss_head_split", dst, hd, B, S, Hh, D, Sp, Dp)
+                lib.call("siss_transpose_bf16", vh, vT, BH, Sp, Dp)
+                ops.gemm_nt(lib.ptr(qh), Dp, kh, lib.ptr(sc), Sp, Sp, Sp, Dp, [0], [0], alpha=D ** -0.5, batch=BH,
+                            stride_a=Sp * Dp, stride_w=Sp * Dp, stride_c=Sp * Sp)
+                lib.call("siss_softmax_rows_fwd", sc, p, BH * Sp, S, Sp, Sp)         # causal: key <= query
+                ops.gemm_nt(lib.ptr(p), Sp, vT, lib.ptr(oh), Dp, Sp, Dp, Sp, [0], [0], batch=BH,
+                            stride_a=Sp * Sp, stride_w=Dp * Sp, stride_c=Sp * Dp)
+                lib.call("siss_head_merge", oh, o, B, S, Hh, D, Sp, Dp)
+                self._linear(o, pre + ".self_attn.out_proj", y, rows, C, C, residual=x)       # y = x + attn
+                self._ln(y, pre + ".layer_norm2", h, rows)
+                self._linear(h, pre + ".mlp.fc1", f1, rows, self.inner, C)
+                lib.call("siss_quick_gelu_f32" if self.f32 else "siss_quick_gelu", f1, f1, f1.numel())
+                self._linear(f1, pre + ".mlp.fc2", x, rows, C, self.inner, residual=y)        # x = y + mlp
+            self._ln(x, "final_layer_norm", h, rows)
         out = h.float().view(B, S, C).clone()
         if return_dict:
             return type("BaseModelOutput", (), {"last_hidden_state": out})()
