@@ -1,6 +1,6 @@
 """Quality metrics of the MNIST T-shirt experiment: the reference's MNIST ResNet-18 (metrics/mnist_resnet.py) on the HIP implicit-GEMM
-convolution of csrc/classifier.hip, and the class surface around it -- `Classifier` (metrics/classifier.py), `InceptionScore`
-(metrics/inception_score.py), `TShirtClassifier` (metrics/tshirt.py) -- plus `TShirtMetrics`, the tracker of delete_tshirt.py's
+convolution of csrc/metric_conv.hip (behind siss_amd/metric_net.py), and the class surface around it -- `Classifier`
+(metrics/classifier.py), `InceptionScore` (metrics/inception_score.py), `TShirtClassifier` (metrics/tshirt.py) -- plus `TShirtMetrics`, the tracker of delete_tshirt.py's
 log_metrics (fraction -> deletion_steps -> Inception Score trigger) that the task loop drives.
 
 The network runs in f32, in eval mode (BatchNorm with its running statistics, folded into the convolutions at load time in f64);
@@ -14,10 +14,10 @@ from collections import OrderedDict
 
 import torch
 
-from . import lib
+from . import metric_net as mn
+from .metric_net import conv_splits  # noqa: F401  (tests/test_hip_sscd.py reads the split-K choice from here)
 
 BN_EPS = 1e-5
-BK = 32                     # K step of cls_conv_kernel: packed weight rows are zero-padded to a multiple of it
 _WIDTHS = (64, 128, 256, 512)
 
 
@@ -37,75 +37,19 @@ def _convs(in_ch):
     return out
 
 
-def fold_bn(sd, conv, bn, eps=BN_EPS):
-    """(w', b') in f64 of the convolution `conv` followed by the eval-mode BatchNorm `bn` of the state dict `sd`:
-    w' = w gamma / sqrt(var + eps), b' = beta - mean gamma / sqrt(var + eps)."""
-    w = sd[conv + ".weight"].double()
-    scale = sd[bn + ".weight"].double() / torch.sqrt(sd[bn + ".running_var"].double() + eps)
-    b = sd[bn + ".bias"].double() - sd[bn + ".running_mean"].double() * scale
-    return w * scale.view(-1, 1, 1, 1), b
-
-
-def pack_conv(w, b, stride, pad, device):
-    """A layer of siss_cls_conv from f64 weights [Cout, Cin, k, k] and bias [Cout], each rounded once to f32: the weights as
-    [Cout][Kp] in (kh, kw, ci) order, zero-padded to Kp % 32 == 0."""
-    cout, cin, kh, kw = w.shape
-    K = kh * kw * cin
-    Kp = -(-K // BK) * BK
-    wp = torch.zeros(cout, Kp, dtype=torch.float32)
-    wp[:, :K] = w.permute(0, 2, 3, 1).reshape(cout, K).float()
-    return dict(w=wp.to(device), b=b.float().to(device), cin=cin, cout=cout, k=kh, stride=stride, pad=pad, Kp=Kp)
-
-
-def conv_out(L, H, W):
-    k, s, p = L["k"], L["stride"], L["pad"]
-    return (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
-
-
-def conv_splits(M, cout, Kp):
-    """Split-K where the grid is small (the late layers / fc at small N): up to one block per CU, >= 4 K steps per split."""
-    steps = Kp // BK
-    blocks = -(-M // 64) * -(-cout // 64)
-    return 1 if blocks >= 128 else max(1, min(steps // 4, -(-256 // blocks)))
-
-
-def run_conv(L, x, N, H, W, relu, res=None, nchw_in=False):
-    """One siss_cls_conv launch of the packed layer L on x (NHWC [N, H, W, Cin], or the NCHW image when nchw_in): (y NHWC, Ho, Wo)."""
-    k, s, p = L["k"], L["stride"], L["pad"]
-    Ho, Wo = conv_out(L, H, W)
-    M, cout = N * Ho * Wo, L["cout"]
-    y = torch.empty(N, Ho, Wo, cout, device=x.device, dtype=torch.float32)
-    splits = conv_splits(M, cout, L["Kp"])
-    ws = torch.empty(splits * M * cout, device=x.device, dtype=torch.float32) if splits > 1 else None
-    lib.call("siss_cls_conv", x, int(nchw_in), L["w"], L["b"], res, y, ws, 0 if ws is None else ws.numel(),
-             N, H, W, L["cin"], Ho, Wo, cout, k, k, s, p, L["Kp"], int(relu), splits)
-    return y, Ho, Wo
-
-
-def max_pool(x, N, H, W, C):
-    """nn.MaxPool2d(3, 2, 1) on NHWC (siss_cls_maxpool): (y, Ho, Wo)."""
-    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-    y = torch.empty(N, Ho, Wo, C, device=x.device, dtype=torch.float32)
-    lib.call("siss_cls_maxpool", x, y, N, H, W, C, Ho, Wo)
-    return y, Ho, Wo
-
-
-class ResNet18:
+class ResNet18(mn.MetricNet):
     """metrics/mnist_resnet.py's resnet18(num_classes, grayscale) on the HIP kernels: `[N, C, H, W]` f32 images -> `[N, num_classes]`
     logits (the reference disables avgpool, so fc reads the flattened 512 x 1 x 1 map: H, W <= 32).  The parameters live on the host
     under torch's key names; `.to(device)` / the first call packs them (BN folded) onto the device."""
 
     def __init__(self, num_classes, grayscale):
         self.num_classes, self.in_ch = int(num_classes), (1 if grayscale else 3)
-        self.device = torch.device("cpu")
-        self.training = False
-        self._packed = None
         sd = OrderedDict()
         # the reference's constructor: conv N(0, sqrt(2 / (k^2 Cout))), BN weight 1 / bias 0 (stats 0 / 1), nn.Linear's default for fc;
         # drawn from a fork of the global generator, so that building the metric leaves the global stream where it was
         with torch.random.fork_rng(devices=[]):
             self._init(sd)
-        self._sd = self._ordered(sd)
+        super().__init__(self._ordered(sd))
 
     def _init(self, sd):
         for name, cin, cout, k, _, _, bn in _convs(self.in_ch):
@@ -125,60 +69,16 @@ class ResNet18:
         keys += ["fc.weight", "fc.bias"]
         return OrderedDict((k, sd[k]) for k in keys)
 
-    # -- the nn.Module surface the reference uses ------------------------------------------------
-    def to(self, device):
-        self.device = torch.device(device)
-        self._packed = None
-        return self
-
-    def eval(self):
-        self.training = False
-        return self
-
-    def train(self, mode=True):
-        if mode:
-            raise NotImplementedError("ResNet18 runs in eval mode only (BatchNorm folded into the convolutions); the reference's "
-                                      "metrics put the classifier in eval() before use")
-        return self.eval()
-
-    def state_dict(self):
-        return OrderedDict((k, v.clone()) for k, v in self._sd.items())
-
-    def load_state_dict(self, sd, strict=True):
-        """Strict over torch's key names; only `num_batches_tracked` may be missing.  Missing / unexpected keys or a wrong shape raise."""
-        want = self._sd
-        got = {k: v for k, v in sd.items()}
-        missing = [k for k in want if k not in got and not k.endswith("num_batches_tracked")]
-        unexpected = [k for k in got if k not in want]
-        if missing or unexpected:
-            raise RuntimeError(f"ResNet18.load_state_dict: missing keys {missing}, unexpected keys {unexpected}")
-        for k, v in got.items():
-            if tuple(v.shape) != tuple(want[k].shape):
-                raise RuntimeError(f"ResNet18.load_state_dict: {k} has shape {tuple(v.shape)}, the model {tuple(want[k].shape)}")
-        new = OrderedDict()
-        for k, v in want.items():
-            src = got.get(k, v)
-            new[k] = src.detach().to("cpu", torch.long if k.endswith("num_batches_tracked") else torch.float32).clone()
-        self._sd = new
-        self._packed = None
-        return None
-
-    # -- packing ---------------------------------------------------------------------------------
     def _pack(self):
-        """Per convolution: w' = w gamma / sqrt(var + eps), b' = beta - mean gamma / sqrt(var + eps) in f64, rounded once to f32;
-        weights as [Cout][Kp] in (kh, kw, ci) order, zero-padded to Kp % 32 == 0.  fc is a 1 x 1 convolution with its bias."""
-        if self.device.type != "cuda":
-            raise RuntimeError("ResNet18: call .to(<cuda device>) first -- the network runs on the HIP kernels only")
+        """Per convolution the folded BN in f64, rounded once to f32 (metric_net.pack_conv); fc is a 1 x 1 convolution with its bias."""
+        self._need_device()
         sd = self._sd
         layers = {}
         for name, cin, cout, k, s, p, bn in _convs(self.in_ch):
-            layers[name] = pack_conv(*fold_bn(sd, name, bn), s, p, self.device)
-        layers["fc"] = pack_conv(sd["fc.weight"].double().view(self.num_classes, 512, 1, 1), sd["fc.bias"].double(), 1, 0, self.device)
+            layers[name] = mn.pack_conv(*mn.fold_bn(sd, name, bn, BN_EPS), s, p, self.device)
+        layers["fc"] = mn.pack_conv(sd["fc.weight"].double().view(self.num_classes, 512, 1, 1), sd["fc.bias"].double(), 1, 0,
+                                            self.device)
         self._packed = layers
-
-    # -- forward ---------------------------------------------------------------------------------
-    def _conv(self, L, x, N, H, W, relu, res=None, nchw_in=False):
-        return run_conv(L, x, N, H, W, relu, res, nchw_in)
 
     @torch.no_grad()
     def __call__(self, x):
@@ -193,17 +93,16 @@ class ResNet18:
         x = x.to(self.device, torch.float32).contiguous()
         if N == 0:
             return torch.empty(0, self.num_classes, device=self.device)
-        P = self._packed
-        h, H, W = self._conv(P["conv1"], x, N, H, W, relu=True, nchw_in=True)
-        h, H, W = max_pool(h, N, H, W, 64)
+        P, conv = self._packed, mn.conv
+        h = mn.max_pool3(conv(P["conv1"], x, nchw_in=True), 2, 1)
         for i in range(1, 5):
             for j in range(2):
                 pre = f"layer{i}.{j}."
-                a, Ha, Wa = self._conv(P[pre + "conv1"], h, N, H, W, relu=True)
-                sc = self._conv(P[pre + "downsample.0"], h, N, H, W, relu=False)[0] if pre + "downsample.0" in P else h
-                h, H, W = self._conv(P[pre + "conv2"], a, N, Ha, Wa, relu=True, res=sc)
-        assert H == 1 and W == 1
-        return self._conv(P["fc"], h, N, 1, 1, relu=False)[0].view(N, self.num_classes)
+                a = conv(P[pre + "conv1"], h)
+                sc = conv(P[pre + "downsample.0"], h, relu=False) if pre + "downsample.0" in P else h
+                h = conv(P[pre + "conv2"], a, res=sc)
+        assert h.shape[1] == 1 and h.shape[2] == 1
+        return mn.linear(P["fc"], h.view(N, 512))
 
     forward = __call__
 

@@ -4,7 +4,7 @@ image tower (a three-convolution stem, Bottlenecks [3, 4, 6, 3] whose stride is 
 shortcut's 1 x 1, BN eps 1e-5, attention pooling called WITHOUT its positional embedding, at the image's own size: no resize, no crop)
 and the text tower that embeds the anchor prompts "Good photo." / "Bad photo."; the score is the positive anchor's share of
 softmax(100 cos(image, anchors)) -- on the HIP kernels: every convolution and the q / c_proj / text_projection products on
-classifier.hip's implicit-GEMM convolution, the preprocessing on sscd.hip's, the average pools, the attention pool and the score on
+metric_conv.hip's implicit-GEMM convolution, the preprocessing on sscd.hip's, the average pools, the attention pool and the score on
 csrc/clip_iqa.hip, the text tower on `CLIPTextEncoder(dtype=torch.float32)`.  `CLIPIQAScore` is the tracker the task loop drives.
 
 The attention pool has one query (the mean token) per head, so the key and value projections of the T = HW + 1 tokens are never
@@ -16,22 +16,20 @@ torch.autocast (fp16) -- a deliberate deviation, as for every metric network her
 raises.  Neither the checkpoint nor torchmetrics / piq was available when this was written: everything is restated from the public
 description (tests/clip_iqa_ref.py is the same restatement in torch.nn); tools/check_clip_iqa.py is the check for whoever has them.
 """
-import json
 import math
 import os
-import zipfile
 from collections import OrderedDict
 
 import torch
 
 from . import lib
-from .classifier import conv_out, conv_splits, fold_bn, pack_conv, run_conv
+from . import metric_net as mn
 
+BN_EPS = 1e-5
 CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
 CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
 ACT = torch.float32         # of every activation and result (the host test of the wiring runs this module on f64 emulations)
 NORM_EPS = 1e-12            # of the anchors' normalisation (F.normalize's default; the rows are far from it)
-MAX_ELEMENTS = 1 << 31      # an activation (or split-K slab) of a chunk stays below this many elements
 OPTIONAL_KEYS = ("input_resolution", "context_length", "vocab_size", "logit_scale")    # may be absent from / extra in a checkpoint
 # torchmetrics' built-in prompt pairs (functional/multimodal/clip_iqa.py _PROMPTS): name -> (positive, negative)
 PROMPTS = OrderedDict([
@@ -120,11 +118,16 @@ def pack_linear(w, b, device):
     return w.to(device, torch.float32).contiguous(), b.to(device, torch.float32).contiguous()
 
 
-class CLIPIQAModel:
+class CLIPIQAModel(mn.ChunkedImageNet):
     """OpenAI CLIP RN50 as clip_iqa uses it: `[N, 3, H, W]` f32 images, already normalised -> the raw `[N, output_dim]` rows of the
     image tower on the device; `anchors(ids)` the unit rows of the text tower; `scores_*` the probabilities `[N, P]`.  The parameters
     live on the host under the OpenAI state dict's key names; `.to(device)` / the first call packs them (BN folded) onto the device.
     Images go through in chunks of `batch_size`.  The architecture's sizes are arguments so that small networks can be built."""
+
+    # Strict over the key names: only `num_batches_tracked` and `logit_scale` may be missing, only `input_resolution`, `context_length`
+    # and `vocab_size` (the scalars an OpenAI archive carries) may be extra.
+    optional_missing = (".num_batches_tracked",) + OPTIONAL_KEYS
+    ignored = OPTIONAL_KEYS
 
     def __init__(self, layers=(3, 4, 6, 3), width=64, heads=None, output_dim=1024, input_resolution=224, text_width=512, text_heads=8,
                  text_layers=12, vocab_size=49408, context_length=77, batch_size=16):
@@ -146,10 +149,6 @@ class CLIPIQAModel:
                              "width that is a multiple of 8 are needed")
         if min(self.output_dim, self.batch_size, self.text_layers, self.vocab_size, self.context_length) <= 0 or self.input_resolution < 32:
             raise ValueError("CLIPIQAModel: positive sizes (and input_resolution >= 32) are needed")
-        self.device = torch.device("cpu")
-        self.training = False
-        self._packed = self._text = None
-        self._anchors = {}
         E, C, sd = self.embed, self.text_width, OrderedDict()
         with torch.random.fork_rng(devices=[]):      # building the metric leaves the global random stream where it was
             sd["positional_embedding"] = torch.empty(self.context_length, C).normal_(0, 0.01)
@@ -177,48 +176,10 @@ class CLIPIQAModel:
                 sd[p + "ln_2.weight"], sd[p + "ln_2.bias"] = torch.ones(C), torch.zeros(C)
             sd["token_embedding.weight"] = torch.empty(self.vocab_size, C).normal_(0, 0.02)
             sd["ln_final.weight"], sd["ln_final.bias"] = torch.ones(C), torch.zeros(C)
-        self._sd = sd           # (filled in the OpenAI module's order: its own parameters, visual, transformer, token_embedding, ln_final)
+        super().__init__(sd)    # (filled in the OpenAI module's order: its own parameters, visual, transformer, token_embedding, ln_final)
 
-    # -- the nn.Module surface -------------------------------------------------------------------
-    def to(self, device):
-        device = torch.device(device)
-        if device != self.device:
-            self.device, self._packed, self._text, self._anchors = device, None, None, {}
-        return self
-
-    def eval(self):
-        self.training = False
-        return self
-
-    def train(self, mode=True):
-        if mode:
-            raise NotImplementedError("CLIPIQAModel runs in eval mode only (BatchNorm folded into the convolutions); the metric "
-                                      "never trains its network")
-        return self.eval()
-
-    def state_dict(self):
-        return OrderedDict((k, v.clone()) for k, v in self._sd.items())
-
-    def load_state_dict(self, sd, strict=True):
-        """Strict over the key names: only `num_batches_tracked` and `logit_scale` may be missing, only `input_resolution`,
-        `context_length` and `vocab_size` (the scalars an OpenAI archive carries) may be extra.  Anything else, or a wrong shape,
-        raises with the keys listed."""
-        want = self._sd
-        got = {k: v for k, v in sd.items() if k in want or k not in OPTIONAL_KEYS}
-        missing = [k for k in want if k not in got and not k.endswith("num_batches_tracked") and k not in OPTIONAL_KEYS]
-        unexpected = [k for k in got if k not in want]
-        if missing or unexpected:
-            raise RuntimeError(f"CLIPIQAModel.load_state_dict: missing keys {missing}, unexpected keys {unexpected}")
-        for k, v in got.items():
-            if tuple(v.shape) != tuple(want[k].shape):
-                raise RuntimeError(f"CLIPIQAModel.load_state_dict: {k} has shape {tuple(v.shape)}, the model {tuple(want[k].shape)}")
-        new = OrderedDict()
-        for k, v in want.items():
-            src = got.get(k, v)
-            new[k] = src.detach().to("cpu", torch.long if k.endswith("num_batches_tracked") else torch.float32).clone()
-        self._sd = new
+    def _dropped(self):
         self._packed, self._text, self._anchors = None, None, {}
-        return None
 
     @classmethod
     def load(cls, path, batch_size=16):
@@ -226,22 +187,7 @@ class CLIPIQAModel:
         RN50.pt in), else a `torch.load` state dict, else -- when the file is not a zip archive -- a `.safetensors` file.  The sizes
         are read from the tensors' shapes, as OpenAI's build_model reads them.  Any other key set raises RuntimeError with the
         missing and unexpected keys."""
-        path = str(path)
-        if not os.path.isfile(path):
-            raise FileNotFoundError(f"CLIP checkpoint {path!r} is not a file on disk")
-        if zipfile.is_zipfile(path):
-            try:
-                sd = torch.jit.load(path, map_location="cpu").state_dict()
-            except RuntimeError:                        # a zip archive without TorchScript code: torch.save's format
-                sd = torch.load(path, map_location="cpu")
-        else:
-            try:
-                from safetensors.torch import load_file
-                sd = load_file(path, device="cpu")
-            except Exception as e:
-                raise RuntimeError(f"{path}: neither a TorchScript / torch.save archive nor a .safetensors file ({e})") from e
-        if not isinstance(sd, dict) or not all(torch.is_tensor(v) for v in sd.values()):
-            raise RuntimeError(f"{path}: a state dict of tensors is needed, got {type(sd).__name__}")
+        sd = mn.read_state_dict(path, "CLIP")
         kw = {}
         try:
             blocks = lambda i: len({k.split(".")[2] for k in sd if k.startswith(f"visual.layer{i}.")})
@@ -263,19 +209,15 @@ class CLIPIQAModel:
         return net.eval()
 
     # -- packing ---------------------------------------------------------------------------------
-    def _need_device(self):
-        if self.device.type != "cuda":
-            raise RuntimeError("CLIPIQAModel: call .to(<cuda device>) first -- the network runs on the HIP kernels only")
-
     def _pack(self):
         self._need_device()
         sd, E = self._sd, self.embed
         P = {}
         for name, _, _, _, s, p, bn, _ in visual_convs(self.layers, self.width):
-            P[name] = pack_conv(*fold_bn(sd, "visual." + name, "visual." + bn), s, p, self.device)
+            P[name] = mn.pack_conv(*mn.fold_bn(sd, "visual." + name, "visual." + bn, BN_EPS), s, p, self.device)
         for name in ("q_proj", "c_proj"):
             w = sd[f"visual.attnpool.{name}.weight"].double()
-            P[name] = pack_conv(w.view(w.shape[0], E, 1, 1), sd[f"visual.attnpool.{name}.bias"].double(), 1, 0, self.device)
+            P[name] = mn.pack_conv(w.view(w.shape[0], E, 1, 1), sd[f"visual.attnpool.{name}.bias"].double(), 1, 0, self.device)
         for name in ("k_proj", "v_proj"):                # (visual.attnpool.positional_embedding is loaded and not used)
             P[name + ".w"], P[name + ".b"] = pack_linear(sd[f"visual.attnpool.{name}.weight"], sd[f"visual.attnpool.{name}.bias"], self.device)
         self._packed = P
@@ -292,9 +234,9 @@ class CLIPIQAModel:
             if min(H, W) < 1:
                 raise ValueError(f"CLIPIQAModel: the map in front of {name} is empty: the images are too small")
             L = P[name]
-            Ho, Wo = conv_out(L, H, W)
+            Ho, Wo = mn.conv_out(L, H, W)
             M = N * Ho * Wo
-            big = max(big, M * L["cout"] * conv_splits(M, L["cout"], L["Kp"]))
+            big = max(big, M * L["cout"] * mn.conv_splits(M, L["cout"], L["Kp"]))
             return Ho, Wo
         for name in ("conv1", "conv2", "conv3"):
             H, W = after(name, H, W)
@@ -315,12 +257,13 @@ class CLIPIQAModel:
         return self._shapes(N, H, W)[1]
 
     # -- forward ---------------------------------------------------------------------------------
-    def _avg_pool(self, x, N, H, W, C, k=2):
+    def _avg_pool(self, x, k=2):
+        N, H, W, C = x.shape
         if H < k or W < k:
             raise ValueError(f"CLIPIQAModel: a {H} x {W} map in front of AvgPool2d({k}): the images are too small")
         y = torch.empty(N, H // k, W // k, C, device=x.device, dtype=ACT)
         lib.call("siss_clipiqa_avgpool", x, y, N, H, W, C, k)
-        return y, H // k, W // k
+        return y
 
     def attention_pool(self, h, N, HW, return_logits=False):
         """The NHWC layer4 map `h` ([N, HW, embed] as rows) -> [N, output_dim]: mean token, q, the folded query, the logits over the
@@ -330,7 +273,7 @@ class CLIPIQAModel:
         f32 = dict(device=h.device, dtype=ACT)
         m = torch.empty(N, E, **f32)
         lib.call("siss_clipiqa_token_mean", h, m, N, HW, E)
-        q = run_conv(P["q_proj"], m.view(N, 1, 1, E), N, 1, 1, relu=False)[0]
+        q = mn.linear(P["q_proj"], m)
         qt, c = torch.empty(N, Hh, E, **f32), torch.empty(N, Hh, **f32)
         lib.call("siss_clipiqa_fold_query", q, P["k_proj.w"], P["k_proj.b"], qt, c, N, E, Hh, float((E // Hh) ** -0.5))
         s = torch.empty(N, Hh, HW + 1, **f32)
@@ -339,47 +282,29 @@ class CLIPIQAModel:
         lib.call("siss_clipiqa_pool", h, m, s, xbar, N, HW, E, Hh)
         o = torch.empty(N, E, **f32)
         lib.call("siss_clipiqa_head_value", xbar, P["v_proj.w"], P["v_proj.b"], o, N, E, Hh)
-        out = run_conv(P["c_proj"], o.view(N, 1, 1, E), N, 1, 1, relu=False)[0].view(N, self.output_dim)
+        out = mn.linear(P["c_proj"], o)
         return (out, s) if return_logits else out
 
     def _features(self, x):
         """One chunk: the normalised NCHW images -> the image tower's raw rows [n, output_dim]."""
-        N, _, H, W = x.shape
-        if H < 1 or W < 1:
-            raise ValueError(f"CLIPIQAModel: empty images {tuple(x.shape)}")
-        big = self.max_elements(N, H, W)
-        if big >= MAX_ELEMENTS:
-            raise ValueError(f"CLIPIQAModel: a chunk of {N} images of {H} x {W} holds a tensor of {big} elements, 2^31 or more: lower "
-                             f"batch_size (now {self.batch_size})")
+        N, H, W = self._chunk_shape(x)
         P = self._packed
-        h, H, W = run_conv(P["conv1"], x, N, H, W, relu=True, nchw_in=True)
-        h, H, W = run_conv(P["conv2"], h, N, H, W, relu=True)
-        h, H, W = run_conv(P["conv3"], h, N, H, W, relu=True)
-        h, H, W = self._avg_pool(h, N, H, W, self.width)
+        h = mn.conv(P["conv3"], mn.conv(P["conv2"], mn.conv(P["conv1"], x, nchw_in=True)))
+        h = self._avg_pool(h)
         for i, n in enumerate(self.layers, 1):
-            planes = self.width * 2 ** (i - 1)
             for j in range(n):
                 pre = f"layer{i}.{j}."
                 s = 2 if (i > 1 and j == 0) else 1
-                a = run_conv(P[pre + "conv1"], h, N, H, W, relu=True)[0]
-                a = run_conv(P[pre + "conv2"], a, N, H, W, relu=True)[0]          # stride 1: the stride is the pool behind it
-                sc, Ho, Wo = h, H, W
+                a = mn.conv(P[pre + "conv2"], mn.conv(P[pre + "conv1"], h))      # stride 1: the stride is the pool behind it
+                sc = h
                 if s > 1:
-                    a, Ho, Wo = self._avg_pool(a, N, H, W, planes)
+                    a = self._avg_pool(a)
                 if pre + "downsample.0" in P:
                     if s > 1:
-                        sc = self._avg_pool(h, N, H, W, h.shape[3])[0]
-                    sc = run_conv(P[pre + "downsample.0"], sc, N, Ho, Wo, relu=False)[0]
-                h, H, W = run_conv(P[pre + "conv3"], a, N, Ho, Wo, relu=True, res=sc)
-        return self.attention_pool(h, N, H * W)
-
-    def _preprocess(self, src, form, want_u8):
-        n = src.shape[0]
-        h, w = (src.shape[1], src.shape[2]) if form == 0 else (src.shape[2], src.shape[3])
-        x = torch.empty(n, 3, h, w, device=self.device, dtype=torch.float32)
-        u8 = torch.empty(n, h, w, 3, device=self.device, dtype=torch.uint8) if want_u8 else None
-        lib.call("siss_sscd_preprocess", src, form, n, h, w, *CLIP_MEAN, *CLIP_STD, u8, x)
-        return x, u8
+                        sc = self._avg_pool(h)
+                    sc = mn.conv(P[pre + "downsample.0"], sc, relu=False)
+                h = mn.conv(P[pre + "conv3"], a, res=sc)
+        return self.attention_pool(h, N, h.shape[1] * h.shape[2])
 
     def _score(self, rows, anchors):
         n, P = rows.shape[0], anchors.shape[0] // 2
@@ -387,46 +312,13 @@ class CLIPIQAModel:
         lib.call("siss_clipiqa_score", rows, anchors, n, self.output_dim, P, out)
         return out
 
-    @torch.no_grad()
     def _run(self, src, form, anchors):
         """Chunks of batch_size through (preprocess ->) the image tower (-> the score): (rows, scores or None, uint8 or None)."""
-        if self._packed is None:
-            self._pack()
-        n = src.shape[0]
-        if n == 0:
-            raise ValueError("CLIPIQAModel: no images")
         if anchors is not None:
             anchors = anchors.to(self.device, ACT).contiguous()
             if anchors.dim() != 2 or anchors.shape[0] < 2 or anchors.shape[0] % 2 or anchors.shape[1] != self.output_dim:
                 raise ValueError(f"anchor rows [2 P, {self.output_dim}] are needed, got {tuple(anchors.shape)}")
-        rows, scores, u8s = [], [], []
-        for s in range(0, n, self.batch_size):
-            part = src[s:s + self.batch_size].contiguous()
-            u8 = None
-            if form is not None:
-                part, u8 = self._preprocess(part, form, want_u8=form != 0)
-            r = self._features(part)
-            rows.append(r)
-            scores.append(None if anchors is None else self._score(r, anchors))
-            u8s.append(u8)
-        cat = lambda xs: None if xs[0] is None else (xs[0] if len(xs) == 1 else torch.cat(xs))
-        return cat(rows), cat(scores), cat(u8s)
-
-    def _check_u8(self, u8):
-        u8 = torch.as_tensor(u8)
-        if u8.dtype != torch.uint8 or u8.dim() != 4 or u8.shape[3] != 3:
-            raise ValueError(f"uint8 images [n, H, W, 3] are needed, got {u8.dtype} {tuple(u8.shape)}")
-        self._need_device()
-        return u8.to(self.device)
-
-    def _check_decoded(self, img):
-        if not (torch.is_tensor(img) and img.is_cuda and img.dim() == 4 and img.shape[1] == 3):
-            raise ValueError("the decoder's output [n, 3, H, W] on the device is needed")
-        if img.dtype not in (torch.float32, torch.bfloat16):
-            raise TypeError(f"decoder output of dtype {img.dtype}: float32 or bfloat16")
-        if img.device != self.device:
-            raise ValueError(f"decoder output on {img.device}, the network on {self.device}")
-        return 2 if img.dtype == torch.bfloat16 else 1
+        return self._chunks(src, form, CLIP_MEAN, CLIP_STD, lambda r: (r, None if anchors is None else self._score(r, anchors)))
 
     def __call__(self, x, anchors=None):
         """`[N, 3, H, W]` f32, already normalised with CLIP's mean / std -> the image tower's raw rows `[N, output_dim]`; with
@@ -492,12 +384,11 @@ class CLIPIQAModel:
                 if self._packed is None:
                     self._pack()
                 wp = self._sd["text_projection"].double().t().contiguous().view(self.output_dim, C, 1, 1)
-                self._packed["text_projection"] = pack_conv(wp, torch.zeros(self.output_dim, dtype=torch.float64), 1, 0, self.device)
-            a = run_conv(self._packed["text_projection"], rows.view(n, 1, 1, C), n, 1, 1, relu=False)[0].view(n, self.output_dim)
+                self._packed["text_projection"] = mn.pack_conv(wp, torch.zeros(self.output_dim, dtype=torch.float64), 1, 0, self.device)
+            a = mn.linear(self._packed["text_projection"], rows)
             lib.call("siss_sscd_normalize_score", a, n, self.output_dim, NORM_EPS, None, a, None)
             self._anchors[key] = a
         return self._anchors[key]
-
 
 
 def tokenize(prompts, tokenizer, context_length=77):
@@ -599,8 +490,4 @@ class CLIPIQAScore:
         return self.model.scores_decoded(img, self._anchors(img.device))
 
     def record(self, prompt, scores, step):
-        value = float(torch.as_tensor(scores).detach().cpu().double().mean())
-        rec = {"global_step": int(step), f"clip_iqa_{prompt}": value if math.isfinite(value) else None}
-        with open(self.out_path, "a") as f:
-            f.write(json.dumps(rec) + "\n")
-        return rec
+        return mn.record_mean(self.out_path, f"clip_iqa_{prompt}", scores, step)

@@ -1,7 +1,7 @@
 // The SD experiment's image-quality score (delete_sd.py:222-223,:264-267: torchmetrics' CLIPImageQualityAssessment with its
 // defaults -- the OpenAI CLIP RN50 "ModifiedResNet", its attention pooling, and the softmax over the cosines with the two anchor
 // prompts "Good photo." / "Bad photo.").  The convolutions and the three small projections (q, c_proj as 1 x 1 convolutions on a
-// 1 x 1 map) run on classifier.hip's siss_cls_conv, the preprocessing on sscd.hip's siss_sscd_preprocess; this file holds what is
+// 1 x 1 map) run on metric_conv.hip's siss_metric_conv, the preprocessing on sscd.hip's siss_sscd_preprocess; this file holds what is
 // around them, f32 in and out:
 //   - avgpool     : the anti-aliasing nn.AvgPool2d(k) of the stem, of a Bottleneck's main path and of its shortcut, NHWC, with floor
 //   - token_mean  : the mean over the HW positions of the layer4 map: the attention pool's only query and its first token

@@ -1,7 +1,7 @@
 // The SD experiment's copy-detection score (delete_sd.py:226-228,:277-283: the SSCD network `sscd_disc_mixup.torchscript.pt`, a
 // torchvision-layout ResNet-50 with GeM pooling, a 2048 -> 512 linear layer and L2 normalisation; the score is the cosine of the
-// memorized image's embedding and a validation image's).  The trunk and the linear layer run on classifier.hip's siss_cls_conv /
-// siss_cls_maxpool; this file holds what is around them, f32 in and out:
+// memorized image's embedding and a validation image's).  The trunk and the linear layer run on metric_conv.hip's siss_metric_conv /
+// siss_metric_maxpool3; this file holds what is around them, f32 in and out:
 //   - preprocess     : the network's input from uint8 images, or straight from the VAE decoder's output (quantised exactly as
 //                      kmeans.hip quantises it, decoded_u8.h; the bytes are written too, for the PNG grid):
 //                      Normalize(mean, std)(ToTensor(.)) = ((u8 / 255) - mean[c]) / std[c], each operation an IEEE f32 operation as

@@ -1,5 +1,6 @@
 """The FID metric of the CelebA-HQ experiment (metrics/fid.py of the reference: `FIDEvaluator` around torchmetrics'
-`FrechetInceptionDistance(normalize=True, reset_real_features=False)`, feature dimension 2048) on the HIP kernels of csrc/inception.hip:
+`FrechetInceptionDistance(normalize=True, reset_real_features=False)`, feature dimension 2048) on the HIP kernels of
+csrc/metric_conv.hip (behind siss_amd/metric_net.py) and csrc/inception.hip:
 `InceptionV3FID` (the FID Inception-v3 of torch-fidelity, pt_inception-2015-12-05, up to the global average pool),
 `FrechetInceptionDistance` (the six statistics on the device in f64, the eigenvalue step on the host) and `FIDEvaluator`, plus
 `FIDTracker`, what the task loop drives.
@@ -18,16 +19,12 @@ from collections import OrderedDict
 import torch
 
 from . import lib
+from . import metric_net as mn
 
 BN_EPS = 1e-3
-BK = 32                     # K step of inc_conv_kernel: input channel strides and packed weight rows are multiples of it
 FEATURES = 2048
 SIZE = 299
 DEFAULT_CKPT = "checkpoints/classifiers/pt_inception-2015-12-05-6726825d.pth"
-
-
-def _pair(v):
-    return (v, v) if isinstance(v, int) else tuple(v)
 
 
 def _block_a(name, cin, pf):
@@ -67,74 +64,7 @@ def convs():
             (p + "_1", 768, 192, 1, 1, 0), (p + "_2", 192, 192, (1, 7), 1, (0, 3)), (p + "_3", 192, 192, (7, 1), 1, (3, 0)),
             (p + "_4", 192, 192, 3, 2, 0)]
     out += _block_e("Mixed_7b", 1280) + _block_e("Mixed_7c", 2048)
-    return [(n, ci, co, _pair(k), s, _pair(p)) for n, ci, co, k, s, p in out]
-
-
-def _padded(c):
-    """The channel stride a C-channel activation is carried with: C itself for the image, else the next multiple of the K step."""
-    return c if c <= 4 else -(-c // BK) * BK
-
-
-def conv_splits(M, cout, Kp):
-    """Split-K factor of one convolution: 1 when the 64 x 64 tiles number at least 128, else enough splits for up to 256 blocks -- one
-    per CU of an MI355X -- with at least 4 K steps per split (the 17 x 17 and 8 x 8 maps at small N).  128 and 256 are taken over from
-    the classifier's convolution and rest on the CU count alone: no sweep has been run for these shapes."""
-    steps = Kp // BK
-    blocks = -(-M // 64) * -(-cout // 64)
-    return 1 if blocks >= 128 else max(1, min(steps // 4, -(-256 // blocks)))
-
-
-def pack_conv(w, b, stride, pad, device):
-    """A packed layer from f64 / f32 conv weights [Cout, Cin, KH, KW] and bias [Cout] (BN already folded): the weights as [Cout][Kp]
-    f32 in (kh, kw, ci) order over the padded channel stride (zero weights on the padding), Kp % 32 == 0."""
-    cout, cin, kh, kw = w.shape
-    cp = _padded(cin)
-    K = kh * kw * cp
-    Kp = -(-K // BK) * BK
-    wp = torch.zeros(cout, kh, kw, cp, dtype=torch.float32)
-    wp[..., :cin] = w.permute(0, 2, 3, 1).float()
-    wk = torch.zeros(cout, Kp, dtype=torch.float32)
-    wk[:, :K] = wp.reshape(cout, K)
-    ph, pw = _pair(pad)
-    return dict(w=wk.to(device), b=b.float().to(device), cin=cin, cin_p=cp, cout=cout, kh=kh, kw=kw, stride=int(stride), ph=ph, pw=pw,
-                Kp=Kp)
-
-
-def conv_bn_relu(L, x, out=None, col=0):
-    """relu(conv(x) + bias) of a packed layer on NHWC f32 x [N, H, W, C] (C the layer's Cin or its padded stride), written into
-    out[..., col:col + Cout] (a fresh [N, Ho, Wo, padded Cout] buffer, zero beyond Cout, when out is None).  Returns that buffer."""
-    N, H, W, C = x.shape
-    if C != L["cin_p"]:
-        if C != L["cin"]:
-            raise ValueError(f"conv_bn_relu: the input has {C} channels, the layer {L['cin']} (carried as {L['cin_p']})")
-        x = torch.nn.functional.pad(x, (0, L["cin_p"] - C))
-    x = x.contiguous()
-    Ho = (H + 2 * L["ph"] - L["kh"]) // L["stride"] + 1
-    Wo = (W + 2 * L["pw"] - L["kw"]) // L["stride"] + 1
-    cout = L["cout"]
-    if out is None:
-        cp = _padded(cout)
-        out = (torch.empty if cp == cout else torch.zeros)(N, Ho, Wo, cp, device=x.device, dtype=torch.float32)
-    if tuple(out.shape[:3]) != (N, Ho, Wo) or not out.is_contiguous() or col < 0 or col + cout > out.shape[3]:
-        raise ValueError(f"conv_bn_relu: output {tuple(out.shape)} does not take {(N, Ho, Wo, cout)} at column {col}")
-    M = N * Ho * Wo
-    splits = conv_splits(M, cout, L["Kp"])
-    ws = torch.empty(splits * M * cout, device=x.device, dtype=torch.float32) if splits > 1 else None
-    lib.call("siss_inc_conv", x, L["w"], L["b"], out, ws, 0 if ws is None else ws.numel(), N, H, W, L["cin_p"], Ho, Wo, cout,
-             L["kh"], L["kw"], L["stride"], L["ph"], L["pw"], L["Kp"], out.shape[3], col, splits)
-    return out
-
-
-def max_pool3(x, stride, pad, out=None, col=0):
-    """3 x 3 max pool of NHWC f32 x into out[..., col:col + C] (a fresh buffer when None)."""
-    N, H, W, C = x.shape
-    Ho, Wo = (H + 2 * pad - 3) // stride + 1, (W + 2 * pad - 3) // stride + 1
-    if out is None:
-        out = torch.empty(N, Ho, Wo, C, device=x.device, dtype=torch.float32)
-    if tuple(out.shape[:3]) != (N, Ho, Wo) or not out.is_contiguous() or col < 0 or col + C > out.shape[3]:
-        raise ValueError(f"max_pool3: output {tuple(out.shape)} does not take {(N, Ho, Wo, C)} at column {col}")
-    lib.call("siss_inc_maxpool", x.contiguous(), out, N, H, W, C, Ho, Wo, stride, pad, out.shape[3], col)
-    return out
+    return [(n, ci, co, mn.pair(k), s, mn.pair(p)) for n, ci, co, k, s, p in out]
 
 
 def avg_pool3(x):
@@ -163,16 +93,15 @@ def preprocess(imgs):
     return out
 
 
-class InceptionV3FID:
+class InceptionV3FID(mn.MetricNet):
     """torch-fidelity's FeatureExtractorInceptionV3 (the network torchmetrics' FrechetInceptionDistance(feature=2048) runs) on the HIP
     kernels: `[N, 3, H, W]` f32 images in [0, 1] -> `[N, 2048]` pool features.  The parameters live on the host under the key names of
     pt_inception-2015-12-05-6726825d.pth (`<block>.<branch>.conv.weight`, `<block>.<branch>.bn.*`, `fc.*`; fc is loaded and checked
     but not run); `.to(device)` / the first call packs them (BN folded) onto the device."""
 
+    ignored = (".num_batches_tracked",)         # a BatchNorm's counter, which eval mode never reads, is passed over
+
     def __init__(self):
-        self.device = torch.device("cpu")
-        self.training = False
-        self._packed = None
         sd = OrderedDict()
         # He-normal convolutions under identity BatchNorms (activations stay O(1) through the 94 layers), drawn from a fork of the
         # global generator, so that building the metric leaves the global stream where it was
@@ -184,56 +113,13 @@ class InceptionV3FID:
             bound = 1.0 / math.sqrt(FEATURES)
             sd["fc.weight"] = torch.empty(1008, FEATURES).uniform_(-bound, bound)
             sd["fc.bias"] = torch.empty(1008).uniform_(-bound, bound)
-        self._sd = sd
+        super().__init__(sd)
 
-    # -- the nn.Module surface the metric uses ---------------------------------------------------
-    def to(self, device):
-        self.device = torch.device(device)
-        self._packed = None
-        return self
-
-    def eval(self):
-        self.training = False
-        return self
-
-    def train(self, mode=True):
-        if mode:
-            raise NotImplementedError("InceptionV3FID runs in eval mode only (BatchNorm folded into the convolutions), as the FID "
-                                      "feature extractor always does")
-        return self.eval()
-
-    def state_dict(self):
-        return OrderedDict((k, v.clone()) for k, v in self._sd.items())
-
-    def load_state_dict(self, sd, strict=True):
-        """Strict over the checkpoint's key names (a BatchNorm's `num_batches_tracked`, which eval mode never reads, is passed over).
-        Missing / unexpected keys or a wrong shape raise."""
-        want = self._sd
-        got = {k: v for k, v in sd.items() if not k.endswith(".num_batches_tracked")}
-        missing = [k for k in want if k not in got]
-        unexpected = [k for k in got if k not in want]
-        if missing or unexpected:
-            raise RuntimeError(f"InceptionV3FID.load_state_dict: missing keys {missing}, unexpected keys {unexpected}")
-        for k, v in got.items():
-            if tuple(v.shape) != tuple(want[k].shape):
-                raise RuntimeError(f"InceptionV3FID.load_state_dict: {k} has shape {tuple(v.shape)}, the model {tuple(want[k].shape)}")
-        self._sd = OrderedDict((k, got[k].detach().to("cpu", torch.float32).clone()) for k in want)
-        self._packed = None
-        return None
-
-    # -- packing ---------------------------------------------------------------------------------
     def _pack(self):
-        """Per convolution: w' = w gamma / sqrt(var + eps), b' = beta - mean gamma / sqrt(var + eps) in f64, rounded once to f32."""
-        if self.device.type != "cuda":
-            raise RuntimeError("InceptionV3FID: call .to(<cuda device>) first -- the network runs on the HIP kernels only")
-        sd = self._sd
-        layers = {}
-        for name, _, _, _, stride, pad in convs():
-            bn = name + ".bn"
-            scale = sd[bn + ".weight"].double() / torch.sqrt(sd[bn + ".running_var"].double() + BN_EPS)
-            b = sd[bn + ".bias"].double() - sd[bn + ".running_mean"].double() * scale
-            layers[name] = pack_conv(sd[name + ".conv.weight"].double() * scale.view(-1, 1, 1, 1), b, stride, pad, self.device)
-        self._packed = layers
+        """Per convolution the folded BN in f64, rounded once to f32 (metric_net.pack_conv)."""
+        self._need_device()
+        self._packed = {name: mn.pack_conv(*mn.fold_bn(self._sd, name + ".conv", name + ".bn", BN_EPS), stride, pad, self.device)
+                        for name, _, _, _, stride, pad in convs()}
 
     # -- forward ---------------------------------------------------------------------------------
     def _out(self, x, c, stride=1):
@@ -244,8 +130,8 @@ class InceptionV3FID:
     def _chain(self, x, names, out=None, col=0):
         P = self._packed
         for n in names[:-1]:
-            x = conv_bn_relu(P[n], x)
-        return conv_bn_relu(P[names[-1]], x, out, col)
+            x = mn.conv(P[n], x)
+        return mn.conv(P[names[-1]], x, out=out, col=col)
 
     def _a(self, name, x, pf):
         y, b = self._out(x, 224 + pf), name + ".branch"
@@ -259,7 +145,7 @@ class InceptionV3FID:
         y, b = self._out(x, 768, stride=2), name + ".branch"
         self._chain(x, [b + "3x3"], y, 0)
         self._chain(x, [b + "3x3dbl_1", b + "3x3dbl_2", b + "3x3dbl_3"], y, 384)
-        max_pool3(x, 2, 0, y, 480)
+        mn.max_pool3(x, 2, 0, y, 480)
         return y
 
     def _c(self, name, x):
@@ -274,18 +160,18 @@ class InceptionV3FID:
         y, b = self._out(x, 1280, stride=2), name + ".branch"
         self._chain(x, [b + "3x3_1", b + "3x3_2"], y, 0)
         self._chain(x, [b + f"7x7x3_{i}" for i in (1, 2, 3, 4)], y, 320)
-        max_pool3(x, 2, 0, y, 512)
+        mn.max_pool3(x, 2, 0, y, 512)
         return y
 
     def _e(self, name, x, pooled):
         y, b, P = self._out(x, 2048), name + ".branch", self._packed
         self._chain(x, [b + "1x1"], y, 0)
-        t = conv_bn_relu(P[b + "3x3_1"], x)
-        conv_bn_relu(P[b + "3x3_2a"], t, y, 320)
-        conv_bn_relu(P[b + "3x3_2b"], t, y, 704)
+        t = mn.conv(P[b + "3x3_1"], x)
+        mn.conv(P[b + "3x3_2a"], t, out=y, col=320)
+        mn.conv(P[b + "3x3_2b"], t, out=y, col=704)
         t = self._chain(x, [b + "3x3dbl_1", b + "3x3dbl_2"])
-        conv_bn_relu(P[b + "3x3dbl_3a"], t, y, 1088)
-        conv_bn_relu(P[b + "3x3dbl_3b"], t, y, 1472)
+        mn.conv(P[b + "3x3dbl_3a"], t, out=y, col=1088)
+        mn.conv(P[b + "3x3dbl_3b"], t, out=y, col=1472)
         self._chain(pooled, [b + "_pool"], y, 1856)
         return y
 
@@ -294,9 +180,9 @@ class InceptionV3FID:
         if self._packed is None:
             self._pack()
         x = self._chain(x, ["Conv2d_1a_3x3", "Conv2d_2a_3x3", "Conv2d_2b_3x3"])
-        x = max_pool3(x, 2, 0)
+        x = mn.max_pool3(x, 2, 0)
         x = self._chain(x, ["Conv2d_3b_1x1", "Conv2d_4a_3x3"])
-        x = max_pool3(x, 2, 0)
+        x = mn.max_pool3(x, 2, 0)
         x = self._a("Mixed_5b", x, 32)
         x = self._a("Mixed_5c", x, 64)
         x = self._a("Mixed_5d", x, 64)
@@ -305,15 +191,14 @@ class InceptionV3FID:
             x = self._c(name, x)
         x = self._d("Mixed_7a", x)
         x = self._e("Mixed_7b", x, avg_pool3(x))
-        x = self._e("Mixed_7c", x, max_pool3(x, 1, 1))          # the FID variant: a MAX pool in the last block's pool branch
+        x = self._e("Mixed_7c", x, mn.max_pool3(x, 1, 1))          # the FID variant: a MAX pool in the last block's pool branch
         return global_avg(x)
 
     @torch.no_grad()
     def __call__(self, imgs):
         if imgs.dim() != 4 or imgs.shape[1] != 3:
             raise ValueError(f"InceptionV3FID expects [N, 3, H, W] images in [0, 1], got {tuple(imgs.shape)}")
-        if self.device.type != "cuda":
-            raise RuntimeError("InceptionV3FID: call .to(<cuda device>) first -- the network runs on the HIP kernels only")
+        self._need_device()
         if imgs.shape[0] == 0:
             return torch.empty(0, FEATURES, device=self.device)
         return self.features(preprocess(imgs.to(self.device, torch.float32)))

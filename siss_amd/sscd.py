@@ -1,7 +1,7 @@
 """The SD experiment's copy-detection score (delete_sd.py:226-228,:277-283): the SSCD network -- `sscd_disc_mixup.torchscript.pt`, a
 torchvision-layout ResNet-50 (Bottleneck [3, 4, 6, 3], the stride on the 3 x 3 conv2, BN eps 1e-5) whose average pool is GeM pooling
 (p = 3, eps 1e-6), whose fc is a 2048 -> dims linear layer, followed by F.normalize -- on the HIP kernels: the trunk and fc on
-classifier.hip's implicit-GEMM convolution (fc as a 1 x 1 convolution on a 1 x 1 map), the preprocessing, GeM pooling and the
+metric_conv.hip's implicit-GEMM convolution (fc as a 1 x 1 convolution on a 1 x 1 map), the preprocessing, GeM pooling and the
 normalisation with the score on csrc/sscd.hip.  `SSCDScore` is the tracker the task loop drives.
 
 The network runs in f32, in eval mode (BatchNorm folded into the convolutions at pack time in f64); the reference runs it under
@@ -9,23 +9,20 @@ torch.autocast (fp16) -- a deliberate deviation, as for every metric network her
 raises.  Neither the checkpoint nor torchvision was available when this was written: the architecture is restated from its public
 description (tests/sscd_ref.py is the same restatement in torch.nn); tools/check_sscd.py is the check for whoever has the file.
 """
-import json
 import math
-import os
-import zipfile
 from collections import OrderedDict
 
 import torch
 
 from . import lib
-from .classifier import conv_out, conv_splits, fold_bn, max_pool, pack_conv, run_conv
+from . import metric_net as mn
 
+BN_EPS = 1e-5
 BLOCKS = (3, 4, 6, 3)
 WIDTHS = (64, 128, 256, 512)
 FEATURES = 2048
 GEM_EPS = 1e-6              # GlobalGeMPool2d's clamp
 NORM_EPS = 1e-12            # F.normalize's default
-MAX_ELEMENTS = 1 << 31      # an activation (or split-K slab) of a chunk stays below this many elements
 _ALIASES = {"embeddings.1.weight": "backbone.fc.weight", "embeddings.1.bias": "backbone.fc.bias"}
 
 
@@ -55,7 +52,7 @@ def _three(v, what):
     return v
 
 
-class SSCDModel:
+class SSCDModel(mn.ChunkedImageNet):
     """The SSCD ResNet-50: `[N, 3, H, W]` f32 images, already normalised -> `[N, dims]` unit rows on the device.  The parameters live
     on the host under torchvision's key names with the prefix `backbone.`; `.to(device)` / the first call packs them (BN folded)
     onto the device.  Images are embedded in chunks of `batch_size`."""
@@ -64,9 +61,6 @@ class SSCDModel:
         self.dims, self.pool_param, self.batch_size = int(dims), float(pool_param), int(batch_size)
         if self.dims <= 0 or self.pool_param <= 0 or self.batch_size <= 0:
             raise ValueError(f"SSCDModel(dims={dims!r}, pool_param={pool_param!r}, batch_size={batch_size!r}): positive values are needed")
-        self.device = torch.device("cpu")
-        self.training = False
-        self._packed = None
         sd = OrderedDict()
         # torchvision's constructor: conv kaiming_normal_(fan_out, relu), BN weight 1 / bias 0 (stats 0 / 1), nn.Linear's default for
         # fc; drawn from a fork of the global generator, so that building the metric leaves the global stream where it was
@@ -80,46 +74,7 @@ class SSCDModel:
             bound = 1.0 / math.sqrt(FEATURES)
             sd["backbone.fc.weight"] = torch.empty(self.dims, FEATURES).uniform_(-bound, bound)
             sd["backbone.fc.bias"] = torch.empty(self.dims).uniform_(-bound, bound)
-        self._sd = sd           # (filled in torch's order: a convolution, then its BN; fc last)
-
-    # -- the nn.Module surface -------------------------------------------------------------------
-    def to(self, device):
-        device = torch.device(device)
-        if device != self.device:
-            self.device, self._packed = device, None
-        return self
-
-    def eval(self):
-        self.training = False
-        return self
-
-    def train(self, mode=True):
-        if mode:
-            raise NotImplementedError("SSCDModel runs in eval mode only (BatchNorm folded into the convolutions); the reference "
-                                      "loads a TorchScript archive exported in eval mode")
-        return self.eval()
-
-    def state_dict(self):
-        return OrderedDict((k, v.clone()) for k, v in self._sd.items())
-
-    def load_state_dict(self, sd, strict=True):
-        """Strict over the key names; only `num_batches_tracked` may be missing.  Missing / unexpected keys or a wrong shape raise."""
-        want = self._sd
-        got = {k: v for k, v in sd.items()}
-        missing = [k for k in want if k not in got and not k.endswith("num_batches_tracked")]
-        unexpected = [k for k in got if k not in want]
-        if missing or unexpected:
-            raise RuntimeError(f"SSCDModel.load_state_dict: missing keys {missing}, unexpected keys {unexpected}")
-        for k, v in got.items():
-            if tuple(v.shape) != tuple(want[k].shape):
-                raise RuntimeError(f"SSCDModel.load_state_dict: {k} has shape {tuple(v.shape)}, the model {tuple(want[k].shape)}")
-        new = OrderedDict()
-        for k, v in want.items():
-            src = got.get(k, v)
-            new[k] = src.detach().to("cpu", torch.long if k.endswith("num_batches_tracked") else torch.float32).clone()
-        self._sd = new
-        self._packed = None
-        return None
+        super().__init__(sd)    # (filled in torch's order: a convolution, then its BN; fc last)
 
     @classmethod
     def load(cls, path, pool_param=3.0, batch_size=16):
@@ -127,22 +82,7 @@ class SSCDModel:
         in), else a `torch.load` state dict, else -- when the file is not a zip archive -- a `.safetensors` file.  The linear layer
         is taken as `backbone.fc.{weight,bias}` or as `embeddings.1.{weight,bias}`; its rows give `dims`.  Any other key set (a
         ClassyVision-style trunk among them) raises RuntimeError with the missing and unexpected keys."""
-        path = str(path)
-        if not os.path.isfile(path):
-            raise FileNotFoundError(f"SSCD checkpoint {path!r} is not a file on disk")
-        if zipfile.is_zipfile(path):
-            try:
-                sd = torch.jit.load(path, map_location="cpu").state_dict()
-            except RuntimeError:                        # a zip archive without TorchScript code: torch.save's format
-                sd = torch.load(path, map_location="cpu")
-        else:
-            try:
-                from safetensors.torch import load_file
-                sd = load_file(path, device="cpu")
-            except Exception as e:
-                raise RuntimeError(f"{path}: neither a TorchScript / torch.save archive nor a .safetensors file ({e})") from e
-        if not isinstance(sd, dict) or not all(torch.is_tensor(v) for v in sd.values()):
-            raise RuntimeError(f"{path}: a state dict of tensors is needed, got {type(sd).__name__}")
+        sd = mn.read_state_dict(path, "SSCD")
         clash = [a for a, k in _ALIASES.items() if a in sd and k in sd]
         if clash:
             raise RuntimeError(f"{path}: the linear layer is there twice ({clash} beside backbone.fc.*)")
@@ -158,14 +98,13 @@ class SSCDModel:
 
     # -- packing ---------------------------------------------------------------------------------
     def _pack(self):
-        if self.device.type != "cuda":
-            raise RuntimeError("SSCDModel: call .to(<cuda device>) first -- the network runs on the HIP kernels only")
+        self._need_device()
         sd = self._sd
         layers = {}
         for name, _, _, _, s, p, bn in _convs():
-            layers[name] = pack_conv(*fold_bn(sd, "backbone." + name, "backbone." + bn), s, p, self.device)
-        layers["fc"] = pack_conv(sd["backbone.fc.weight"].double().view(self.dims, FEATURES, 1, 1), sd["backbone.fc.bias"].double(),
-                                 1, 0, self.device)
+            layers[name] = mn.pack_conv(*mn.fold_bn(sd, "backbone." + name, "backbone." + bn, BN_EPS), s, p, self.device)
+        layers["fc"] = mn.pack_conv(sd["backbone.fc.weight"].double().view(self.dims, FEATURES, 1, 1), sd["backbone.fc.bias"].double(),
+                                    1, 0, self.device)
         self._packed = layers
 
     def max_elements(self, N, H, W):
@@ -177,9 +116,9 @@ class SSCDModel:
 
         def after(L, H, W):
             nonlocal big
-            Ho, Wo = conv_out(L, H, W)
+            Ho, Wo = mn.conv_out(L, H, W)
             M = N * Ho * Wo
-            big = max(big, M * L["cout"] * conv_splits(M, L["cout"], L["Kp"]))
+            big = max(big, M * L["cout"] * mn.conv_splits(M, L["cout"], L["Kp"]))
             return Ho, Wo
         H, W = after(P["conv1"], H, W)
         H, W = (H - 1) // 2 + 1, (W - 1) // 2 + 1
@@ -196,26 +135,18 @@ class SSCDModel:
     # -- forward ---------------------------------------------------------------------------------
     def _features(self, x):
         """One chunk: the normalised NCHW images -> the raw (not yet normalised) fc rows [n, dims]."""
-        N, _, H, W = x.shape
-        if H < 1 or W < 1:
-            raise ValueError(f"SSCDModel: empty images {tuple(x.shape)}")
-        big = self.max_elements(N, H, W)
-        if big >= MAX_ELEMENTS:
-            raise ValueError(f"SSCDModel: a chunk of {N} images of {H} x {W} holds a tensor of {big} elements, 2^31 or more: lower "
-                             f"batch_size (now {self.batch_size})")
+        N, H, W = self._chunk_shape(x)
         P = self._packed
-        h, H, W = run_conv(P["conv1"], x, N, H, W, relu=True, nchw_in=True)
-        h, H, W = max_pool(h, N, H, W, 64)
+        h = mn.max_pool3(mn.conv(P["conv1"], x, nchw_in=True), 2, 1)
         for i, n in enumerate(BLOCKS, 1):
             for j in range(n):
                 pre = f"layer{i}.{j}."
-                sc = run_conv(P[pre + "downsample.0"], h, N, H, W, relu=False)[0] if j == 0 else h
-                a, Ha, Wa = run_conv(P[pre + "conv1"], h, N, H, W, relu=True)
-                a, H, W = run_conv(P[pre + "conv2"], a, N, Ha, Wa, relu=True)
-                h, H, W = run_conv(P[pre + "conv3"], a, N, H, W, relu=True, res=sc)
+                sc = mn.conv(P[pre + "downsample.0"], h, relu=False) if j == 0 else h
+                a = mn.conv(P[pre + "conv2"], mn.conv(P[pre + "conv1"], h))
+                h = mn.conv(P[pre + "conv3"], a, res=sc)
         pooled = torch.empty(N, FEATURES, device=self.device, dtype=torch.float32)
-        lib.call("siss_sscd_gem", h, pooled, N, H * W, FEATURES, self.pool_param, GEM_EPS)
-        return run_conv(P["fc"], pooled.view(N, 1, 1, FEATURES), N, 1, 1, relu=False)[0].view(N, self.dims)
+        lib.call("siss_sscd_gem", h, pooled, N, h.shape[1] * h.shape[2], FEATURES, self.pool_param, GEM_EPS)
+        return mn.linear(P["fc"], pooled)
 
     def _finish(self, rows, ref):
         """(unit rows, scores against the unit row `ref` or None) of raw fc rows."""
@@ -229,42 +160,16 @@ class SSCDModel:
         lib.call("siss_sscd_normalize_score", rows, n, self.dims, NORM_EPS, ref, rows, score)
         return rows, score
 
-    def _preprocess(self, src, form, mean, std, want_u8):
-        n = src.shape[0]
-        h, w = (src.shape[1], src.shape[2]) if form == 0 else (src.shape[2], src.shape[3])
-        x = torch.empty(n, 3, h, w, device=self.device, dtype=torch.float32)
-        u8 = torch.empty(n, h, w, 3, device=self.device, dtype=torch.uint8) if want_u8 else None
-        lib.call("siss_sscd_preprocess", src, form, n, h, w, *mean, *std, u8, x)
-        return x, u8
-
-    @torch.no_grad()
     def _run(self, src, form, mean, std, ref):
         """Chunks of batch_size through (preprocess ->) trunk -> GeM -> fc -> normalise: (embeddings, scores or None, uint8 or None)."""
-        if self._packed is None:
-            self._pack()
-        n = src.shape[0]
-        if n == 0:
-            raise ValueError("SSCDModel: no images")
-        emb, scores, u8s = [], [], []
-        for s in range(0, n, self.batch_size):
-            part = src[s:s + self.batch_size].contiguous()
-            u8 = None
-            if form is not None:
-                part, u8 = self._preprocess(part, form, mean, std, want_u8=form != 0)
-            e, sc = self._finish(self._features(part), ref)
-            emb.append(e)
-            scores.append(sc)
-            u8s.append(u8)
-        cat = lambda xs: None if xs[0] is None else (xs[0] if len(xs) == 1 else torch.cat(xs))
-        return cat(emb), cat(scores), cat(u8s)
+        return self._chunks(src, form, mean, std, lambda rows: self._finish(rows, ref))
 
     def __call__(self, x, ref=None):
         """`[N, 3, H, W]` f32, already normalised (the reference's call form) -> `[N, dims]` unit rows; with `ref` (a unit row)
         -> (rows, their cosines with it [N])."""
         if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != 3:
             raise ValueError(f"SSCDModel expects [N, 3, H, W] images, got {tuple(getattr(x, 'shape', ()))}")
-        if self.device.type != "cuda":
-            raise RuntimeError("SSCDModel: call .to(<cuda device>) first -- the network runs on the HIP kernels only")
+        self._need_device()
         emb, scores, _ = self._run(x.to(self.device, torch.float32), None, None, None, ref)
         return emb if ref is None else (emb, scores)
 
@@ -273,24 +178,13 @@ class SSCDModel:
     def embed_u8(self, u8, mean=(0.0,), std=(1.0,), ref=None):
         """uint8 images `[n, H, W, 3]` -> unit rows of Normalize(mean, std)(ToTensor(image)), the preprocessing fused into one launch
         (bitwise torch's f32 chain); with `ref` -> (rows, scores)."""
-        u8 = torch.as_tensor(u8)
-        if u8.dtype != torch.uint8 or u8.dim() != 4 or u8.shape[3] != 3:
-            raise ValueError(f"uint8 images [n, H, W, 3] are needed, got {u8.dtype} {tuple(u8.shape)}")
-        if self.device.type != "cuda":
-            raise RuntimeError("SSCDModel: call .to(<cuda device>) first -- the network runs on the HIP kernels only")
-        emb, scores, _ = self._run(u8.to(self.device), 0, _three(mean, "mean"), _three(std, "std"), ref)
+        emb, scores, _ = self._run(self._check_u8(u8), 0, _three(mean, "mean"), _three(std, "std"), ref)
         return emb if ref is None else (emb, scores)
 
     def embed_decoded(self, img, mean=(0.0,), std=(1.0,), ref=None):
         """The VAE decoder's output `[n, 3, H, W]` (f32 or bf16, on the device) -> (unit rows, the uint8 images `[n, H, W, 3]`
         -- bitwise `kmeans.from_decoded`'s -- ) in one preprocessing launch per chunk; with `ref` -> (rows, uint8, scores)."""
-        if not (torch.is_tensor(img) and img.is_cuda and img.dim() == 4 and img.shape[1] == 3):
-            raise ValueError("the decoder's output [n, 3, H, W] on the device is needed")
-        if img.dtype not in (torch.float32, torch.bfloat16):
-            raise TypeError(f"decoder output of dtype {img.dtype}: float32 or bfloat16")
-        if img.device != self.device:
-            raise ValueError(f"decoder output on {img.device}, the network on {self.device}")
-        emb, scores, u8 = self._run(img, 2 if img.dtype == torch.bfloat16 else 1, _three(mean, "mean"), _three(std, "std"), ref)
+        emb, scores, u8 = self._run(img, self._check_decoded(img), _three(mean, "mean"), _three(std, "std"), ref)
         return (emb, u8) if ref is None else (emb, u8, scores)
 
 
@@ -324,8 +218,4 @@ class SSCDScore:
         return scores, u8
 
     def record(self, prompt, scores, step):
-        value = float(torch.as_tensor(scores).detach().cpu().double().mean())
-        rec = {"global_step": int(step), f"sscd_{prompt}": value if math.isfinite(value) else None}
-        with open(self.out_path, "a") as f:
-            f.write(json.dumps(rec) + "\n")
-        return rec
+        return mn.record_mean(self.out_path, f"sscd_{prompt}", scores, step)

@@ -13,6 +13,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 import clip_iqa_ref as R  # noqa: E402
+import metric_net_emul  # noqa: E402
+from siss_amd import metric_net  # noqa: E402
 
 SMALL_KW = dict(layers=(1, 1, 1, 1), width=64, output_dim=64, text_width=128, text_heads=2, text_layers=2, vocab_size=96, context_length=16)
 SOT, EOT = 94, 95                                   # the two last ids of the small vocabulary, as in CLIP's
@@ -135,19 +137,15 @@ def test_loader_on_torchscript_state_dict_safetensors_and_a_foreign_key_set(smal
 
 
 # ---------------------------------------------------------------- the wiring, launchers emulated in f64
-def _pack_conv64(w, b, stride, pad, device):
-    cout, cin, k, _ = w.shape
-    return dict(w=w.double(), b=b.double(), cin=cin, cout=cout, k=k, stride=stride, pad=pad, Kp=-(-k * k * cin // 32) * 32)
-
-
-def _run_conv64(L, x, N, H, W, relu, res=None, nchw_in=False):
-    import torch.nn.functional as F
-    assert tuple(x.shape) == ((N, L["cin"], H, W) if nchw_in else (N, H, W, L["cin"])) and (nchw_in or L["cin"] % 32 == 0)
-    o = F.conv2d((x if nchw_in else x.permute(0, 3, 1, 2)).double(), L["w"], L["b"], stride=L["stride"], padding=L["pad"]).permute(0, 2, 3, 1)
-    if res is not None:
-        assert res.shape == o.shape
-        o = o + res
-    return (F.relu(o) if relu else o).contiguous(), o.shape[1], o.shape[2]
+def _pack_conv64(w, b, stride, pad, device, _pack=metric_net.pack_conv):
+    """metric_net.pack_conv's layer with the weights and the bias kept in f64 (its layout restated: [Cout][Kp] in (kh, kw, ci) order)."""
+    L = _pack(w, b, stride, pad, "cpu")
+    cout, cin, kh, kw = w.shape
+    assert L["cin_p"] == cin and (cin <= 4 or cin % 32 == 0)
+    L["w"] = torch.zeros(cout, L["Kp"], dtype=torch.float64)
+    L["w"][:, :kh * kw * cin] = w.permute(0, 2, 3, 1).reshape(cout, -1).double()
+    L["b"] = b.double()
+    return L
 
 
 def _tokens(x, m, N, HW, E):
@@ -155,8 +153,11 @@ def _tokens(x, m, N, HW, E):
 
 
 def _emulated_call(name, *a):
-    """What the launchers of csrc/clip_iqa.hip compute, by torch's f64 operations on host tensors (the arguments as lib.call gets them)."""
+    """What the launchers compute, by torch's f64 operations on host tensors (the arguments as lib.call gets them): the shared
+    convolution in tests/metric_net_emul.py (in f64 here: the buffers are), csrc/clip_iqa.hip's own here."""
     import torch.nn.functional as F
+    if metric_net_emul.call(name, *a) == 0:
+        return 0
     if name == "siss_clipiqa_avgpool":
         x, y, N, H, W, C, k = a
         assert tuple(x.shape) == (N, H, W, C) and tuple(y.shape) == (N, H // k, W // k, C) and C % 4 == 0
@@ -202,8 +203,7 @@ def test_network_wiring_with_emulated_launchers(small, monkeypatch, h, w):
     from siss_amd import clip_iqa, lib
     monkeypatch.setattr(lib, "call", _emulated_call)
     monkeypatch.setattr(clip_iqa, "ACT", torch.float64)
-    monkeypatch.setattr(clip_iqa, "pack_conv", _pack_conv64)
-    monkeypatch.setattr(clip_iqa, "run_conv", _run_conv64)
+    monkeypatch.setattr(metric_net, "pack_conv", _pack_conv64)
     monkeypatch.setattr(clip_iqa, "pack_linear", lambda w_, b_, d: (w_.double(), b_.double()))
     u8 = torch.randint(0, 256, (3, h, w, 3), generator=torch.Generator().manual_seed(h), dtype=torch.uint8)
     x = R.normalise(u8).double()

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import fid_ref
+import metric_net_emul
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -48,23 +49,12 @@ def test_load_state_dict_is_strict():
 
 
 def _emulated_call(name, *a):
-    """What the launchers of csrc/inception.hip compute, by torch's f64 operations on host tensors (the arguments as lib.call gets them)."""
+    """What the launchers compute, by torch's f64 operations on host tensors (the arguments as lib.call gets them): the shared
+    convolution and max pool in tests/metric_net_emul.py, csrc/inception.hip's own here."""
     import torch.nn.functional as F
-    if name == "siss_inc_conv":
-        x, w, b, y, ws, ws_words, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, ph, pw, Kp, ldy, coff, splits = a
-        assert tuple(x.shape) == (N, H, W, Cin) and tuple(y.shape) == (N, Ho, Wo, ldy) and 0 <= coff and coff + Cout <= ldy
-        assert (Cin % 32 == 0 or Cin <= 4) and Kp % 32 == 0 and (splits == 1 or ws_words >= splits * N * Ho * Wo * Cout)
-        K = KH * KW * Cin
-        assert not w[:, K:].any()
-        wt = w[:, :K].reshape(Cout, KH, KW, Cin).permute(0, 3, 1, 2).double()
-        o = F.relu(F.conv2d(x.permute(0, 3, 1, 2).double(), wt, b.double(), stride=stride, padding=(ph, pw)))
-        assert tuple(o.shape[2:]) == (Ho, Wo)
-        y[..., coff:coff + Cout] = o.permute(0, 2, 3, 1).float()
-    elif name == "siss_inc_maxpool":
-        x, y, N, H, W, C, Ho, Wo, stride, pad, ldy, coff = a
-        assert tuple(y.shape) == (N, Ho, Wo, ldy) and coff + C <= ldy
-        y[..., coff:coff + C] = F.max_pool2d(x.permute(0, 3, 1, 2), 3, stride, pad).permute(0, 2, 3, 1)
-    elif name == "siss_inc_avgpool":
+    if metric_net_emul.call(name, *a) == 0:
+        return 0
+    if name == "siss_inc_avgpool":
         x, y = a[:2]
         y.copy_(F.avg_pool2d(x.permute(0, 3, 1, 2).double(), 3, 1, 1, count_include_pad=False).permute(0, 2, 3, 1).float())
     elif name == "siss_inc_global_avg":
@@ -80,7 +70,7 @@ def test_network_wiring_with_emulated_launchers(monkeypatch):
     writes at which column, the pools, Mixed_7c's max pool -- against the f64 restatement, no GPU: the launchers are replaced by
     torch's f64 operations (f32 between layers).  The bound is 8 x the f32 restatement's own deviation from f64 (3.13e-7 of max
     |f64| on these two images, the figure tests/test_hip_fid.py records); measured 8.9e-8."""
-    from siss_amd import fid, lib
+    from siss_amd import fid, lib, metric_net
     monkeypatch.setattr(lib, "call", _emulated_call)
     net = fid_ref.make(0)
     imgs = torch.randint(0, 256, (2, 3, 64, 64), generator=torch.Generator().manual_seed(1)).float() / 255
@@ -88,7 +78,7 @@ def test_network_wiring_with_emulated_launchers(monkeypatch):
     m = fid.InceptionV3FID()
     m.load_state_dict(net.state_dict())
     m.device = torch.device("cuda")                              # packing is refused on a CPU model; the tensors below stay on the host
-    monkeypatch.setattr(fid, "pack_conv", lambda w, b, s, p, d, _pack=fid.pack_conv: _pack(w, b, s, p, "cpu"))
+    monkeypatch.setattr(metric_net, "pack_conv", lambda w, b, s, p, d, _pack=metric_net.pack_conv: _pack(w, b, s, p, "cpu"))
     m._pack()
     m.device = torch.device("cpu")
     got = m.features(fid_ref.preprocess(imgs).permute(0, 2, 3, 1).contiguous()).double()

@@ -1,5 +1,5 @@
-"""The FID metric on the GPU (csrc/inception.hip behind siss_amd/fid.py): the convolution against F.conv2d in f64 at every corner the
-network reaches, the pools and the preprocessing against torch / the restatement, the whole Inception-v3 against the f64
+"""The FID metric on the GPU (csrc/inception.hip behind siss_amd/fid.py; the convolution and the max pool it shares with the other
+metric networks are held in tests/test_hip_metric_conv.py): the average pools and the preprocessing against torch / the restatement, the whole Inception-v3 against the f64
 restatement (tests/fid_ref.py) with negative controls and determinism, the f64 statistics, FIDEvaluator end to end, and the metric
 in the delete_celeb task loop."""
 import copy
@@ -15,7 +15,6 @@ import fid_ref as R
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CONV_BOUND = 1e-4       # max |d| <= CONV_BOUND * max |ref| (the bound tests/test_hip_classifier.py holds the same arithmetic to)
 # The f32 restatement against the f64 restatement on the CPU, the network test's two images: max |f32 - f64| / max |f64| = 3.13e-07.
 # The GPU sums in another order and splits K over ~100 layers: 8 x that; a wrong tap or pool lands at 0.3 of max |f64|.
 E32 = 3.13e-7
@@ -54,68 +53,6 @@ def _inception(net, dev):
     return m.to(dev).eval()
 
 
-# ---------------------------------------------------------------- convolution
-def _conv_case(dev, seed, N, H, W, cin, cout, k, stride, pad):
-    from siss_amd import fid
-    g = torch.Generator().manual_seed(seed)
-    kh, kw = fid._pair(k)
-    w = torch.randn(cout, cin, kh, kw, generator=g) / (cin * kh * kw) ** 0.5
-    b = torch.randn(cout, generator=g) * 0.3
-    x = torch.randn(N, cin, H, W, generator=g)
-    ref = F.relu(F.conv2d(x.double(), w.double(), b.double(), stride=stride, padding=fid._pair(pad)))
-    L = fid.pack_conv(w, b, stride, pad, dev)
-    return fid, L, x.permute(0, 2, 3, 1).contiguous().to(dev), ref
-
-
-CONV_CASES = {
-    # (N, H, W, Cin, Cout, k, stride, pad, whether the call splits K)
-    "stem 3->32 k3 s2 at 299": (1, 299, 299, 3, 32, 3, 2, 0, False),
-    "80->192 k3 at 9 (Cin off the K step)": (2, 9, 9, 80, 192, 3, 1, 0, True),
-    "64->48 k1 at 7 (Cout off the tile)": (2, 7, 7, 64, 48, 1, 1, 0, False),
-    "128->128 (1,7) p(0,3) at 17": (1, 17, 17, 128, 128, (1, 7), 1, (0, 3), True),
-    "128->128 (7,1) p(3,0) at 17": (1, 17, 17, 128, 128, (7, 1), 1, (3, 0), True),
-    "288->384 k3 s2 at 35 (odd map, no padding)": (1, 35, 35, 288, 384, 3, 2, 0, True),
-    "448->384 k3 p1 at 8 (split-K)": (2, 8, 8, 448, 384, 3, 1, 1, True),
-}
-
-
-@pytest.mark.parametrize("case", list(CONV_CASES))
-def test_convolution_against_conv2d_in_f64(dev, case):
-    N, H, W, cin, cout, k, stride, pad, split = CONV_CASES[case]
-    fid, L, x, ref = _conv_case(dev, len(case), N, H, W, cin, cout, k, stride, pad)
-    y = fid.conv_bn_relu(L, x)
-    got = y[..., :cout].permute(0, 3, 1, 2).cpu().double()
-    assert got.shape == ref.shape
-    scale, err = float(ref.abs().max()), float((got - ref).abs().max())
-    print(f"\n{case}: max|d| {err:.3e} = {err / scale:.2e} of max|ref| {scale:.3e}")
-    assert float((ref == 0).double().mean()) > 0.1 and scale > 0.5          # the ReLU cuts, and not everything
-    assert err <= CONV_BOUND * scale
-    if y.shape[3] != cout:                                       # a padded channel stride: zero beyond Cout
-        assert not y[..., cout:].any()
-    assert (fid.conv_splits(N * ref.shape[2] * ref.shape[3], cout, L["Kp"]) > 1) == split
-    assert torch.equal(y, fid.conv_bn_relu(L, x))                # the same call, the same bits
-
-
-@pytest.mark.parametrize("N, H, cin, k, pad", [(2, 7, 48, 5, 2), (2, 35, 192, 1, 0)])
-def test_convolution_into_a_channel_slice_leaves_the_neighbours_alone(dev, N, H, cin, k, pad):
-    """A branch written at column offset 64 of a 288-wide buffer (the 5 x 5 branch of Mixed_5d): once through split-K, once not."""
-    fid, L, x, ref = _conv_case(dev, H, N, H, H, cin, 64, k, 1, pad)
-    assert (fid.conv_splits(N * H * H, 64, L["Kp"]) > 1) == (H == 7)
-    buf = torch.randn(N, H, H, 288, generator=torch.Generator().manual_seed(9)).to(dev)
-    before = buf.clone()
-    assert fid.conv_bn_relu(L, x, buf, 64) is buf
-    assert torch.equal(buf[..., :64], before[..., :64]) and torch.equal(buf[..., 128:], before[..., 128:])
-    got = buf[..., 64:128].permute(0, 3, 1, 2).cpu().double()
-    assert float((got - ref).abs().max()) <= CONV_BOUND * float(ref.abs().max())
-    with pytest.raises(ValueError, match="column"):
-        fid.conv_bn_relu(L, x, buf, 256)                          # 256 + 64 > 288: refused on the host
-    from siss_amd import lib
-    with pytest.raises(RuntimeError, match="bad argument"):      # and by the launcher
-        lib.call("siss_inc_conv", x.contiguous() if cin % 32 == 0 else F.pad(x, (0, 16)), L["w"], L["b"], buf, None, 0, N, H, H,
-                 L["cin_p"], H, H, 64, k, k, 1, pad, pad, L["Kp"], 288, 256, 1)
-    assert torch.equal(buf[..., 128:], before[..., 128:])
-
-
 # ---------------------------------------------------------------- pools
 def _nhwc(x, dev):
     return x.permute(0, 2, 3, 1).contiguous().to(dev)
@@ -136,19 +73,6 @@ def test_pools_against_torch(dev):
     # the sum of their magnitudes (n <= 9), so the average is within 8 * 2^-24 * avg|x| of exact
     floor = 8 * 2.0 ** -24 * F.avg_pool2d(x.double().abs(), 3, 1, 1, count_include_pad=False)
     assert bool(((got - ref).abs() <= 1e-6 * ref.abs() + floor).all()), float(((got - ref).abs() / ref.abs()).max())
-    # max pools match bitwise; all-negative maps: a padded position, were it ever chosen, would win with its zero
-    for N, C, H, stride, pad in ((2, 64, 7, 2, 0), (1, 288, 35, 2, 0), (2, 2048, 8, 1, 1)):
-        x = -torch.rand(N, C, H, H, generator=g) - 0.5
-        x[:, ::3] = torch.randn(N, len(range(0, C, 3)), H, H, generator=g)
-        ref = F.max_pool2d(x, 3, stride, pad)
-        assert ref.shape[2] == {7: 3, 35: 17, 8: 8}[H]
-        assert torch.equal(_nchw(fid.max_pool3(_nhwc(x, dev), stride, pad)), ref)
-        # into a channel slice of a wider buffer: the neighbours stay
-        buf = torch.randn(N, ref.shape[2], ref.shape[3], C + 40, generator=g).to(dev)
-        before = buf.clone()
-        fid.max_pool3(_nhwc(x, dev), stride, pad, buf, 8)
-        assert torch.equal(_nchw(buf[..., 8:8 + C]), ref)
-        assert torch.equal(buf[..., :8], before[..., :8]) and torch.equal(buf[..., 8 + C:], before[..., 8 + C:])
     # the global average over 8 x 8
     x = torch.randn(3, 2048, 8, 8, generator=g)
     ref = x.double().mean(dim=(2, 3))

@@ -229,7 +229,7 @@ def _against_f64(net, model, dev, shape, seed):
 @pytest.mark.parametrize("shape", [(3, 3, 64, 64), (1, 3, 96, 64)], ids=["3x64x64", "1x96x64"])
 def test_network_against_the_f64_restatement(dev, net, model, shape):
     """N = 3 at 64 x 64 (the layer4 map is 2 x 2) and N = 1 at 96 x 64 (non-square, split-K on the late layers)."""
-    from siss_amd.classifier import conv_splits
+    from siss_amd.metric_net import conv_splits
     u8, x, ref, got, bound = _against_f64(net, model, dev, shape, seed=shape[2])
     n, _, h, w = shape
     assert (h // 32, w // 32) == ((2, 2) if h == 64 else (3, 2))

@@ -13,6 +13,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
+import metric_net_emul  # noqa: E402
 import sscd_ref as R  # noqa: E402
 
 
@@ -123,26 +124,11 @@ def test_loader_on_torchscript_state_dict_alias_and_safetensors(net, tmp_path):
 
 
 def _emulated_call(name, *a):
-    """What the launchers compute, by torch's f64 operations on host tensors (the arguments as lib.call gets them)."""
-    import torch.nn.functional as F
-    if name == "siss_cls_conv":
-        x, nchw, w, b, res, y, ws, ws_words, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, Kp, relu, splits = a
-        assert tuple(x.shape) == ((N, Cin, H, W) if nchw else (N, H, W, Cin)) and tuple(y.shape) == (N, Ho, Wo, Cout)
-        assert (Cin <= 4 if nchw else Cin % 32 == 0) and Kp % 32 == 0 and 0 <= Kp - KH * KW * Cin < 32
-        assert 1 <= splits <= Kp // 32 and (splits == 1 or ws_words >= splits * N * Ho * Wo * Cout)
-        K = KH * KW * Cin
-        assert not w[:, K:].any()
-        wt = w[:, :K].reshape(Cout, KH, KW, Cin).permute(0, 3, 1, 2).double()
-        o = F.conv2d((x if nchw else x.permute(0, 3, 1, 2)).double(), wt, b.double(), stride=stride, padding=pad).permute(0, 2, 3, 1)
-        assert tuple(o.shape) == (N, Ho, Wo, Cout)
-        if res is not None:
-            assert res.shape == y.shape
-            o = o + res.double()
-        y.copy_((F.relu(o) if relu else o).float())
-    elif name == "siss_cls_maxpool":
-        x, y, N, H, W, C, Ho, Wo = a
-        y.copy_(F.max_pool2d(x.permute(0, 3, 1, 2), 3, 2, 1).permute(0, 2, 3, 1))
-    elif name == "siss_sscd_gem":
+    """What the launchers compute, by torch's f64 operations on host tensors (the arguments as lib.call gets them): the shared
+    convolution and max pool in tests/metric_net_emul.py, csrc/sscd.hip's own here."""
+    if metric_net_emul.call(name, *a) == 0:
+        return 0
+    if name == "siss_sscd_gem":
         x, y, N, HW, C, p, eps = a
         assert x.numel() == N * HW * C and tuple(y.shape) == (N, C)
         y.copy_(x.reshape(N, HW, C).clamp(min=eps).double().pow(p).mean(1).pow(1 / p).float())
@@ -161,7 +147,7 @@ def test_network_wiring_with_emulated_launchers(net, monkeypatch):
     """siss_amd/sscd.py's side of the network -- BN folding, packing, which layer reads what, where the stride and the shortcut sit,
     GeM, fc as a 1 x 1 convolution, the normalisation and the score -- against the f64 restatement, no GPU: the launchers are replaced
     by torch's f64 operations (f32 between layers).  Bound: 8 x the f32 restatement's own deviation from f64, measured here."""
-    from siss_amd import lib, sscd
+    from siss_amd import lib, metric_net, sscd
     monkeypatch.setattr(lib, "call", _emulated_call)
     u8 = torch.randint(0, 256, (2, 40, 56, 3), generator=torch.Generator().manual_seed(1), dtype=torch.uint8)
     x = R.normalise(u8, R.IMAGENET_MEAN, R.IMAGENET_STD)
@@ -170,7 +156,7 @@ def test_network_wiring_with_emulated_launchers(net, monkeypatch):
     m = sscd.SSCDModel(batch_size=1)                              # two chunks
     m.load_state_dict(net.state_dict())
     m.device = torch.device("cuda")                               # packing is refused on a CPU model; the tensors below stay on the host
-    monkeypatch.setattr(sscd, "pack_conv", lambda w, b, s, p, d, _pack=sscd.pack_conv: _pack(w, b, s, p, "cpu"))
+    monkeypatch.setattr(metric_net, "pack_conv", lambda w, b, s, p, d, _pack=metric_net.pack_conv: _pack(w, b, s, p, "cpu"))
     m._pack()
     m.device = torch.device("cpu")
     unit = torch.nn.functional.normalize(torch.randn(512, generator=torch.Generator().manual_seed(2)), dim=0)

@@ -3,7 +3,7 @@
 
     python tools/bench_classifier.py [--reps 20] [--no-eval]
 
-  * hip_ms[N] / tflops[N] / peak_frac[N]: the MNIST ResNet-18 logits (siss_amd.classifier, f32, csrc/classifier.hip) at
+  * hip_ms[N] / tflops[N] / peak_frac[N]: the MNIST ResNet-18 logits (siss_amd.classifier, f32, csrc/metric_conv.hip) at
     N = 128, 1024, 4096 images of 28 x 28, against the 157.3 TF f32 MFMA peak; algorithmic flops = 2 x MACs of the convolutions
     and fc;
   * torch_ms[N]: the same weights in tests/classifier_ref.py's module on torch-ROCm (f32, eval);

@@ -4,7 +4,7 @@
     python tools/bench_clip_iqa.py [--reps 10] [--sizes 8,64] [--size 512]
 
   * hip_ms[N] / images_per_s[N] / tflops[N] / peak_frac[N]: preprocessing from uint8 + the CLIP RN50 image tower + the score
-    (siss_amd.clip_iqa, f32: csrc/classifier.hip's convolution, csrc/clip_iqa.hip around it) of N images of --size x --size, in
+    (siss_amd.clip_iqa, f32: csrc/metric_conv.hip's convolution, csrc/clip_iqa.hip around it) of N images of --size x --size, in
     chunks of 16, against the 157.3 TF f32 MFMA peak; algorithmic flops = 2 x MACs of the convolutions and the FOLDED attention pool;
   * trunk_ms[N] / attnpool_ms[N]: the same chunks split into the trunk (preprocessing .. layer4) and the attention pool (mean token
     .. c_proj), each timed on its own; attnpool_unfolded_macs is what projecting every token through k_proj and v_proj would cost.

@@ -4,7 +4,7 @@
     python tools/bench_sscd.py [--reps 10] [--sizes 8,64] [--size 512] [--no-torch]
 
   * hip_ms[N] / images_per_s[N] / tflops[N] / peak_frac[N]: preprocessing from uint8 + the SSCD ResNet-50 embeddings
-    (siss_amd.sscd, f32: csrc/classifier.hip's convolution, csrc/sscd.hip around it) of N images of --size x --size, in chunks of
+    (siss_amd.sscd, f32: csrc/metric_conv.hip's convolution, csrc/sscd.hip around it) of N images of --size x --size, in chunks of
     16, against the 157.3 TF f32 MFMA peak; algorithmic flops = 2 x MACs of the 53 convolutions and fc (the trunk);
   * torch_ms[N] / torch_tflops[N]: the same weights in tests/sscd_ref.py's module on torch-ROCm (f32, eval), its normalisation
     included, in the same chunks.
