@@ -8,6 +8,10 @@ guidance and the DDIM update and leaves the step's per-block partial sums of ||e
 in a [steps, 2, n, blocks] slab.  The host reads that slab ONCE, after the last step (the reference pays 2n ``.item()``
 syncs per step for the same norms), and sums each sample's partials in f64.  Then the VAE decoder (siss_amd/vae.py) and
 diffusers' postprocess.
+
+The img2img half of that class (``get_timesteps``, ``prepare_latents_img2img``, :241-323) enters the same loop part of the way
+down: ``denoise_injection`` noises an image's latents to the first remaining timestep -- ONE launch from the VAE encoder's posterior
+moments (csrc/injection.hip ``siss_latent_inject``) -- and denoises them back under the prompt.
 """
 import contextlib
 import os
@@ -53,13 +57,33 @@ def cfg_ddim_step(eps, x, out, coeffs, guidance, clip=0.0, norms=None):
     return out
 
 
+def latent_inject(moments, eps_z, eps_t, scaling, a, b, out=None, nblk=None):
+    """x[i] = a * ((mean[j] + exp(0.5 * clamp(logvar[j], -30, 20)) * eps_z[j]) * scaling) + b * eps_t[i], j = i mod m: the n
+    starting latents of an img2img DDIM loop from the posterior moments [m, 2C, h, w] (f32 or bf16; mean first) of m images,
+    eps_z [m, C, h, w] and eps_t [n, C, h, w] (f32).  a, b: sqrt(alphas_cumprod[t]), sqrt(1 - alphas_cumprod[t]).  nblk: blocks per
+    sample (default ddim_blocks: the same capped grid as the DDIM step)."""
+    m, n = moments.shape[0], eps_t.shape[0]
+    chw = eps_t[0].numel()
+    if moments.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"moments of dtype {moments.dtype}: f32 or bf16 are taken")
+    assert eps_z.dtype == eps_t.dtype == torch.float32 and moments.is_contiguous() and eps_z.is_contiguous() and eps_t.is_contiguous()
+    assert moments[0].numel() == 2 * chw and eps_z.shape[0] == m and eps_z[0].numel() == chw
+    out = torch.empty_like(eps_t) if out is None else out
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == eps_t.shape
+    lib.call("siss_latent_inject", moments, int(moments.dtype == torch.bfloat16), eps_z, eps_t, out, m, n, chw, float(scaling),
+             float(a), float(b), ddim_blocks(n, chw) if nblk is None else int(nblk))
+    return out
+
+
 class SDSampler:
     """Text-to-image pipeline over the HIP ``UNet2DConditionModel``, ``VAEDecoder`` and ``CLIPTextEncoder``; the call surface of
     the reference's LocalStableDiffusionPipeline.  ``unconditional_ids``: token ids of the negative (empty) prompt; or pass
-    ``negative_prompt_embeds`` to every call (then no text encoder is needed)."""
+    ``negative_prompt_embeds`` to every call (then no text encoder is needed).  ``vae_encoder``: the VAEEncoder that
+    ``denoise_injection`` / ``prepare_latents_img2img`` turn an image into latents with (not needed for 4-channel latents)."""
 
-    def __init__(self, unet, vae=None, text_encoder=None, scheduler=None, unconditional_ids=None, use_graph=True):
-        self.unet, self.vae, self.text_encoder = unet, vae, text_encoder
+    def __init__(self, unet, vae=None, text_encoder=None, scheduler=None, unconditional_ids=None, use_graph=True,
+                 vae_encoder=None):
+        self.unet, self.vae, self.text_encoder, self.vae_encoder = unet, vae, text_encoder, vae_encoder
         self.scheduler = scheduler or DDIMScheduler.from_pretrained(None)
         self.unconditional_ids = torch.tensor([SD_V1_UNCOND_IDS]) if unconditional_ids is None else unconditional_ids
         self.use_graph = use_graph
@@ -82,14 +106,7 @@ class SDSampler:
         e = self.text_encoder(self.unconditional_ids.reshape(1, -1))[0].float()
         return e.expand(n_prompts, *e.shape[1:])
 
-    @torch.no_grad()
-    def __call__(self, prompt_embeds, negative_prompt_embeds=None, num_inference_steps=50, guidance_scale=7.5,
-                 num_images_per_prompt=1, generator=None, latents=None, output_type="pil", track_noise_norm=True,
-                 height=None, width=None, eta=0.0, lp=2):
-        """prompt_embeds [B, L, X].  Returns (images, {"uncond_noise_norm", "text_noise_norm"}): images a list of PIL images
-        ("pil"), a uint8 [n, H, W, 3] array ("np"), the final latents ("latent") or the VAE decoder's raw output [n, 3, H, W] on the
-        device ("decoded": what KMeansClassifier.from_decoded turns into the uint8 images and their labels without leaving it); the
-        norms per image and denoising step, in step order (empty without guidance)."""
+    def _check_call(self, output_type, eta, lp):
         if eta != 0.0:
             raise NotImplementedError(f"eta={eta}: only the deterministic DDIM step (eta = 0) is implemented")
         if lp != 2:
@@ -98,26 +115,24 @@ class SDSampler:
             raise ValueError(f"output_type={output_type!r}: one of 'pil', 'np', 'latent', 'decoded'")
         if output_type != "latent" and self.vae is None:
             raise ValueError(f"output_type={output_type!r} needs a VAE decoder")
-        unet = self.unet
-        dev = unet.device
-        cfg = guidance_scale > 1.0                       # do_classifier_free_guidance (local_sd_pipeline.py:109)
+
+    def _embeddings(self, prompt_embeds, negative_prompt_embeds, num_images_per_prompt, cfg):
+        """(the UNet's encoder_hidden_states -- uncond rows first under guidance, as diffusers orders them --, images n)."""
+        dev = self.unet.device
         text = prompt_embeds.to(dev).float().repeat_interleave(num_images_per_prompt, dim=0)
-        n = text.shape[0]
-        if cfg:
-            neg = self._negative(prompt_embeds.shape[0]) if negative_prompt_embeds is None else negative_prompt_embeds
-            neg = neg.to(dev).float().repeat_interleave(num_images_per_prompt, dim=0)
-            emb = torch.cat([neg, text]).contiguous()    # uncond rows first, as diffusers orders them
-        else:
-            emb = text.contiguous()
-        C, s = unet.config.in_channels, unet.config.sample_size
-        h = (height or s * self.vae_scale_factor) // self.vae_scale_factor
-        w = (width or s * self.vae_scale_factor) // self.vae_scale_factor
-        if latents is None:
-            gdev = generator.device if generator is not None else dev
-            latents = torch.randn((n, C, h, w), generator=generator, device=gdev)
-        x = latents.to(dev).float().contiguous().clone()       # (DDIM: init_noise_sigma = 1)
-        sch = self.scheduler
-        steps = sch.set_timesteps(num_inference_steps)
+        if not cfg:
+            return text.contiguous(), text.shape[0]
+        neg = self._negative(prompt_embeds.shape[0]) if negative_prompt_embeds is None else negative_prompt_embeds
+        neg = neg.to(dev).float().repeat_interleave(num_images_per_prompt, dim=0)
+        return torch.cat([neg, text]).contiguous(), text.shape[0]
+
+    def _denoise(self, x, steps, emb, guidance_scale, output_type, track_noise_norm):
+        """The per-step loop over the timesteps `steps` (a suffix of the scheduler's current set_timesteps) from the start latents
+        x [n, C, h, w] (f32, contiguous, overwritten), then the noise norms and the output of `output_type`."""
+        unet, sch = self.unet, self.scheduler
+        dev = unet.device
+        cfg = guidance_scale > 1.0
+        n = x.shape[0]
         clip = sch.clip_sample_range if sch.clip_sample else 0.0
         chw = x[0].numel()
         slab = torch.zeros(len(steps), 2, n, ddim_blocks(n, chw), dtype=torch.float32, device=dev) if cfg else None
@@ -149,6 +164,96 @@ class SDSampler:
             return u8, stats
         from PIL import Image
         return [Image.fromarray(a) for a in u8], stats
+
+    @torch.no_grad()
+    def __call__(self, prompt_embeds, negative_prompt_embeds=None, num_inference_steps=50, guidance_scale=7.5,
+                 num_images_per_prompt=1, generator=None, latents=None, output_type="pil", track_noise_norm=True,
+                 height=None, width=None, eta=0.0, lp=2):
+        """prompt_embeds [B, L, X].  Returns (images, {"uncond_noise_norm", "text_noise_norm"}): images a list of PIL images
+        ("pil"), a uint8 [n, H, W, 3] array ("np"), the final latents ("latent") or the VAE decoder's raw output [n, 3, H, W] on the
+        device ("decoded": what KMeansClassifier.from_decoded turns into the uint8 images and their labels without leaving it); the
+        norms per image and denoising step, in step order (empty without guidance)."""
+        self._check_call(output_type, eta, lp)
+        unet = self.unet
+        dev = unet.device
+        cfg = guidance_scale > 1.0                       # do_classifier_free_guidance (local_sd_pipeline.py:109)
+        emb, n = self._embeddings(prompt_embeds, negative_prompt_embeds, num_images_per_prompt, cfg)
+        C, s = unet.config.in_channels, unet.config.sample_size
+        h = (height or s * self.vae_scale_factor) // self.vae_scale_factor
+        w = (width or s * self.vae_scale_factor) // self.vae_scale_factor
+        if latents is None:
+            gdev = generator.device if generator is not None else dev
+            latents = torch.randn((n, C, h, w), generator=generator, device=gdev)
+        x = latents.to(dev).float().contiguous().clone()       # (DDIM: init_noise_sigma = 1)
+        steps = self.scheduler.set_timesteps(num_inference_steps)
+        return self._denoise(x, steps, emb, guidance_scale, output_type, track_noise_norm)
+
+    def get_timesteps(self, num_inference_steps, strength, device=None):
+        """The reference's get_timesteps (data/src/local_sd_pipeline.py:241-248): (the last init_timestep = min(int(steps *
+        strength), steps) timesteps of set_timesteps(steps), their count).  The scheduler's order is 1; `device` is accepted for the
+        reference's signature (the timesteps are host integers).  No step left (strength * steps < 1) raises."""
+        n = int(num_inference_steps)
+        init_timestep = min(int(n * strength), n)
+        t_start = max(n - init_timestep, 0)
+        timesteps = self.scheduler.set_timesteps(n)[t_start:]
+        if not timesteps:
+            raise ValueError(f"strength={strength!r} of num_inference_steps={n} leaves no denoising step (int({n} * {strength!r}) "
+                             "< 1)")
+        return timesteps, n - t_start
+
+    @torch.no_grad()
+    def prepare_latents_img2img(self, image, timestep, batch_size, num_images_per_prompt, dtype=None, device=None, generator=None):
+        """The reference's prepare_latents_img2img (:250-323): `image` [m, 4, h, w] is taken as latents; any other image [m, 3, H, W]
+        in [-1, 1] goes through the VAE encoder and its posterior is sampled (normals drawn first) and scaled.  The m latents are
+        tiled to batch_size * num_images_per_prompt (a multiple of m, else ValueError) as torch.cat([latents] * k) orders them and
+        noised to `timestep` with normals drawn second -- sample, scale, tile and add_noise in ONE launch (siss_latent_inject; latents
+        go in as moments of zero variance: mean + std * 0 = mean exactly).  Returns [n, C, h, w] f32."""
+        if isinstance(generator, (list, tuple)):
+            raise NotImplementedError("a list of generators (one per image) is not implemented: pass one generator")
+        if dtype not in (None, torch.float32):
+            raise NotImplementedError(f"dtype={dtype}: the starting latents of the loop are f32")
+        dev = torch.device(device) if device is not None else self.unet.device
+        gdev = generator.device if generator is not None else dev
+        image = image.to(dev)
+        if image.dim() != 4:
+            raise ValueError(f"image of shape {tuple(image.shape)}: [m, C, H, W] is needed")
+        want = batch_size * num_images_per_prompt
+        if image.shape[1] == 4:
+            z = image.float()
+            moments = torch.cat([z, torch.zeros_like(z)], dim=1).contiguous()
+            eps_z, scaling = torch.zeros_like(z).contiguous(), 1.0
+        else:
+            if self.vae_encoder is None:
+                raise ValueError(f"an image with {image.shape[1]} channels has to be encoded: SDSampler(vae_encoder=...) is needed")
+            moments = self.vae_encoder.raw_moments(image)
+            m, c2, h, w = moments.shape
+            eps_z = torch.randn((m, c2 // 2, h, w), generator=generator, device=gdev).to(dev)   # latent_dist.sample(generator)
+            scaling = self.vae_encoder.cfg.scaling_factor
+        m = moments.shape[0]
+        if want > m and want % m != 0:
+            raise ValueError(f"Cannot duplicate `image` of batch size {m} to {want} text prompts.")
+        n = want if want > m else m
+        eps_t = torch.randn((n, *eps_z.shape[1:]), generator=generator, device=gdev).to(dev)
+        ac = self.scheduler.alphas_cumprod[int(timestep)]                  # add_noise's f32 coefficients
+        return latent_inject(moments, eps_z, eps_t, scaling, float(ac ** 0.5), float((1 - ac) ** 0.5))
+
+    @torch.no_grad()
+    def denoise_injection(self, image, prompt_embeds, strength=0.5, negative_prompt_embeds=None, num_inference_steps=50,
+                          guidance_scale=7.5, num_images_per_prompt=1, generator=None, output_type="pil", track_noise_norm=True,
+                          eta=0.0, lp=2):
+        """Inject-then-denoise: `image` (latents [m, 4, h, w], or images [m, 3, H, W] in [-1, 1] through the VAE encoder) noised to
+        the first of the last int(num_inference_steps * strength) timesteps, then denoised under the prompt over those timesteps --
+        the reference pipeline's img2img entry (get_timesteps, prepare_latents_img2img) into the loop of __call__.  Returns what
+        __call__ returns for `output_type`; the noise norms have one entry per executed step."""
+        self._check_call(output_type, eta, lp)
+        cfg = guidance_scale > 1.0
+        emb, _ = self._embeddings(prompt_embeds, negative_prompt_embeds, num_images_per_prompt, cfg)
+        steps, _ = self.get_timesteps(num_inference_steps, strength)
+        x = self.prepare_latents_img2img(image, steps[0], prompt_embeds.shape[0], num_images_per_prompt, generator=generator)
+        if x.shape[0] != emb.shape[0] // (2 if cfg else 1):
+            raise ValueError(f"{x.shape[0]} starting latents for {emb.shape[0] // (2 if cfg else 1)} prompt rows: pass at most as "
+                             "many images as prompts x num_images_per_prompt")
+        return self._denoise(x, steps, emb, guidance_scale, output_type, track_noise_norm)
 
     def aug_prompt(self, prompt=None, height=None, width=None, num_inference_steps=50, guidance_scale=7.5, negative_prompt=None,
                    num_images_per_prompt=1, eta=0.0, generator=None, latents=None, prompt_embeds=None, negative_prompt_embeds=None,

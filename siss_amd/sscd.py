@@ -219,3 +219,21 @@ class SSCDScore:
 
     def record(self, prompt, scores, step):
         return mn.record_mean(self.out_path, f"sscd_{prompt}", scores, step)
+
+
+class InjectionScore(SSCDScore):
+    """The inject-then-denoise check of the pixel-space tasks as numbers (the paper's SSCD similarity for CelebA-HQ; the reference
+    only logs the image grid, delete_celeb.py:404-436,:500-503, and scores offline): the cosine of the forget image's embedding with
+    each denoised injection's, both taken from uint8 bytes -- the PNG grid's own -- as an offline scorer would read them.
+    `record(scores, step, timestep)` appends {global_step, timestep, sscd_mean, sscd_max, sscd} to `out_path`, the mean in f64 on
+    the host."""
+
+    def record(self, scores, step, timestep):
+        import json
+        s = torch.as_tensor(scores).detach().cpu().double().reshape(-1)
+        finite = lambda v: v if math.isfinite(v) else None
+        rec = {"global_step": int(step), "timestep": int(timestep), "sscd_mean": finite(float(s.mean())),
+               "sscd_max": finite(float(s.max())), "sscd": [finite(v) for v in s.tolist()]}
+        with open(self.out_path, "a") as f:
+            f.write(json.dumps(rec) + "\n")
+        return rec

@@ -40,6 +40,37 @@ def _dist():
     return world, rank, local, pg
 
 
+def _sscd_normalize(node, what):
+    """(mean, std) of `<what>.data_transforms`: null, or a Compose of exactly one Normalize with one or three means and non-zero
+    stds (the ToTensor in front of it is part of the fused preprocessing)."""
+    from .data import Compose, Normalize
+    mean, std = [0.0], [1.0]
+    if node is not None:
+        tf = hydra_lite.instantiate(node) if isinstance(node, dict) and "_target_" in node else node
+        ts = tf.transforms if isinstance(tf, Compose) else None
+        if ts is None or len(ts) != 1 or not isinstance(ts[0], Normalize):
+            raise ValueError(f"{what}.data_transforms={node!r}: null or a Compose of exactly one Normalize is needed "
+                             "(ToTensor and the normalisation run fused on the device)")
+        mean, std = list(ts[0].mean), list(ts[0].std)
+        if len(mean) not in (1, 3) or len(std) not in (1, 3) or not all(float(v) != 0 for v in std):
+            raise ValueError(f"{what}.data_transforms: Normalize(mean={mean}, std={std}) needs one or three means and "
+                             "non-zero stds")
+    return mean, std
+
+
+def _load_sscd(path, allow_random_init, what):
+    """The SSCDModel of `<what>.model_path`: the file when it is on disk, else (allow_random_init) a random-init network, loudly."""
+    from .sscd import SSCDModel
+    if os.path.isfile(str(path)):
+        return SSCDModel.load(str(path))
+    if not allow_random_init:
+        raise FileNotFoundError(f"{what}.model_path {path!r} is not a file on disk (pass allow_random_init=true for "
+                                "random-init weights of the same architecture)")
+    print(f"[siss_amd] allow_random_init: SSCD checkpoint {path!r} not on disk, RANDOM-INIT ResNet-50: the SSCD figures are "
+          "NOT comparable with published ones")
+    return SSCDModel()
+
+
 class _DeleteBase(Task):
     timestep_low = 999          # delete_celeb.py:593 hard-codes randint(999, 1000)
     inf_guard = False
@@ -157,7 +188,10 @@ class _DeleteBase(Task):
         samples from the current model (DDPMPipeline, `pipeline.num_inference_steps`) and the forget image noised to
         `metrics.denoising_injections.timestep` and denoised back, written as PNG grids instead of wandb images.
         Runs every `eval_every` optimizer steps -- OPT-IN (null by default): the reference's `sampling_steps: 1`
-        spends ~300 UNet forwards per optimizer step on it."""
+        spends ~300 UNet forwards per optimizer step on it.  With `metrics.denoising_injections.sscd` (check_injection_score) the
+        denoised injections are quantised on the device by the grid's own rule, those bytes go through the SSCD network against the
+        forget image's embedding, and {global_step, timestep, sscd_mean, sscd_max, sscd} is appended to injection_rank0.jsonl; the
+        grid is then made of the same bytes."""
         import numpy as np
         from PIL import Image
         from .sampler import Evaluator
@@ -173,10 +207,17 @@ class _DeleteBase(Task):
         clean = forget_image.to(device).float()
         noise = torch.randn((n, *clean.shape), generator=g, device=device)
         noisy = sched.add_noise(clean.expand(n, *clean.shape), noise, torch.full((n,), t_inj, device=device))
-        den = ev.denoise_images(noisy, t_inj).cpu().numpy()
+        den = ev.denoise_images(noisy, t_inj)                                                # [n, H, W, C] in [0, 1], on the device
+        if self.injection is not None:
+            if den.shape[-1] != 3:
+                raise ValueError(f"metrics.denoising_injections.sscd: the SSCD network takes 3-channel images, got {den.shape[-1]}")
+            den = (den.clamp(0, 1) * 255).to(torch.uint8).contiguous()                       # grid()'s rule: truncation
+            self.injection.record(self.injection.score_u8(den), step, t_inj)                 # only the n scores leave the device
+        den = den.cpu().numpy()
 
         def grid(a):
-            a = (np.clip(a, 0, 1) * 255).astype(np.uint8)
+            if a.dtype != np.uint8:
+                a = (np.clip(a, 0, 1) * 255).astype(np.uint8)
             row = np.concatenate(list(a), axis=1)
             return Image.fromarray(row[..., 0] if row.shape[-1] == 1 else row)
         grid(imgs).save(os.path.join(cfg.output_dir, f"samples_step{step}.png"))
@@ -212,8 +253,54 @@ class _DeleteBase(Task):
     def check_metrics(self):
         """Refuse, before the first step, a metrics block that cannot run (a host-side check: no GPU needed)."""
         self.check_membership()
+        self.injection = self.check_injection_score()
 
     membership_supported = True
+    injection = None            # the injection check's scorer / settings (check_injection_score), None when not configured
+
+    def _image_channels(self):
+        """The UNet's in_channels as far as the host can tell before it is loaded: cfg.unet.in_channels, else the checkpoint's
+        config.json when it is on disk, else the task's default architecture."""
+        cfg = self.cfg
+        ch = (cfg.get("unet") or {}).get("in_channels")
+        if ch is not None:
+            return ch
+        path = str(cfg.get("checkpoint_path") or "")
+        sub = (cfg.get("subfolders") or {}).get("unet") or ""
+        for fn in (os.path.join(path, sub, "config.json"), os.path.join(path, "unet", "config.json")):
+            if os.path.isfile(fn):
+                with open(fn) as f:
+                    return json.load(f).get("in_channels", 3)
+        return self.default_unet().in_channels
+
+    def check_injection_score(self):
+        """metrics.denoising_injections.sscd: {model_path, data_transforms} (null / absent: nothing): the SSCD similarity of the
+        denoised injections with the forget image.  Needs model_path on disk (or allow_random_init=true, there or at the top level:
+        a random-init network, loudly), data_transforms null or a Compose of exactly one Normalize, a 3-channel UNet, and the forget
+        image at metrics.denoising_injections.img_path (the reference's key) on disk -- refused here, before the first step.
+        Returns the sscd.InjectionScore, or None."""
+        cfg = self.cfg
+        inj = (cfg.get("metrics") or {}).get("denoising_injections")
+        sc = inj.get("sscd") if isinstance(inj, dict) else None
+        if not sc:
+            return None
+        what = "metrics.denoising_injections.sscd"
+        path = sc.get("model_path") if isinstance(sc, dict) else None
+        if not path:
+            raise ValueError(f"{what}={sc!r}: model_path is needed (sscd_disc_mixup.torchscript.pt, or a state dict of it)")
+        mean, std = _sscd_normalize(sc.get("data_transforms"), what)
+        ch = self._image_channels()
+        if ch != 3:
+            raise ValueError(f"{what}: the SSCD network takes 3-channel images, the UNet has in_channels={ch!r}")
+        img = inj.get("img_path")
+        if not img or not os.path.isfile(str(img)):
+            raise FileNotFoundError(f"{what}: metrics.denoising_injections.img_path {img!r} (the forget image the injections are "
+                                    "compared with) is not a file on disk")
+        model = _load_sscd(path, sc.get("allow_random_init") or cfg.get("allow_random_init"), what)
+        if not cfg.get("eval_every"):
+            print(f"[siss_amd] {what} is set but eval_every is not: the score is taken at evaluations only")
+        from .sscd import InjectionScore
+        return InjectionScore(model, str(img), os.path.join(str(cfg.output_dir), "injection_rank0.jsonl"), mean, std)
 
     def check_membership(self, n_all=None, n_deletion=None):
         """metrics.membership_loss needs class_cfg, a positive step_frequency (unless plot_params stops the run before the first
@@ -737,23 +824,11 @@ class DeleteSD(_DeleteBase):
         sc = (cfg.get("metrics") or {}).get("sscd")
         if not sc:
             return None
-        from .data import Compose, Normalize
-        from .sscd import SSCDModel, SSCDScore
+        from .sscd import SSCDScore
         path = sc.get("model_path") if isinstance(sc, dict) else None
         if not path:
             raise ValueError(f"metrics.sscd={sc!r}: model_path is needed (sscd_disc_mixup.torchscript.pt, or a state dict of it)")
-        node = sc.get("data_transforms")
-        mean, std = [0.0], [1.0]
-        if node is not None:
-            tf = hydra_lite.instantiate(node) if isinstance(node, dict) and "_target_" in node else node
-            ts = tf.transforms if isinstance(tf, Compose) else None
-            if ts is None or len(ts) != 1 or not isinstance(ts[0], Normalize):
-                raise ValueError(f"metrics.sscd.data_transforms={node!r}: null or a Compose of exactly one Normalize is needed "
-                                 "(ToTensor and the normalisation run fused on the device)")
-            mean, std = list(ts[0].mean), list(ts[0].std)
-            if len(mean) not in (1, 3) or len(std) not in (1, 3) or not all(float(v) != 0 for v in std):
-                raise ValueError(f"metrics.sscd.data_transforms: Normalize(mean={mean}, std={std}) needs one or three means and "
-                                 "non-zero stds")
+        mean, std = _sscd_normalize(sc.get("data_transforms"), "metrics.sscd")
         ckpt = str(cfg.get("pretrained_model_name_or_path") or "")
         if not os.path.isdir(os.path.join(ckpt, "vae")):
             raise FileNotFoundError(f"metrics.sscd embeds decoded validation images: no vae/ under {ckpt!r}")
@@ -761,18 +836,50 @@ class DeleteSD(_DeleteBase):
         if not mem or not os.path.isfile(str(mem)):
             raise FileNotFoundError(f"metrics.sscd: data_files.mem_img_path {mem!r} (the memorized image; set from "
                                     "clustering_info_path when deletion.frac_deletion is null) is not a file on disk")
-        if os.path.isfile(str(path)):
-            model = SSCDModel.load(str(path))
-        elif not (sc.get("allow_random_init") or cfg.get("allow_random_init")):
-            raise FileNotFoundError(f"metrics.sscd.model_path {path!r} is not a file on disk (pass allow_random_init=true for "
-                                    "random-init weights of the same architecture)")
-        else:
-            model = SSCDModel()
-            print(f"[siss_amd] allow_random_init: SSCD checkpoint {path!r} not on disk, RANDOM-INIT ResNet-50: the SSCD figures are "
-                  "NOT comparable with published ones")
+        model = _load_sscd(path, sc.get("allow_random_init") or cfg.get("allow_random_init"), "metrics.sscd")
         if not cfg.get("eval_every"):
             print("[siss_amd] metrics.sscd is set but eval_every is not: the score is taken at evaluations only")
         return SSCDScore(model, str(mem), os.path.join(str(cfg.output_dir), "metrics_rank0.jsonl"), mean, std)
+
+    def check_injection_score(self):
+        """metrics.denoising_injections: {strength, num_images, prompt} (null / absent: nothing): at each evaluation the memorized
+        image is noised part of the way (strength of pipeline.num_inference_steps) and denoised under validation_prompts[prompt]
+        (SDSampler.denoise_injection).  Needs a vae/ in the checkpoint directory (encoder and decoder), data_files.mem_img_path on
+        disk, 0 < strength with at least one step left (strength * num_inference_steps >= 1), a positive num_images and a prompt
+        index inside validation_prompts -- refused here, before the first step.  Returns the settings, or None."""
+        cfg = self.cfg
+        inj = (cfg.get("metrics") or {}).get("denoising_injections")
+        if not inj:
+            return None
+        if not isinstance(inj, dict):
+            raise ValueError(f"metrics.denoising_injections={inj!r}: a mapping {{strength, num_images, prompt}} is needed")
+        number = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool)
+        strength = inj.get("strength", 0.5)
+        if not number(strength) or not strength > 0:
+            raise ValueError(f"metrics.denoising_injections.strength={strength!r}: a positive number is needed")
+        steps = int(((cfg.get("pipeline") or {}).get("num_inference_steps")) or 50)
+        if int(steps * strength) < 1:
+            raise ValueError(f"metrics.denoising_injections.strength={strength!r} of pipeline.num_inference_steps={steps} leaves no "
+                             "denoising step (strength * num_inference_steps < 1)")
+        n = inj.get("num_images", 1)
+        if not isinstance(n, int) or isinstance(n, bool) or n <= 0:
+            raise ValueError(f"metrics.denoising_injections.num_images={n!r}: a positive count is needed")
+        vp = cfg.get("validation_prompts") or [None]
+        prompt = inj.get("prompt", 0)
+        if not isinstance(prompt, int) or isinstance(prompt, bool) or not 0 <= prompt < len(vp):
+            raise ValueError(f"metrics.denoising_injections.prompt={prompt!r}: an index into validation_prompts ({len(vp)} entries) "
+                             "is needed")
+        ckpt = str(cfg.get("pretrained_model_name_or_path") or "")
+        if not os.path.isdir(os.path.join(ckpt, "vae")):
+            raise FileNotFoundError(f"metrics.denoising_injections encodes the memorized image and decodes the result: no vae/ "
+                                    f"under {ckpt!r}")
+        mem = (cfg.get("data_files") or {}).get("mem_img_path")
+        if not mem or not os.path.isfile(str(mem)):
+            raise FileNotFoundError(f"metrics.denoising_injections: data_files.mem_img_path {mem!r} (the memorized image; set from "
+                                    "clustering_info_path when deletion.frac_deletion is null) is not a file on disk")
+        if not cfg.get("eval_every"):
+            print("[siss_amd] metrics.denoising_injections is set but eval_every is not: the check runs at evaluations only")
+        return dict(strength=float(strength), num_images=n, prompt=prompt, mem_img_path=str(mem))
 
     def check_fraction_deletion(self):
         """metrics.fraction_deletion (delete_sd.py:224-225,:269-275; null / absent: nothing) needs classifier_path, that file on disk,
@@ -884,7 +991,7 @@ class DeleteSD(_DeleteBase):
         else:
             raise FileNotFoundError("evaluation needs the empty prompt's embedding: no text_encoder/ in the checkpoint directory "
                                     "(pass allow_synthetic=true for a synthetic one)")
-        self.pipeline = SDSampler(unet, vae=vae, scheduler=DDIMScheduler.from_pretrained(path or None))
+        self.pipeline = SDSampler(unet, vae=vae, scheduler=DDIMScheduler.from_pretrained(path or None), vae_encoder=self.vae)
         self._negative_embeds = neg
         return self.pipeline
 
@@ -903,7 +1010,8 @@ class DeleteSD(_DeleteBase):
         to the same file.  With metrics.clip_iqa the same uint8 images go through the CLIP RN50 (clip_iqa.CLIPIQAScore: from the bytes
         the other two metrics made when one of them is on, else bytes and scores in one pass) and {global_step, clip_iqa_<i>} -- the
         mean probability of "Good photo." against "Bad photo." (:264-267) -- is appended as well; only the scores, the labels and
-        the grid's bytes leave the device."""
+        the grid's bytes leave the device.  With metrics.denoising_injections the memorized image is then injected and denoised
+        (evaluate_injection)."""
         import numpy as np
         cfg = self.cfg
         sampler = self.pipeline or self._validation_pipeline(unet, device)
@@ -967,6 +1075,37 @@ class DeleteSD(_DeleteBase):
                        "uncond_noise_norm": np.mean(np.asarray(uncond_n), axis=0)[::-1].tolist()}
                 with open(os.path.join(cfg.output_dir, "noise_norms_rank0.jsonl"), "a") as f:
                     f.write(json.dumps(rec) + "\n")
+            if self.injection is not None:
+                self.evaluate_injection(sampler, step, device, steps)
+
+    _mem_image = None           # the memorized image [1, 3, H, W] in [-1, 1] on the device, read at the first injection
+
+    def evaluate_injection(self, sampler, step, device, steps):
+        """metrics.denoising_injections (check_injection_score): data_files.mem_img_path -- (bytes - 127.5) / 127.5, as
+        data_transforms maps the training images -- through the VAE encoder, noised to the first of the last int(steps * strength)
+        DDIM timesteps and denoised under validation_prompts[prompt] at the validation pass's guidance scale, num_images times
+        from a generator of its own seeded from cfg.seed.  The images go to injected_mem_s<strength>_step<k>.png; with metrics.sscd
+        their mean cosine with the memorized image's embedding is appended to metrics_rank0.jsonl as sscd_inj_<prompt>."""
+        import numpy as np
+        cfg, inj = self.cfg, self.injection
+        if sampler.vae is None or sampler.vae_encoder is None:
+            raise FileNotFoundError("metrics.denoising_injections: the validation pipeline has no VAE encoder / decoder")
+        if self._mem_image is None:
+            from PIL import Image
+            u8 = np.asarray(Image.open(inj["mem_img_path"]).convert("RGB"), dtype=np.uint8)
+            self._mem_image = ((torch.from_numpy(u8.copy()).to(device).float() - 127.5) / 127.5).permute(2, 0, 1)[None].contiguous()
+        vp = cfg.get("validation_prompts") or [None]
+        e = self._prompt_embedding(vp[inj["prompt"]], device)
+        g = torch.Generator(device=device).manual_seed(self.seed())
+        im, _ = sampler.denoise_injection(self._mem_image, e, strength=inj["strength"], negative_prompt_embeds=self._negative_embeds,
+                                          num_inference_steps=steps, guidance_scale=7.5, num_images_per_prompt=inj["num_images"],
+                                          generator=g, output_type="decoded" if self.sscd is not None else "np")
+        if self.sscd is not None:
+            scores, im = self.sscd.score_decoded(im)            # bytes and embeddings in one pass
+            self.sscd.record(f"inj_{inj['prompt']}", scores.cpu(), step)
+            im = im.cpu().numpy()
+        name = f"injected_mem_s{inj['strength']:g}_step{step}.png"
+        _grid(list(im), int(np.sqrt(len(im)))).save(os.path.join(cfg.output_dir, name))
 
 
 def _grid(images, nrow, padding=2):

@@ -138,6 +138,13 @@ class VAEEncoder(_VAEHalf):
     @torch.no_grad()
     def moments(self, x):
         """x [N, 3, H, W] images in [-1, 1] (f32 / bf16, device).  Returns (mean, logvar) [N, 4, H/8, W/8] f32."""
+        mean, logvar = self.raw_moments(x).chunk(2, dim=1)
+        return mean.contiguous(), logvar.clamp(-30.0, 20.0).contiguous()
+
+    @torch.no_grad()
+    def raw_moments(self, x):
+        """The posterior moments as conv_out (with quant_conv folded in) leaves them: [N, 8, H/8, W/8] f32, the mean in channels
+        0..3, the UNCLAMPED log-variance in 4..7 -- what siss_latent_inject (siss_amd/sd_sampler.py) samples from in one launch."""
         cfg = self.cfg
         assert x.is_cuda and x.dim() == 4 and x.shape[1] == cfg.in_channels
         self.tape, self.gmap, self._uid = [], {}, 0
@@ -154,9 +161,7 @@ class VAEEncoder(_VAEHalf):
         a, _ = self.gn(h, "conv_norm_out", True)
         m, _ = self.conv(a, "conv_out")
         self.tape = []                                   # forward only: drop the backward closures
-        mom = m.to_nchw()
-        mean, logvar = mom.chunk(2, dim=1)
-        return mean.contiguous(), logvar.clamp(-30.0, 20.0).contiguous()
+        return m.to_nchw()
 
     @torch.no_grad()
     def encode(self, x, eps=None, generator=None):
