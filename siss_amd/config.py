@@ -34,11 +34,16 @@ _FIXED_COND = {
 }
 
 
-def _checked(d, names, fixed, what, down_ok, up_ok):
+# What diffusers' EMAModel.save_pretrained registers in `unet_ema/config.json` beside the model's own keys (the EMA's bookkeeping,
+# read back by siss_amd/ema.py::EMAModel.from_pretrained): they do not describe the network.
+EMA_KEYS = ("decay", "min_decay", "optimization_step", "update_after_step", "use_ema_warmup", "inv_gamma", "power")
+
+
+def _checked(d, names, fixed, what, down_ok, up_ok, skip=()):
     """Split a config dict into dataclass fields; raise on keys / values the implementation does not cover."""
     kw = {}
     for k, v in d.items():
-        if k.startswith("_"):                       # _class_name, _diffusers_version, _name_or_path, hydra's _target_
+        if k.startswith("_") or k in skip:          # _class_name, _diffusers_version, _name_or_path, hydra's _target_
             continue
         if k in names:
             kw[k] = tuple(v) if isinstance(v, list) else v
@@ -91,7 +96,8 @@ class UNet2DConfig:
     @staticmethod
     def from_dict(d):
         names = {f.name for f in fields(UNet2DConfig)}
-        kw = _checked(d, names, _FIXED_2D, "UNet2DModel", {"DownBlock2D", "AttnDownBlock2D"}, {"UpBlock2D", "AttnUpBlock2D"})
+        kw = _checked(d, names, _FIXED_2D, "UNet2DModel", {"DownBlock2D", "AttnDownBlock2D"}, {"UpBlock2D", "AttnUpBlock2D"},
+                      skip=EMA_KEYS)
         # UNet2DModel defaults that differ from the celeb dataclass defaults
         kw.setdefault("attention_head_dim", 8)
         kw.setdefault("norm_eps", 1e-5)

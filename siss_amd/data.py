@@ -102,6 +102,38 @@ class SDData(torch.utils.data.Dataset):
         return img, self.img_labels[idx]
 
 
+class HFDataset(torch.utils.data.Dataset):
+    """data/src/hf_dataset.py:4-32 of the reference without the hub: `name` is a DIRECTORY holding `<split>.npz` with `image`
+    (uint8 [N, H, W] or [N, H, W, C]) and `label` ([N] integers); filter in {all, deletion (label == class_to_remove), nondeletion}.
+    Items are the images through `transform` (the reference hands the transform a PIL image; ToTensor takes the array alike)."""
+
+    def __init__(self, filter, name, split, image_key="image", class_to_remove=None, transform=None):
+        fn = os.path.join(str(name), f"{split}.npz")
+        if not os.path.isfile(fn):
+            raise FileNotFoundError(f"dataset {name!r}: {fn} is not a file on disk (no network: hub ids cannot be fetched; export the "
+                                    "split as an .npz with `image` and `label`, or pass allow_synthetic=true for synthetic images)")
+        with np.load(fn) as z:
+            images, labels = z[image_key], z["label"]
+        if images.dtype != np.uint8 or images.ndim not in (3, 4) or labels.shape != images.shape[:1]:
+            raise ValueError(f"{fn}: `{image_key}` must be uint8 [N, H, W] or [N, H, W, C] with `label` [N]; got {images.dtype} "
+                             f"{images.shape}, label {labels.shape}")
+        if filter in ("deletion", "nondeletion"):
+            if class_to_remove is None:
+                raise ValueError(f"{filter.capitalize()} filter requires removal class to be specified.")
+            keep = (labels == class_to_remove) if filter == "deletion" else (labels != class_to_remove)
+            images, labels = images[keep], labels[keep]
+        elif filter != "all":
+            raise ValueError("Invalid filter.")
+        self.images, self.labels, self.transform, self.image_key = images, labels, transform, image_key
+
+    def __len__(self):
+        return len(self.images)
+
+    def __getitem__(self, idx):
+        image = self.images[int(idx)]
+        return self.transform(image) if self.transform else image
+
+
 class ImagesOnly(torch.utils.data.Dataset):
     """The images of a dataset whose items are (image, label): what the loop stacks into a batch (delete_sd.py takes batch[0])."""
 
@@ -183,6 +215,34 @@ class RepeatedSampler(torch.utils.data.Sampler):
 
     def __iter__(self):
         return iter(torch.arange(len(self.data_source)).repeat_interleave(self.num_repeats).tolist())
+
+
+class EpochSampler:
+    """The batches of DataLoader(shuffle=True, batch_size=B) epoch by epoch, resumable: epoch e's permutation comes from a generator
+    seeded by (seed, e) alone, so (epoch, position) names the state -- position counts the batches of that epoch already taken.
+    The partial last batch is kept.  Iterating yields (epoch, position, index list) from the current state on and moves it."""
+
+    def __init__(self, n, batch_size, seed, num_epochs, epoch=0, position=0):
+        assert n > 0 and batch_size > 0
+        self.n, self.batch_size, self.seed, self.num_epochs = int(n), int(batch_size), int(seed), int(num_epochs)
+        self.epoch, self.position = int(epoch), int(position)
+
+    def __len__(self):
+        """batches per epoch: len(train_dataloader)"""
+        return -(-self.n // self.batch_size)
+
+    def permutation(self, epoch):
+        return np.random.default_rng([self.seed, int(epoch)]).permutation(self.n)
+
+    def __iter__(self):
+        while self.epoch < self.num_epochs:
+            perm = self.permutation(self.epoch)
+            while self.position < len(self):
+                lo = self.position * self.batch_size
+                item = (self.epoch, self.position, perm[lo:lo + self.batch_size].tolist())
+                self.position += 1
+                yield item
+            self.epoch, self.position = self.epoch + 1, 0
 
 
 def batches(dataset, sampler, batch_size):

@@ -173,6 +173,7 @@ TARGET_REMAP = {
     "torchvision.transforms.Normalize": "siss_amd.data.Normalize",
     "data.src.celeb_dataset.CelebAHQ": "siss_amd.data.CelebAHQ",
     "data.src.sd_dataset.SDData": "siss_amd.data.SDData",
+    "data.src.hf_dataset.HFDataset": "siss_amd.data.HFDataset",
     "metrics.likelihood.LikelihoodEvaluator": "siss_amd.likelihood.LikelihoodEvaluator",
     "metrics.song_likelihood.sde_lib.VPSDE": "siss_amd.likelihood.VPSDE",
     "metrics.song_likelihood.sde_lib.VESDE": "siss_amd.likelihood.VESDE",          # (refused when built)

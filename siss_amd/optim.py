@@ -5,6 +5,7 @@ import torch
 from . import lib
 
 MODE_NORM_FIX, MODE_ERASEDIFF, MODE_NORM_FIX_INF_GUARD = 0, 1, 2
+EMA_STEP, EMA_ONE_MINUS_DECAY, EMA_DECAY = 5, 6, 7        # slots of the single-set block (csrc/train_state.hip TrainScalars)
 
 
 class FlatAdamW:
@@ -62,6 +63,46 @@ class FlatAdamW:
         lib.call("siss_recombine_clip_adamw", gx_shard, ga_shard, self.p[lo:hi], self.m[lo:hi], self.v[lo:hi],
                  self.shadow[lo:hi] if self.shadow is not None else None, None, n, self.lr, self.betas[0],
                  self.betas[1], self.eps, self.wd, self.scalars)
+
+    # ------------------------------------------------------------------ the single-set update (csrc/train_state.hip)
+    def _train_block(self):
+        """The scalar block of the single-set update (its own: `scalars` above belongs to launch / launch_sharded), the f64 slabs,
+        and the host's mirror of the block's EMA step count (every launch adds exactly one: no read-back needed to know it)."""
+        if getattr(self, "train_scalars", None) is None:
+            dev = self.p.device
+            self.train_scalars = torch.zeros(lib.query("siss_train_scalars_words"), dtype=torch.float32, device=dev)
+            self.train_partials = torch.zeros(lib.query("siss_train_partials_words"), dtype=torch.float64, device=dev)
+            self.train_ema_step = 0
+        return self.train_scalars
+
+    def launch_single(self, g, ema=None, want_grad=False):
+        """Enqueue clip + AdamW on ONE gradient set g [P] f32 (train_unconditional.py:409-415 of the reference), with the EMA of the
+        weights in the same pass (ema: siss_amd.ema.EMAModel over this parameter buffer, or None).  No host sync."""
+        n = self.p.numel()
+        assert g.dtype == torch.float32 and g.shape == (n,) and g.is_contiguous()
+        blk = self._train_block()
+        if ema is not None:
+            assert ema.flat.shape == self.p.shape and ema.flat.device == self.p.device
+            if ema.optimization_step != self.train_ema_step:      # the EMA was stepped (or loaded) elsewhere: the block follows it
+                blk[EMA_STEP:EMA_STEP + 1].fill_(float(ema.optimization_step))
+                self.train_ema_step = ema.optimization_step
+            sched = ema.schedule_args()
+        else:
+            sched = (0.0, 0.0, 1.0, 1.0, 0, 0)
+        lib.call("siss_grad_norm_single", g, n, self.max_grad_norm, self.betas[0], self.betas[1], *sched,
+                 self.train_partials, blk)
+        if want_grad and (self.last_grad is None):
+            self.last_grad = torch.empty_like(self.p)
+        lib.call("siss_clip_adamw_ema", g, self.p, self.m, self.v, None if ema is None else ema.flat, self.shadow,
+                 self.last_grad if want_grad else None, n, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, blk)
+        self.train_ema_step += 1
+        if ema is not None:
+            ema.optimization_step += 1
+
+    @staticmethod
+    def train_stats_from(s):
+        """stats_from for the single-set block (siss_train_scalars_words: ||g||, clip, step, bc1, bc2_sqrt, EMA step, 1 - decay, decay)."""
+        return {"pre_clip_norm": float(s[0]), "clip_coef": float(s[1]), "step": int(s[2]), "ema_decay": float(s[EMA_DECAY])}
 
     def stats(self):
         """One small D2H copy: the logged gradient scalars (delete_celeb.py:748)."""

@@ -1,11 +1,13 @@
 """Task classes behind the reference's entry points (main.py:9-35): ``Task.run()``,
-``delete_celeb.DeleteCeleb(cfg)``, ``delete_tshirt.DeleteTShirt(cfg)``, ``delete_sd.DeleteSD(cfg)``.
+``delete_celeb.DeleteCeleb(cfg)``, ``delete_tshirt.DeleteTShirt(cfg)``, ``delete_sd.DeleteSD(cfg)``, and the pre-training task
+``train_unconditional.TrainUnconditional(cfg)`` that produces the T-shirt experiment's base checkpoint.
 
 The loop is the hot path of delete_celeb.py:557-773 / delete_tshirt.py:501-717 driven through
 ``SISSStepper`` (fused kernels, one dual-cotangent backward, one collective per optimizer step).
 Evaluation / sampling / wandb (log_metrics, delete_celeb.py:484-545) are outside this path; the
 per-step scalars the reference logs are returned by ``stepper.stats()`` and written as JSON lines.
 """
+import contextlib
 import json
 import os
 import time
@@ -1106,6 +1108,167 @@ class DeleteSD(_DeleteBase):
             im = im.cpu().numpy()
         name = f"injected_mem_s{inj['strength']:g}_step{step}.png"
         _grid(list(im), int(np.sqrt(len(im)))).save(os.path.join(cfg.output_dir, name))
+
+
+class TrainUnconditional(Task):
+    """config/train_tshirt_mnist.yaml -- DDPM pre-training (train_unconditional.py:76-532 of the reference): `num_epochs` epochs of
+    the plain eps-MSE step (siss_amd/train.py) with the EMA of the weights, a sample grid from the EMA weights every `sampling_steps`,
+    a resumable `checkpoint-<global_step>/` every `checkpointing_steps` (siss_amd/checkpoint.py), `unet/` and `unet_ema/` at the end."""
+
+    def __init__(self, cfg):
+        self.cfg = cfg
+
+    compute_dtype = _DeleteBase.compute_dtype
+
+    def check_supported(self):
+        cfg = self.cfg
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise NotImplementedError("WORLD_SIZE > 1: the pre-training task runs on one GPU (no sharded epoch loader, no all-reduce "
+                                      "of the single gradient set yet)")
+        pt = (cfg.get("scheduler") or {}).get("prediction_type", "epsilon")
+        if pt != "epsilon":
+            raise NotImplementedError(f"scheduler.prediction_type={pt!r}: only the epsilon objective (train_unconditional.py:388-391) "
+                                      "is implemented; 'sample' with its SNR weights (:392-403) is not")
+        if cfg.get("mixed_precision") == "fp16":
+            raise NotImplementedError("mixed_precision='fp16': this build computes in 'bf16' or in f32 (null / 'no'); there is no "
+                                      "loss scaler")
+        if cfg.get("enable_xformers_memory_efficient_attention"):
+            raise NotImplementedError("enable_xformers_memory_efficient_attention=true: xformers is not used here (the attention "
+                                      "kernels are this package's own)")
+
+    def dataset(self, shape):
+        cfg = self.cfg
+        try:
+            if cfg.get("dataset") is None:
+                raise FileNotFoundError("no dataset configured")
+            return hydra_lite.instantiate(cfg.dataset, transform=hydra_lite.instantiate(cfg.transform))
+        except FileNotFoundError as e:
+            if not cfg.get("allow_synthetic"):
+                raise
+            n = int(cfg.get("synthetic_images") or 4096)
+            print(f"[siss_amd] allow_synthetic: dataset unavailable ({e}); using {n} SYNTHETIC images")
+            return SyntheticImages(n, shape, seed=1)
+
+    def run(self):
+        from .checkpoint import load_state, save_state, step_of
+        from .data import EpochSampler
+        from .ema import EMAModel
+        from .model import UNet2DModel
+        from .scheduler import lr_multiplier
+        from .train import TrainStepper
+        cfg = self.cfg
+        self.check_supported()
+        device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
+        torch.cuda.set_device(device)
+        seed = int(cfg.random_seed)
+        torch.manual_seed(seed)
+        dt = self.compute_dtype()
+        ucfg = {k: v for k, v in (cfg.get("unet") or {}).items() if not k.startswith("_")}
+        unet = UNet2DModel(UNet2DConfig.from_dict(ucfg) if ucfg else UNet2DConfig.mnist_tshirt(), device=device, compute_dtype=dt)
+        unet.engine.init_random(seed=seed)
+        sc = cfg.get("scheduler") or {}
+        sched = DDPMScheduler(**{k: sc[k] for k in ("num_train_timesteps", "beta_start", "beta_end", "beta_schedule",
+                                                    "prediction_type") if k in sc})
+        ecfg = cfg.get("ema") or {}
+        ema = None
+        if ecfg.get("use_ema"):                                  # train_unconditional.py:186-194
+            ema = EMAModel(unet, decay=float(ecfg.get("ema_max_decay", 0.9999)), use_ema_warmup=True,
+                           inv_gamma=float(ecfg.get("ema_inv_gamma", 1.0)), power=float(ecfg.get("ema_power", 2 / 3)),
+                           model_cls=UNet2DModel, model_config=unet.config)
+        opt = hydra_lite.instantiate(cfg.optimizer)
+        B, ga = int(cfg.train_batch_size), int(cfg.gradient_accumulation_steps)
+        stepper = TrainStepper(unet.engine, sched.alphas_cumprod, lr=opt.lr, betas=opt.betas, eps=opt.eps,
+                               weight_decay=opt.weight_decay, grad_accum=ga, ema=ema, mixed_precision=cfg.get("mixed_precision"))
+        shape = (unet.config.in_channels, unet.config.sample_size, unet.config.sample_size)
+        ds = self.dataset(shape)
+        num_epochs = int(cfg.num_epochs)
+        sampler = EpochSampler(len(ds), B, seed, num_epochs)
+        per_epoch = -(-len(sampler) // ga)                       # num_update_steps_per_epoch (:297-299)
+        max_steps = num_epochs * per_epoch
+        lr_name = str(cfg.get("lr_scheduler") or "constant")
+        warm, total = int(cfg.get("lr_warmup_steps") or 0) * ga, len(sampler) * num_epochs        # :277-282
+        lr_multiplier(lr_name, 0, warm, total)                   # raises now for a schedule that is not implemented
+        g = torch.Generator(device=device).manual_seed(seed)
+        T = sched.config.num_train_timesteps
+        global_step = lr_pos = 0
+        path = cfg.get("checkpoint_path")
+        if path:                                                 # :320-345
+            print(f"Resuming from checkpoint {path}")
+            state = load_state(str(path), unet, ema, stepper, generator=g)
+            global_step = step_of(path)
+            if state["global_step"] != global_step:
+                raise ValueError(f"{path}: the directory name says step {global_step}, its state.json {state['global_step']}")
+            sampler.epoch, sampler.position, lr_pos = int(state["epoch"]), int(state["position"]), int(state["lr_position"])
+        os.makedirs(cfg.output_dir, exist_ok=True)
+        log = open(os.path.join(cfg.output_dir, "train_log_rank0.jsonl"), "a")
+        sampling_steps, ckpt_steps = int(cfg.get("sampling_steps") or 0), int(cfg.get("checkpointing_steps") or 0)
+        limit = cfg.get("checkpoints_total_limit")
+        t0 = time.perf_counter()
+        pending = None
+
+        def write_log(handle, meta):
+            st = handle.get()
+            st["step"], st["epoch"], st["elapsed_s"] = meta
+            log.write(json.dumps(st) + "\n")
+            log.flush()
+            print(f"step {meta[0]}/{max_steps}  loss {st['loss']:.4g}  lr {st['lr']:.3g}  |g| {st['pre_clip_norm']:.4g}")
+
+        try:
+            for epoch, pos, idx in sampler:
+                # lr_scheduler.step() (:414): accelerate's wrapper advances the schedule once per optimizer step that really happens,
+                # not per micro-batch (AcceleratedScheduler under accumulate()); lr_pos counts those
+                if stepper._micro == 0:
+                    stepper.opt.lr = opt.lr * lr_multiplier(lr_name, lr_pos, warm, total)
+                x0 = torch.stack([ds[i] for i in idx]).to(device, non_blocking=True)
+                noise = torch.randn(x0.shape, device=device, generator=g)
+                t = torch.randint(0, T, (x0.shape[0],), device=device, generator=g)
+                stepper.micro_step(x0, noise, t)
+                if pos + 1 == len(sampler):
+                    stepper.flush()                              # a partial accumulation group at the end of an epoch steps on what it has
+                if stepper._micro != 0:
+                    continue
+                global_step += 1
+                lr_pos += 1
+                handle, meta = stepper.stats_async(), (global_step, epoch, time.perf_counter() - t0)
+                if pending is not None:
+                    write_log(*pending)
+                pending = (handle, meta)
+                if sampling_steps and global_step % sampling_steps == 0:
+                    self.sample_grid(unet, ema, sched, global_step)
+                if ckpt_steps and global_step % ckpt_steps == 0:
+                    save_state(os.path.join(cfg.output_dir, f"checkpoint-{global_step}"), unet, ema, stepper,
+                               dict(global_step=global_step, epoch=sampler.epoch + (sampler.position == len(sampler)),
+                                    position=sampler.position % len(sampler), lr_position=lr_pos, generator=g),
+                               limit=None if limit is None else int(limit))
+        finally:
+            if pending is not None:
+                try:
+                    write_log(*pending)
+                except Exception:
+                    pass
+            log.close()
+        unet.save_pretrained(os.path.join(cfg.output_dir, (cfg.get("subfolders") or {}).get("unet") or "unet"))
+        if ema is not None:
+            ema.save_pretrained(os.path.join(cfg.output_dir, (cfg.get("subfolders") or {}).get("unet_ema") or "unet_ema"))
+        return stepper
+
+    def sample_grid(self, unet, ema, sched, global_step):
+        """train_unconditional.py:427-452: `eval_batch_size` samples from the EMA weights (swapped under the engine for the
+        evaluation), as a make_grid image samples_step<N>.png."""
+        import numpy as np
+        from .sampler import Evaluator
+        cfg = self.cfg
+        if getattr(self, "_evaluator", None) is None:           # one per run: the captured forward is reused by every grid
+            self._evaluator = Evaluator(cfg)
+            self._evaluator.load_model(unet, sched)
+        ev = self._evaluator
+        n = int(cfg.get("eval_batch_size") or 16)
+        with (ema.applied(unet) if ema is not None else contextlib.nullcontext()):
+            imgs = ev.sample_images(n)
+        imgs = (np.clip(imgs, 0, 1) * 255).astype(np.uint8)
+        if imgs.shape[-1] == 1:
+            imgs = np.repeat(imgs, 3, axis=-1)
+        _grid(list(imgs), int(np.sqrt(n))).save(os.path.join(cfg.output_dir, f"samples_step{global_step}.png"))
 
 
 def _grid(images, nrow, padding=2):

@@ -13,6 +13,7 @@ DOCS = {
     'gemm_tn.hip': "Panelled TN GEMM on bf16 MFMA: weight (and bias) gradients for both cotangent sets (g_x, g_a) in one pass.\n * Replaces the wgrad half of the two `accelerator.backward` calls (delete_celeb.py:691,:702) and the\n * clone / subtract split of :694-711.",
     'groupnorm.hip': "GroupNorm(+SiLU) forward / backward on padded NHWC.  Replaces torch.nn.GroupNorm + F.silu inside\n * diffusers' ResnetBlock2D.norm1/norm2, Attention.group_norm and UNet2DModel.conv_norm_out.",
     'optimizer.hip': "Flat-buffer norm-fix + recombine + clip + AdamW.  Replaces delete_celeb.py:714-753 (five 450-tensor\n * loops), :767 (clip_grad_norm_) and :769 (torch.optim.AdamW.step).",
+    'train_state.hip': "The training state of the DDPM pre-training task (train_unconditional.py:366-415 of the reference: F.mse_loss ->\n * clip_grad_norm_(1.0) -> torch.optim.AdamW.step -> diffusers' EMAModel.step): ONE gradient set, the EMA of the weights written by the\n * same pass that updates them, and the swap that puts the EMA weights under the engine for an evaluation (EMAModel.store /\n * copy_to / restore in one pass each way).",
     'elementwise.hip': "Data movement on the padded-NHWC layout: F.interpolate(nearest 2x), torch.cat of skip connections,\n * Downsample2D's F.pad+stride-2 gather (space-to-depth), attention reshape/residual, bias-gradient column sums.",
     'conv_small.hip': "conv_out (Cout = image channels): direct kernels for UNet2DModel.conv_out and its backward.",
     'attention.hip': "Row softmax fwd/bwd of the single-head attention block (diffusers Attention, upcast_softmax=True).",
@@ -31,7 +32,7 @@ DOCS = {
     'timeemb.hip': "Sinusoidal timestep embedding (diffusers Timesteps/get_timestep_embedding), TimestepEmbedding MLP and\n * ResnetBlock2D.time_emb_proj linears (M = batch rows), forward and backward.",
 }
 ORDER = ['siss_loss.hip', 'gemm_nt.hip', 'gemm_tn.hip', 'groupnorm.hip', 'conv_small.hip', 'attention.hip', 'attn1h.hip', 'flash_attn.hip', 'transformer.hip',
-         'timeemb.hip', 'elementwise.hip', 'optimizer.hip', 'likelihood.hip', 'membership.hip', 'metric_conv.hip', 'inception.hip', 'kmeans.hip', 'sscd.hip', 'clip_iqa.hip', 'prompt_grad.hip', 'injection.hip', 'f32_path.hip']
+         'timeemb.hip', 'elementwise.hip', 'optimizer.hip', 'train_state.hip', 'likelihood.hip', 'membership.hip', 'metric_conv.hip', 'inception.hip', 'kmeans.hip', 'sscd.hip', 'clip_iqa.hip', 'prompt_grad.hip', 'injection.hip', 'f32_path.hip']
 HEAD = '''/* siss_hip.h -- C ABI of libsiss_hip.so: the MI355X (gfx950) kernels of the SISS unlearning step.
  *
  * GENERATED by tools/gen_header.py from the .hip sources under siss_amd/csrc -- edit the sources, then regenerate.
