@@ -24,6 +24,7 @@ DOCS = {
     'membership.hip': "The membership-loss metric (metrics/class_membership.py of the reference, MembershipLoss.compute_membership_losses):\n * the (image, noise, timestep) work items of an evaluation noised straight into the forward's input and their squared errors\n * summed per pair, both driven by one device index table -- replaces the three expanded I x J tensors, add_noise x2 and\n * torch.sum((out - noise) ** 2) of :77-110.",
     'kmeans.hip': "The SD deletion fraction (delete_sd.py:224-225,:269-275: joblib's scikit-learn KMeans.predict on 255 * ToTensor(PIL) of the\n * validation images, on the CPU) and the fit that produces that classifier: the decoder's output to uint8 with its distances to the\n * centres in one pass, Lloyd's assignment and update over uint8 rows; f64 / integer sums in fixed orders, no atomics.",
     'metric_conv.hip': "What the four f32 metric networks share (the MNIST ResNet-18 of metrics/mnist_resnet.py, the FID Inception-v3, the SSCD\n * ResNet-50 and the CLIP RN50 image tower; siss_amd/metric_net.py): one implicit-GEMM convolution for every layer, fc and projection\n * (NHWC gather with zero fill, or the NCHW image; independent KH / KW / padding; folded-BN bias, optional residual, optional ReLU,\n * written into a channel slice; deterministic split-K) and the 3 x 3 max pool.",
+    'metric_train.hip': "Training of the MNIST ResNet-18 metric classifier (notebooks/cnn-resnet18-mnist.ipynb of the reference: train-mode\n * BatchNorm, F.cross_entropy, autograd, torch.optim.Adam; siss_amd/classifier_train.py), f32: the convolution's data and weight\n * gradients on the packed weights of siss_metric_conv above, batch-statistics BatchNorm forward / backward, the 3 x 3 / 2 max pool's\n * backward and softmax cross-entropy; sums in f64 or in fixed orders, no atomics.",
     'inception.hip': "The FID metric (metrics/fid.py of the reference: torchmetrics' FrechetInceptionDistance on the FID Inception-v3 of\n * torch-fidelity), f32: the preprocessing (uint8 truncation, TF1 bilinear resize to 299 x 299, (x - 128) / 128) in one launch, the\n * average pools, and the f64 feature statistics sum / cov_sum; the 94 BasicConv2d layers and the max pools run on siss_metric_conv /\n * siss_metric_maxpool3 above.",
     'sscd.hip': "The SD copy-detection score (delete_sd.py:226-228,:277-283: torch.jit.load of the SSCD ResNet-50, Normalize(ToTensor(PIL)),\n * the mean of mem_embedding @ all_embeddings.T), f32: the trunk and the 2048 -> 512 linear layer run on siss_metric_conv /\n * siss_metric_maxpool3 above; these are the preprocessing (from uint8, or fused with the decoder output's quantisation), GeM pooling and\n * F.normalize with the score, sums in f64 in fixed orders, no atomics.",
     'clip_iqa.hip': "The SD image-quality score (delete_sd.py:222-223,:264-267: torchmetrics' CLIPImageQualityAssessment, the OpenAI CLIP RN50\n * image tower against the anchors \"Good photo.\" / \"Bad photo.\"), f32: the convolutions and the q / c_proj projections run on\n * siss_metric_conv, the preprocessing on siss_sscd_preprocess above; these are the anti-aliasing average pool, the attention pool with the\n * query folded into the key projection and the value projection taken after the pooling (no T x E x E product, no token tensor), and\n * the score; sums in f64 or in fixed orders, no atomics.",
@@ -32,7 +33,7 @@ DOCS = {
     'timeemb.hip': "Sinusoidal timestep embedding (diffusers Timesteps/get_timestep_embedding), TimestepEmbedding MLP and\n * ResnetBlock2D.time_emb_proj linears (M = batch rows), forward and backward.",
 }
 ORDER = ['siss_loss.hip', 'gemm_nt.hip', 'gemm_tn.hip', 'groupnorm.hip', 'conv_small.hip', 'attention.hip', 'attn1h.hip', 'flash_attn.hip', 'transformer.hip',
-         'timeemb.hip', 'elementwise.hip', 'optimizer.hip', 'train_state.hip', 'likelihood.hip', 'membership.hip', 'metric_conv.hip', 'inception.hip', 'kmeans.hip', 'sscd.hip', 'clip_iqa.hip', 'prompt_grad.hip', 'injection.hip', 'f32_path.hip']
+         'timeemb.hip', 'elementwise.hip', 'optimizer.hip', 'train_state.hip', 'likelihood.hip', 'membership.hip', 'metric_conv.hip', 'metric_train.hip', 'inception.hip', 'kmeans.hip', 'sscd.hip', 'clip_iqa.hip', 'prompt_grad.hip', 'injection.hip', 'f32_path.hip']
 HEAD = '''/* siss_hip.h -- C ABI of libsiss_hip.so: the MI355X (gfx950) kernels of the SISS unlearning step.
  *
  * GENERATED by tools/gen_header.py from the .hip sources under siss_amd/csrc -- edit the sources, then regenerate.
