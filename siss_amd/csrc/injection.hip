@@ -10,15 +10,14 @@
 // reduction, no atomics.  Built with -ffp-contract=off (build.py EXACT): every product and sum rounded on its own, as torch's chain
 // rounds them; libm's expf (not a fast intrinsic).
 #include "common.h"
+#include "latent_sample.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 
 __device__ __forceinline__ float inject_one(float mean, float logvar, float ez, float et, float scaling, float a, float b) {
-    const float lv = fminf(fmaxf(logvar, -30.f), 20.f);
-    const float sd = expf(__fmul_rn(0.5f, lv));
-    const float z = __fmul_rn(__fadd_rn(mean, __fmul_rn(sd, ez)), scaling);
+    const float z = posterior_sample(mean, logvar, ez, scaling);          // latent_sample.h: shared with siss_latent_sample
     return __fadd_rn(__fmul_rn(a, z), __fmul_rn(b, et));
 }
 

@@ -17,10 +17,16 @@ class ToTensor:
             a = a[:, :, None]
         return torch.from_numpy(a).permute(2, 0, 1).contiguous()
 
+    def __repr__(self):
+        return "ToTensor()"
+
 
 class Normalize:
     def __init__(self, mean, std):
         self.mean, self.std = list(mean), list(std)
+
+    def __repr__(self):                                  # (a stable repr: the latent cache's fingerprint hashes it)
+        return f"Normalize(mean={[float(v) for v in self.mean]}, std={[float(v) for v in self.std]})"
 
     def __call__(self, x):
         m = torch.tensor(self.mean, dtype=x.dtype, device=x.device).view(-1, 1, 1)
@@ -31,6 +37,9 @@ class Normalize:
 class Compose:
     def __init__(self, transforms):
         self.transforms = list(transforms)
+
+    def __repr__(self):
+        return "Compose([" + ", ".join(repr(t) for t in self.transforms) + "])"
 
     def __call__(self, x):
         for t in self.transforms:

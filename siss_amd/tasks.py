@@ -18,6 +18,7 @@ import torch
 from . import hydra_lite
 from .config import UNet2DConditionConfig, UNet2DConfig
 from .data import InfiniteSampler, Prefetcher, RepeatedSampler, SyntheticImages, batches
+from .latent_cache import IndexBatch, index_batches
 from .scheduler import DDPMScheduler
 from .step import SISSStepper
 
@@ -414,11 +415,8 @@ class _DeleteBase(Task):
             superfactor_decay=d.get("superfactor_decay"))
         shape = (unet.config.in_channels, unet.config.sample_size, unet.config.sample_size)
         ds_all, ds_del = self.datasets(shape)
-        # keep shard: decoded / pinned / copied in the background, `depth` batches ahead (the forget set is one or a
-        # few images repeated: a plain iterator is enough)
-        it_all = Prefetcher(ds_all, InfiniteSampler(ds_all, rank=rank, num_replicas=world), B, device=device,
-                            workers=int(cfg.get("dataloader_num_workers") or 4))
-        it_del = batches(ds_del, self.deletion_sampler(ds_del, B), B)
+        it_all = self.keep_batches(ds_all, B, rank, world, device)
+        it_del = self.forget_batches(ds_del, B, device)
         n_steps = int(cfg.training_steps) * max(1, len(d.get("img_name") or [1]))
         cond = self.conditioning(B, device)
         os.makedirs(cfg.output_dir, exist_ok=True)
@@ -494,6 +492,16 @@ class _DeleteBase(Task):
 
     def deletion_sampler(self, ds, B):
         return InfiniteSampler(ds, shuffle=False) if len(ds) >= B else RepeatedSampler(ds, 1 << 30)
+
+    def keep_batches(self, ds_all, B, rank, world, device):
+        """The keep batches of the loop, an iterator with close(): the rank's shard decoded / pinned / copied in the background,
+        `depth` batches ahead."""
+        return Prefetcher(ds_all, InfiniteSampler(ds_all, rank=rank, num_replicas=world), B, device=device,
+                          workers=int(self.cfg.get("dataloader_num_workers") or 4))
+
+    def forget_batches(self, ds_del, B, device):
+        """The forget batches of the loop (the forget set is one or a few images repeated: a plain iterator is enough)."""
+        return batches(ds_del, self.deletion_sampler(ds_del, B), B)
 
 
 class DeleteCeleb(_DeleteBase):
@@ -671,9 +679,76 @@ class DeleteSD(_DeleteBase):
             self.text_encoder = CLIPTextEncoder.from_pretrained(path, "text_encoder", device)
 
     def prepare_batch(self, x, generator):
+        if isinstance(x, IndexBatch):                           # latent_cache on: indices -> the cached moments, sampled in one launch
+            return x.cache.latents(x, generator)
         if self.vae is not None and x.shape[1] == self.vae.cfg.in_channels and x.shape[1] != 4:
             return self.vae.encode(x, generator=generator)      # latent_dist.sample() * scaling_factor (:879-888)
         return x
+
+    # -- latent_cache: null | {enabled, path, max_bytes, chunk} (OPT-IN; siss_amd/latent_cache.py) -----------------------------
+    encodes_images = False      # set by datasets(): the loop's batches are images the VAE encodes (not latents)
+    keep_cache = None
+    forget_cache = None
+
+    def latent_cache_cfg(self):
+        """The latent_cache block when it is enabled AND the loop encodes images, else None.  The cache holds the frozen VAE's
+        posterior moments per image, so it has nothing to do for pre-encoded latents_all / latents_deletion or synthetic latents."""
+        lc = self.cfg.get("latent_cache")
+        if not lc:
+            return None
+        if not isinstance(lc, dict):
+            raise ValueError(f"latent_cache={lc!r}: null or a mapping {{enabled, path, max_bytes, chunk}} is needed")
+        unknown = sorted(set(lc) - {"enabled", "path", "max_bytes", "chunk"})
+        if unknown:
+            raise ValueError(f"latent_cache: unknown keys {unknown} (enabled, path, max_bytes, chunk)")
+        if not lc.get("enabled"):
+            return None
+        if not self.encodes_images:
+            print("[siss_amd] latent_cache.enabled is set but this run encodes no images (latents_all / latents_deletion or synthetic "
+                  "latents): the cache does not apply")
+            return None
+        return lc
+
+    def _latent_cache(self, ds, which, lc, device):
+        """The cache of one dataset (`which`: keep / forget): its budget is latent_cache.max_bytes, its file <path>/<which>.safetensors
+        (read by every rank at the start when it is there and belongs)."""
+        from .data import TensorImages
+        from .latent_cache import LatentCache
+        vc = self.vae.cfg
+        down = 2 ** (len(vc.block_out_channels) - 1)
+        hw = tuple(ds.t.shape[-2:]) if isinstance(ds, TensorImages) else (int(self.cfg.resolution),) * 2
+        if hw[0] % down or hw[1] % down:
+            raise ValueError(f"latent_cache: images of {hw[0]} x {hw[1]} are no multiple of the VAE's factor {down}")
+        cache = LatentCache(self.vae, ds, (vc.latent_channels, hw[0] // down, hw[1] // down), device=device,
+                            max_bytes=lc.get("max_bytes"), chunk=lc.get("chunk"), name=f"latent cache ({which})")
+        if lc.get("path"):
+            cache.load(os.path.join(str(lc.get("path")), f"{which}.safetensors"))
+        return cache
+
+    def keep_batches(self, ds_all, B, rank, world, device):
+        lc = self.latent_cache_cfg()
+        if lc is None:
+            return super().keep_batches(ds_all, B, rank, world, device)
+        self.keep_cache = self._latent_cache(ds_all, "keep", lc, device)
+        return index_batches(InfiniteSampler(ds_all, rank=rank, num_replicas=world), B, self.keep_cache)
+
+    def forget_batches(self, ds_del, B, device):
+        lc = self.latent_cache_cfg() if self.keep_cache is not None else None       # (on for both or for neither)
+        if lc is None:
+            return super().forget_batches(ds_del, B, device)
+        self.forget_cache = self._latent_cache(ds_del, "forget", lc, device)
+        return index_batches(self.deletion_sampler(ds_del, B), B, self.forget_cache)
+
+    def run(self):
+        stepper = super().run()
+        path = (self.cfg.get("latent_cache") or {}).get("path")
+        if path and int(os.environ.get("RANK", "0")) == 0:      # rank 0 writes at the end of the run; every rank reads at the start
+            for which, cache in (("keep", self.keep_cache), ("forget", self.forget_cache)):
+                if cache is not None:
+                    rows = cache.save(os.path.join(str(path), f"{which}.safetensors"))
+                    print(f"[siss_amd] {cache.name}: {rows} of {cache.n} rows written to {path}/{which}.safetensors "
+                          f"({cache.encoded} encoded in this run)")
+        return stepper
 
     def seed(self):
         return int(self.cfg.get("seed", 42))                   # config/delete_sd.yaml:80
@@ -924,8 +999,10 @@ class DeleteSD(_DeleteBase):
         if self.vae is not None and img_dir and lp and os.path.isdir(str(img_dir)) and os.path.isfile(str(lp)):
             # delete_sd.py:656,:681-682: the image directory split by kmeans_labels.json; the loop takes batch[0], the images
             kw = dict(img_dir=str(img_dir), labels_fpath=str(lp), transform=hydra_lite.instantiate(cfg.get("data_transforms")))
+            self.encodes_images = True
             return ImagesOnly(hydra_lite.instantiate(cfg.all_data, **kw)), ImagesOnly(hydra_lite.instantiate(cfg.memorized_data, **kw))
         if self.vae is not None and ia and idl and os.path.exists(str(ia)) and os.path.exists(str(idl)):
+            self.encodes_images = True
             return TensorImages(torch.load(ia)), TensorImages(torch.load(idl))     # [N,3,H,W] in [-1,1]: encoded per batch
         if la and ld and os.path.exists(str(la)) and os.path.exists(str(ld)):
             return TensorImages(torch.load(la)), TensorImages(torch.load(ld))
