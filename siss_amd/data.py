@@ -67,8 +67,12 @@ class CelebAHQ(torch.utils.data.Dataset):
     def __len__(self):
         return len(self.paths)
 
+    def load(self, i):
+        """Image i as the transform receives it (what image_store.raw_u8 keeps as bytes)."""
+        return self._open(self.paths[i]).convert("RGB")
+
     def __getitem__(self, i):
-        img = self._open(self.paths[i]).convert("RGB")
+        img = self.load(i)
         return self.transform(img) if self.transform else img
 
 
@@ -223,7 +227,8 @@ class RepeatedSampler(torch.utils.data.Sampler):
         return len(self.data_source) * self.num_repeats
 
     def __iter__(self):
-        return iter(torch.arange(len(self.data_source)).repeat_interleave(self.num_repeats).tolist())
+        # lazily: the loops ask for 2^30 repeats, and a materialised list of them took tens of seconds and 16 GB per forget image
+        return (i for i in range(len(self.data_source)) for _ in range(self.num_repeats))
 
 
 class EpochSampler:
@@ -263,6 +268,32 @@ def batches(dataset, sampler, batch_size):
             if len(buf) == batch_size:
                 yield torch.stack(buf)
                 buf = []
+
+
+class IndexBatch(list):
+    """A batch of dataset indices as the training loop carries it when a device-resident cache of the dataset is on (the latent
+    cache of the SD task, the image store of the pixel-space tasks).  It stays on the HOST -- ``to`` returns it unchanged -- because
+    the cache looks its misses up there, without a device synchronisation; the cache copies the validated indices itself.
+    ``cache``: the LatentCache / ImageStore of the dataset the indices belong to."""
+    cache = None
+
+    def to(self, *args, **kwargs):
+        return self
+
+
+def index_batches(sampler, batch_size, cache=None):
+    """Endless IndexBatch iterator over a sampler: the index order of batches(dataset, sampler, batch_size), nothing decoded."""
+    def fresh():
+        b = IndexBatch()
+        b.cache = cache
+        return b
+    buf = fresh()
+    while True:
+        for i in sampler:
+            buf.append(int(i))
+            if len(buf) == batch_size:
+                yield buf
+                buf = fresh()
 
 
 class Prefetcher:

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import lib
+from .data import IndexBatch, index_batches      # (they live in data.py: the image store carries them too)  # noqa: F401
 
 DEFAULT_MAX_BYTES = 8 << 30
 DEFAULT_CHUNK = 16
@@ -48,31 +49,6 @@ def latent_sample(cache, idx, eps, scaling, out_dtype=torch.float32, out=None, n
     lib.call("siss_latent_sample", cache, idx, eps, out, int(out_dtype == torch.bfloat16), cache.shape[0], n, chw, float(scaling),
              sample_blocks(n, chw) if nblk is None else int(nblk))
     return out
-
-
-class IndexBatch(list):
-    """A batch of dataset indices as the training loop carries it when the cache is on.  It stays on the HOST -- ``to`` returns it
-    unchanged -- because the cache looks its misses up there, without a device synchronisation; LatentCache.latents copies the
-    validated indices itself.  ``cache``: the LatentCache of the dataset the indices belong to."""
-    cache = None
-
-    def to(self, *args, **kwargs):
-        return self
-
-
-def index_batches(sampler, batch_size, cache=None):
-    """Endless IndexBatch iterator over a sampler: the index order of data.batches(dataset, sampler, batch_size), nothing decoded."""
-    def fresh():
-        b = IndexBatch()
-        b.cache = cache
-        return b
-    buf = fresh()
-    while True:
-        for i in sampler:
-            buf.append(int(i))
-            if len(buf) == batch_size:
-                yield buf
-                buf = fresh()
 
 
 # ---------------------------------------------------------------- fingerprint

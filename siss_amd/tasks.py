@@ -17,8 +17,7 @@ import torch
 
 from . import hydra_lite
 from .config import UNet2DConditionConfig, UNet2DConfig
-from .data import InfiniteSampler, Prefetcher, RepeatedSampler, SyntheticImages, batches
-from .latent_cache import IndexBatch, index_batches
+from .data import IndexBatch, InfiniteSampler, Prefetcher, RepeatedSampler, SyntheticImages, batches, index_batches
 from .scheduler import DDPMScheduler
 from .step import SISSStepper
 
@@ -72,6 +71,23 @@ def _load_sscd(path, allow_random_init, what):
     print(f"[siss_amd] allow_random_init: SSCD checkpoint {path!r} not on disk, RANDOM-INIT ResNet-50: the SSCD figures are "
           "NOT comparable with published ones")
     return SSCDModel()
+
+
+def _open_image_stores(task, cfg, datasets, device):
+    """The image stores of a task: `datasets` {which: dataset} -> task.<which>_store, all of them or none (siss_amd/image_store.py)."""
+    from .image_store import ImageStore, has_rule, parse_config
+    ic = parse_config(cfg.get("image_store"))
+    if ic is None:
+        return
+    without = [f"{which} ({type(ds).__name__})" for which, ds in datasets.items() if not has_rule(ds)]
+    if without:
+        print(f"[siss_amd] image_store.enabled is set but unused: the dataset(s) {', '.join(without)} hold no raw uint8 images "
+              "(synthetic or pre-built tensors): the batches are produced as without it")
+        return
+    for which, ds in datasets.items():
+        store = ImageStore(ds, device=device, max_bytes=ic["max_bytes"], workers=ic["workers"], name=f"image store ({which})")
+        setattr(task, f"{which}_store", store)
+        print(f"[siss_amd] {store.name}: {store.n} images x {store.shape} uint8, {store.nbytes} bytes on {device}")
 
 
 class _DeleteBase(Task):
@@ -183,8 +199,26 @@ class _DeleteBase(Task):
         return int(self.cfg.random_seed)
 
     def prepare_batch(self, x, generator):
-        """Images -> what the loss is taken on (identity for the pixel-space tasks; VAE latents for SD)."""
+        """Images -> what the loss is taken on (identity for the pixel-space tasks; VAE latents for SD).  image_store on: the batch is
+        an IndexBatch, gathered from its store's rows in one launch -- the same bits as the stacked batch."""
+        if isinstance(x, IndexBatch):
+            return x.cache.images(x)
         return x
+
+    # -- image_store: null | {enabled, max_bytes, workers} (OPT-IN; siss_amd/image_store.py) -----------------------------------
+    keep_store = None
+    forget_store = None
+
+    def open_image_stores(self, ds_all, ds_del, device):
+        """One ImageStore per dataset (keep, forget) when image_store is enabled and BOTH datasets have a rule for their raw bytes --
+        on for both or for neither; each rank has its own, there are no collectives.  Synthetic and pre-built tensor datasets are
+        left alone: one line says the store is enabled but unused, and why."""
+        _open_image_stores(self, self.cfg, dict(keep=ds_all, forget=ds_del), device)
+
+    def close_image_stores(self):
+        for store in (self.keep_store, self.forget_store):
+            if store is not None:
+                store.close()                            # (its decode threads; the rows and the counters stay readable)
 
     def evaluate(self, unet, sched, forget_image, step, device):
         """The image part of the reference's log_metrics (delete_celeb.py:376-436, :484-545): `eval_batch_size`
@@ -415,6 +449,7 @@ class _DeleteBase(Task):
             superfactor_decay=d.get("superfactor_decay"))
         shape = (unet.config.in_channels, unet.config.sample_size, unet.config.sample_size)
         ds_all, ds_del = self.datasets(shape)
+        self.open_image_stores(ds_all, ds_del, device)
         it_all = self.keep_batches(ds_all, B, rank, world, device)
         it_del = self.forget_batches(ds_del, B, device)
         n_steps = int(cfg.training_steps) * max(1, len(d.get("img_name") or [1]))
@@ -435,6 +470,7 @@ class _DeleteBase(Task):
         membership = self.membership_metric(unet, sched, ds_all, ds_del, device) if rank == 0 else None
         if ((cfg.get("metrics") or {}).get("membership_loss") or {}).get("plot_params"):
             it_all.close()                               # the curve is the run (delete_celeb.py:444-462 exits here)
+            self.close_image_stores()
             log.close()
             return stepper
         if membership is not None:
@@ -486,6 +522,7 @@ class _DeleteBase(Task):
                 except Exception:
                     pass
         it_all.close()
+        self.close_image_stores()
         if rank == 0 and cfg.get("save_final", True):
             unet.save_pretrained(os.path.join(cfg.output_dir, "unet"))
         return stepper
@@ -495,12 +532,16 @@ class _DeleteBase(Task):
 
     def keep_batches(self, ds_all, B, rank, world, device):
         """The keep batches of the loop, an iterator with close(): the rank's shard decoded / pinned / copied in the background,
-        `depth` batches ahead."""
+        `depth` batches ahead -- or, with image_store on, the sampler's indices alone (prepare_batch gathers the images)."""
+        if self.keep_store is not None:
+            return index_batches(InfiniteSampler(ds_all, rank=rank, num_replicas=world), B, self.keep_store)
         return Prefetcher(ds_all, InfiniteSampler(ds_all, rank=rank, num_replicas=world), B, device=device,
                           workers=int(self.cfg.get("dataloader_num_workers") or 4))
 
     def forget_batches(self, ds_del, B, device):
         """The forget batches of the loop (the forget set is one or a few images repeated: a plain iterator is enough)."""
+        if self.forget_store is not None:
+            return index_batches(self.deletion_sampler(ds_del, B), B, self.forget_store)
         return batches(ds_del, self.deletion_sampler(ds_del, B), B)
 
 
@@ -780,6 +821,9 @@ class DeleteSD(_DeleteBase):
         instead of silently training something else (all at their shipped defaults in config/delete_sd.yaml:99-102,125)."""
         super().check_supported()
         cfg = self.cfg
+        if cfg.get("image_store") is not None:
+            raise NotImplementedError(f"image_store={cfg.get('image_store')!r}: the image store serves the pixel-space tasks; the SD "
+                                      "loop trains on VAE latents, and what it keeps on the device is `latent_cache` (config/delete_sd.yaml)")
         if cfg.get("input_perturbation"):
             raise NotImplementedError(f"input_perturbation={cfg.get('input_perturbation')!r}: perturbed noising with an unperturbed "
                                       "target (delete_sd.py:899-903,:920-926) is not implemented; null in config/delete_sd.yaml")
@@ -1196,6 +1240,7 @@ class TrainUnconditional(Task):
         self.cfg = cfg
 
     compute_dtype = _DeleteBase.compute_dtype
+    train_store = None          # image_store on: the ImageStore of the training set (siss_amd/image_store.py)
 
     def check_supported(self):
         cfg = self.cfg
@@ -1258,6 +1303,8 @@ class TrainUnconditional(Task):
                                weight_decay=opt.weight_decay, grad_accum=ga, ema=ema, mixed_precision=cfg.get("mixed_precision"))
         shape = (unet.config.in_channels, unet.config.sample_size, unet.config.sample_size)
         ds = self.dataset(shape)
+        _open_image_stores(self, cfg, dict(train=ds), device)    # image_store on: train_store, one gather launch per micro-batch
+        store = self.train_store
         num_epochs = int(cfg.num_epochs)
         sampler = EpochSampler(len(ds), B, seed, num_epochs)
         per_epoch = -(-len(sampler) // ga)                       # num_update_steps_per_epoch (:297-299)
@@ -1296,7 +1343,7 @@ class TrainUnconditional(Task):
                 # not per micro-batch (AcceleratedScheduler under accumulate()); lr_pos counts those
                 if stepper._micro == 0:
                     stepper.opt.lr = opt.lr * lr_multiplier(lr_name, lr_pos, warm, total)
-                x0 = torch.stack([ds[i] for i in idx]).to(device, non_blocking=True)
+                x0 = store.images(idx) if store is not None else torch.stack([ds[i] for i in idx]).to(device, non_blocking=True)
                 noise = torch.randn(x0.shape, device=device, generator=g)
                 t = torch.randint(0, T, (x0.shape[0],), device=device, generator=g)
                 stepper.micro_step(x0, noise, t)
@@ -1324,6 +1371,8 @@ class TrainUnconditional(Task):
                 except Exception:
                     pass
             log.close()
+            if store is not None:
+                store.close()
         unet.save_pretrained(os.path.join(cfg.output_dir, (cfg.get("subfolders") or {}).get("unet") or "unet"))
         if ema is not None:
             ema.save_pretrained(os.path.join(cfg.output_dir, (cfg.get("subfolders") or {}).get("unet_ema") or "unet_ema"))
