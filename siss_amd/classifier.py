@@ -206,6 +206,7 @@ class TShirtMetrics:
         self.is_images, self.is_batch_size = int(is_images), int(is_batch_size or is_images)
         self.generator = generator
         self.deletion_steps = None
+        self.extra = None                                # fields added to every record (pipeline.sampler: name and step count)
 
     def __call__(self, global_step):
         t0 = time.perf_counter()
@@ -228,6 +229,7 @@ class TShirtMetrics:
         if len(rec) == 1:
             return None
         rec["seconds"] = time.perf_counter() - t0
+        rec.update(self.extra or {})
         with open(self.out_path, "a") as f:
             f.write(json.dumps(rec) + "\n")
         return rec

@@ -489,5 +489,7 @@ class CLIPIQAScore:
         """(probabilities [n, P], uint8 images [n, H, W, 3]), both on the device, of the decoder's output."""
         return self.model.scores_decoded(img, self._anchors(img.device))
 
+    extra = None                # fields added to every record (pipeline.sampler: the sampler's name and step count)
+
     def record(self, prompt, scores, step):
-        return mn.record_mean(self.out_path, f"clip_iqa_{prompt}", scores, step)
+        return mn.record_mean(self.out_path, f"clip_iqa_{prompt}", scores, step, self.extra)

@@ -357,6 +357,7 @@ class FIDTracker:
     def __init__(self, evaluator, out_path, sample, step_frequency, num_images, batch_size, begin=None, end=None):
         self.evaluator, self.out_path, self.sample, self.begin, self.end = evaluator, out_path, sample, begin, end
         self.step_frequency, self.num_images, self.batch_size = int(step_frequency), int(num_images), int(batch_size)
+        self.extra = None                                # fields added to every record (pipeline.sampler: name and step count)
 
     def __call__(self, global_step):
         if global_step % self.step_frequency:
@@ -375,7 +376,7 @@ class FIDTracker:
         fake, real = int(fc.fake_features_num_samples), int(fc.real_features_num_samples)
         fid = float(self.evaluator.compute(reset=True))
         rec = {"global_step": int(global_step), "fid": fid if math.isfinite(fid) else None, "fake_images": fake, "real_images": real,
-               "seconds": time.perf_counter() - t0}
+               "seconds": time.perf_counter() - t0, **(self.extra or {})}
         print(f"FID: {fid}")
         with open(self.out_path, "a") as f:
             f.write(json.dumps(rec) + "\n")

@@ -280,6 +280,7 @@ class DeletionFraction:
     def __init__(self, classifier, out_path):
         self.classifier, self.out_path = classifier, out_path
         self.deletion_steps = {}
+        self.extra = None                                # fields added to every record (pipeline.sampler: name and step count)
 
     def record(self, prompt, labels, step):
         labels = torch.as_tensor(labels)
@@ -287,6 +288,7 @@ class DeletionFraction:
         rec = {"global_step": int(step), f"deletion_fraction_{prompt}": frac}
         if frac == 0 and prompt not in self.deletion_steps:
             self.deletion_steps[prompt] = rec[f"deletion_steps_{prompt}"] = int(step)
+        rec.update(self.extra or {})
         with open(self.out_path, "a") as f:
             f.write(json.dumps(rec) + "\n")
         return rec

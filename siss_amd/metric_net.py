@@ -136,10 +136,11 @@ def read_state_dict(path, what):
     return sd
 
 
-def record_mean(out_path, key, scores, step):
-    """Append {global_step, key: the mean of the scores in f64 on the host (null when not finite)} to `out_path`; returns the record."""
+def record_mean(out_path, key, scores, step, extra=None):
+    """Append {global_step, key: the mean of the scores in f64 on the host (null when not finite)} to `out_path`; returns the record.
+    extra: fields added to it (the sampler's name and step count when the images came from the opt-in pipeline.sampler)."""
     value = float(torch.as_tensor(scores).detach().cpu().double().mean())
-    rec = {"global_step": int(step), key: value if math.isfinite(value) else None}
+    rec = {"global_step": int(step), key: value if math.isfinite(value) else None, **(extra or {})}
     with open(out_path, "a") as f:
         f.write(json.dumps(rec) + "\n")
     return rec

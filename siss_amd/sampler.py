@@ -81,9 +81,12 @@ class Evaluator:
         return out
 
     @torch.no_grad()
-    def sample_images(self, num_samples, num_inference_steps=None, set_generator=False, x_T=None, noises=None, generator=None):
+    def sample_images(self, num_samples, num_inference_steps=None, set_generator=False, x_T=None, noises=None, generator=None,
+                      sampler=None):
         """Returns [N, H, W, C] float numpy images in [0, 1] (DDPMPipeline output_type='numpy').  generator: a device generator the
-        noise is drawn from (instead of the global one, or the fresh seeded one of set_generator)."""
+        noise is drawn from (instead of the global one, or the fresh seeded one of set_generator).  sampler: a
+        DPMSolverMultistepScheduler (OPT-IN, pipeline.sampler) -- num_inference_steps deterministic DPM-Solver++ updates from x_T instead
+        of the ancestral DDPM chain: the generator is consumed for x_T only, `noises` must be None."""
         u, sch = self.unet, self.noise_scheduler
         dev = u.device
         steps = num_inference_steps or (self.cfg.pipeline.num_inference_steps if self.cfg else 50)
@@ -93,6 +96,16 @@ class Evaluator:
         shape = (num_samples, u.config.in_channels, u.config.sample_size, u.config.sample_size)
         x = torch.randn(shape, device=dev, generator=gen) if x_T is None else x_T.to(dev).float().contiguous()
         u.engine.refresh_weights(cast_shadow=True)
+        if sampler is not None:
+            if noises is not None:
+                raise ValueError("sample_images(sampler=...): the solver is deterministic from x_T and takes no `noises`")
+            from .sd_sampler import cfg_dpmpp_step
+            x = x.clone() if x_T is not None else x          # updated in place; the caller's x_T stays
+            m = torch.empty_like(x)                          # the previous step's x0-prediction
+            for i, t in enumerate(sampler.set_timesteps(steps)):
+                co = sampler.coeffs(i)
+                cfg_dpmpp_step(self._eps(x, t), x, m if co[4] != 0.0 else None, x, m, co, 1.0)
+            return (x / 2 + 0.5).clamp(0, 1).permute(0, 2, 3, 1).cpu().numpy()
         T = sch.config.num_train_timesteps
         for i, t in enumerate(inference_timesteps(T, steps)):
             eps = self._eps(x, t)

@@ -130,3 +130,143 @@ class DDIMScheduler:
         """(sqrt(a_t), sqrt(1 - a_t), sqrt(a_prev), sqrt(1 - a_prev)) as DDIMScheduler.step forms them (f32, eta = 0)."""
         a_t, a_prev = self.alphas(t)
         return tuple(float(v) for v in (a_t ** 0.5, (1 - a_t) ** 0.5, a_prev ** 0.5, (1 - a_prev) ** 0.5))
+
+
+SAMPLER_NAME = "dpmsolver++"      # the one value of pipeline.sampler.name
+
+
+class DPMSolverMultistepScheduler:
+    """DPM-Solver++ multistep of order 1 or 2 ("2M"; Lu et al. 2022), the subset of diffusers' DPMSolverMultistepScheduler an
+    epsilon-prediction VP model is sampled with in 15-25 steps: algorithm_type "dpmsolver++", solver_type "midpoint", the last step
+    to sigma = 0.  OPT-IN (pipeline.sampler) and not the reference's protocol: its samplers are DDPM / DDIM at 50 steps.  The update
+    runs on the device (csrc/dpm_solver.hip siss_cfg_dpmpp_step); this class holds the grid and hands out each step's five
+    coefficients, formed in f64 from alphas_cumprod and rounded once to f32.  Options it does not implement are refused, not ignored.
+
+    With a_s = sqrt(ac[s]), s_s = sqrt(1 - ac[s]), l_s = ln a_s - ln s_s, a step from the grid time s to the next one t has the
+    x0-prediction m = (x - s_s e) / a_s, h = l_t - l_s, E = a_t (1 - exp(-h)), c_x = s_t / s_s, and
+        order 1:  x' = c_x x + E m                                         (DDIM with eta = 0)
+        order 2:  x' = c_x x + E (1 + 1 / (2 r)) m - (E / (2 r)) m1,       r = (l_s - l_s1) / h, m1 the prediction at the previous time s1
+    The last step is x' = m."""
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
+                 solver_order=2, prediction_type="epsilon", thresholding=False, algorithm_type="dpmsolver++", solver_type="midpoint",
+                 lower_order_final=True, euler_at_final=False, use_karras_sigmas=False, use_lu_lambdas=False,
+                 final_sigmas_type="zero", variance_type=None, timestep_spacing="linspace", steps_offset=0,
+                 rescale_betas_zero_snr=False, **unused):
+        if algorithm_type != "dpmsolver++":
+            raise NotImplementedError(f"algorithm_type={algorithm_type!r}: only 'dpmsolver++' (the deterministic data-prediction solver) is implemented")
+        if solver_type != "midpoint":
+            raise NotImplementedError(f"solver_type={solver_type!r}: only 'midpoint' is implemented")
+        if solver_order not in (1, 2):
+            raise NotImplementedError(f"solver_order={solver_order!r}: orders 1 and 2 are implemented")
+        if prediction_type != "epsilon":
+            raise NotImplementedError(f"prediction_type={prediction_type!r}: only epsilon prediction is implemented")
+        if thresholding:
+            raise NotImplementedError("thresholding=true: dynamic thresholding is not implemented")
+        if use_karras_sigmas:
+            raise NotImplementedError("use_karras_sigmas=true is not implemented")
+        if use_lu_lambdas:
+            raise NotImplementedError("use_lu_lambdas=true is not implemented")
+        if euler_at_final:
+            raise NotImplementedError("euler_at_final=true is not implemented")
+        if final_sigmas_type != "zero":
+            raise NotImplementedError(f"final_sigmas_type={final_sigmas_type!r}: only 'zero' (the last step lands on the x0-prediction) is implemented")
+        if not lower_order_final:
+            raise NotImplementedError("lower_order_final=false: the last step to sigma = 0 is of order 1")
+        if variance_type is not None:
+            raise NotImplementedError(f"variance_type={variance_type!r}: learned variances are not implemented")
+        if trained_betas is not None:
+            raise NotImplementedError("trained_betas: only the linear / scaled_linear beta schedules are implemented")
+        if rescale_betas_zero_snr:
+            raise NotImplementedError("rescale_betas_zero_snr=true is not implemented")
+        if timestep_spacing not in ("linspace", "leading"):
+            raise NotImplementedError(f"timestep_spacing={timestep_spacing!r}: 'linspace' and 'leading' are implemented")
+        self.alphas_cumprod = DDPMScheduler(num_train_timesteps, beta_start, beta_end, beta_schedule).alphas_cumprod
+        self.num_train_timesteps = int(num_train_timesteps)
+        self.solver_order, self.timestep_spacing, self.steps_offset = int(solver_order), timestep_spacing, int(steps_offset)
+        self.num_inference_steps, self.timesteps = None, None
+
+    from_config = classmethod(DDIMScheduler.from_config.__func__)             # (keys of other schedulers fall into **unused)
+    from_pretrained = classmethod(DDIMScheduler.from_pretrained.__func__)     # scheduler_config.json on disk, else SD_V1_SCHEDULER
+
+    @classmethod
+    def from_sampler_config(cls, node, base=None, **defaults):
+        """The scheduler a `pipeline.sampler` node asks for, or None for a null node.  `base`: the scheduler_config.json-style dict the
+        betas come from (SD: the checkpoint's), or a DDPMScheduler (the pixel tasks' own noise scheduler); `defaults`: the values
+        of solver_order / timestep_spacing / steps_offset where the node leaves them out.  Any name but 'dpmsolver++' is a
+        ValueError."""
+        if node is None:
+            return None
+        node = dict(node)
+        name = node.pop("name", None)
+        if name != SAMPLER_NAME:
+            raise ValueError(f"pipeline.sampler.name={name!r}: the one sampler that can be asked for is {SAMPLER_NAME!r} (null: the "
+                             "task's own DDPM / DDIM sampling)")
+        extra = set(node) - {"solver_order", "timestep_spacing", "steps_offset"}
+        if extra:
+            raise ValueError(f"pipeline.sampler: unknown keys {sorted(extra)} (name, solver_order, timestep_spacing, steps_offset)")
+        if isinstance(base, DDPMScheduler):
+            c = base.config
+            base = dict(num_train_timesteps=c.num_train_timesteps, beta_start=c.beta_start, beta_end=c.beta_end,
+                        beta_schedule=c.beta_schedule, prediction_type=c.prediction_type)
+        betas = {k: v for k, v in (base or {}).items() if k in ("num_train_timesteps", "beta_start", "beta_end", "beta_schedule",
+                                                                "trained_betas", "prediction_type", "rescale_betas_zero_snr")}
+        return cls(**{**betas, **defaults, **node})
+
+    @property
+    def label(self):
+        """What a record written from this sampler's images carries as "sampler": 'dpmsolver++2m' (order 2), 'dpmsolver++1m'."""
+        return f"{SAMPLER_NAME}{self.solver_order}m"
+
+    def record_fields(self, num_inference_steps):
+        return {"sampler": self.label, "num_inference_steps": int(num_inference_steps)}
+
+    def set_timesteps(self, num_inference_steps):
+        """The K grid times, largest first.  linspace: linspace(0, T - 1, K + 1).round() reversed, without the 0; leading:
+        arange(K + 1) * (T // (K + 1)) reversed, without the 0, + steps_offset (diffusers' DPMSolverMultistepScheduler)."""
+        import numpy as np
+        K, T = int(num_inference_steps), self.num_train_timesteps
+        if not 1 <= K < T:
+            raise ValueError(f"num_inference_steps={K}: must lie in [1, num_train_timesteps={T})")
+        if self.timestep_spacing == "linspace":
+            ts = np.linspace(0, T - 1, K + 1).round()[::-1][:-1]
+        else:
+            ts = (np.arange(0, K + 1) * (T // (K + 1)))[::-1][:-1] + self.steps_offset
+        ts = [int(t) for t in ts]
+        if ts[0] >= T or any(a <= b for a, b in zip(ts, ts[1:])):
+            raise ValueError(f"num_inference_steps={K} with steps_offset={self.steps_offset}: the grid {ts[:3]}... leaves [0, {T}) or "
+                             "repeats a timestep")
+        self.num_inference_steps, self.timesteps = K, ts
+        return ts
+
+    def _asl(self, t):
+        """(a_t, s_t, l_t) in f64 from alphas_cumprod[t] widened to f64."""
+        import math
+        ac = float(self.alphas_cumprod[int(t)].double())
+        a, s = math.sqrt(ac), math.sqrt(1.0 - ac)
+        return a, s, math.log(a) - math.log(s)
+
+    def coeffs(self, i, first=None):
+        """The five f32 coefficients (1 / a_s, s_s / a_s, c_x, c_0, c_1) of step i of the current grid (s = timesteps[i]), as
+        siss_cfg_dpmpp_step takes them: m = (1 / a_s) x - (s_s / a_s) e, x' = c_x x + c_0 m + c_1 m1.  first: this is the first step
+        the caller runs (default: i == 0) -- there is no earlier prediction, so it is of order 1, as is every step of solver_order 1;
+        the last step of the grid is x' = m.  c_1 == 0 exactly when m1 is not needed."""
+        import math
+        import struct
+        ts = self.timesteps
+        if ts is None or not 0 <= i < len(ts):
+            raise ValueError(f"step {i}: set_timesteps first; steps run from 0 to {len(ts or []) - 1}")
+        first = (i == 0) if first is None else bool(first)
+        a_s, s_s, l_s = self._asl(ts[i])
+        if i == len(ts) - 1:
+            cx, c0, c1 = 0.0, 1.0, 0.0
+        else:
+            a_t, s_t, l_t = self._asl(ts[i + 1])
+            h = l_t - l_s
+            E = -a_t * math.expm1(-h)
+            cx, c0, c1 = s_t / s_s, E, 0.0
+            if self.solver_order == 2 and not first:
+                r = (l_s - self._asl(ts[i - 1])[2]) / h
+                c0, c1 = E * (1.0 + 0.5 / r), -0.5 * E / r
+        f32 = lambda v: struct.unpack("f", struct.pack("f", v))[0]
+        return tuple(f32(v) for v in (1.0 / a_s, s_s / a_s, cx, c0, c1))

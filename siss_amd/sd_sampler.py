@@ -12,6 +12,10 @@ diffusers' postprocess.
 The img2img half of that class (``get_timesteps``, ``prepare_latents_img2img``, :241-323) enters the same loop part of the way
 down: ``denoise_injection`` noises an image's latents to the first remaining timestep -- ONE launch from the VAE encoder's posterior
 moments (csrc/injection.hip ``siss_latent_inject``) -- and denoises them back under the prompt.
+
+OPT-IN (``pipeline.sampler``; not the reference's protocol): ``SDSampler(scheduler=DPMSolverMultistepScheduler(...))`` runs the same loop
+with DPM-Solver++ multistep updates (csrc/dpm_solver.hip ``siss_cfg_dpmpp_step``: one launch per step, the same noise norms, one extra
+buffer for the previous x0-prediction) in place of the DDIM step; a suffix of the grid (img2img) starts at order 1.
 """
 import contextlib
 import os
@@ -20,7 +24,7 @@ import torch
 
 from . import lib
 from .sampler import Evaluator
-from .scheduler import DDIMScheduler
+from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler
 
 # CLIPTokenizer("") of the SD v1 checkpoints padded to 77: <|startoftext|>, then <|endoftext|> as the pad token
 SD_V1_UNCOND_IDS = [49406] + [49407] * 76
@@ -55,6 +59,24 @@ def cfg_ddim_step(eps, x, out, coeffs, guidance, clip=0.0, norms=None):
         assert norms is not None and norms.dtype == torch.float32 and norms.is_contiguous() and norms.numel() == 2 * n * nblk
     lib.call("siss_cfg_ddim_step", eps, x, out, n, chw, float(guidance), *coeffs, float(clip), norms if cfg else None, nblk)
     return out
+
+
+def cfg_dpmpp_step(eps, x, m_prev, x_out, m_out, coeffs, guidance, norms=None, nblk=None):
+    """(x_out, m_out) = one DPM-Solver++ multistep update of x under eps_uncond + g (eps_text - eps_uncond): m_out the step's
+    x0-prediction, m_prev the previous step's (None exactly when coeffs[4] == 0: an order-1 or final step).  eps [2n, ...] when
+    guidance > 1 (the partial sums of the two norms go to `norms`, [2, n, ddim_blocks(n, chw)] f32: the bits siss_cfg_ddim_step
+    leaves), else [n, ...].  coeffs: DPMSolverMultistepScheduler.coeffs(i).  x_out may be x, m_out may be m_prev."""
+    n, chw = x.shape[0], x[0].numel()
+    cfg = guidance > 1.0
+    for t in (eps, x, x_out, m_out) + (() if m_prev is None else (m_prev,)):
+        assert t.dtype == torch.float32 and t.is_contiguous()
+    assert eps.numel() == (2 if cfg else 1) * n * chw and x_out.shape == m_out.shape == x.shape
+    assert m_prev is None or m_prev.shape == x.shape
+    nblk = ddim_blocks(n, chw) if nblk is None else int(nblk)
+    if cfg and norms is not None:
+        assert norms.dtype == torch.float32 and norms.is_contiguous() and norms.numel() == 2 * n * nblk
+    lib.call("siss_cfg_dpmpp_step", eps, x, m_prev, x_out, m_out, n, chw, float(guidance), *coeffs, norms if cfg else None, nblk)
+    return x_out, m_out
 
 
 def latent_inject(moments, eps_z, eps_t, scaling, a, b, out=None, nblk=None):
@@ -106,6 +128,11 @@ class SDSampler:
         e = self.text_encoder(self.unconditional_ids.reshape(1, -1))[0].float()
         return e.expand(n_prompts, *e.shape[1:])
 
+    def _ddim_only(self, what):
+        if isinstance(self.scheduler, DPMSolverMultistepScheduler):
+            raise NotImplementedError(f"{what} is defined on the DDIM step: build the SDSampler with a DDIMScheduler, not with "
+                                      f"{self.scheduler.label}")
+
     def _check_call(self, output_type, eta, lp):
         if eta != 0.0:
             raise NotImplementedError(f"eta={eta}: only the deterministic DDIM step (eta = 0) is implemented")
@@ -133,7 +160,10 @@ class SDSampler:
         dev = unet.device
         cfg = guidance_scale > 1.0
         n = x.shape[0]
-        clip = sch.clip_sample_range if sch.clip_sample else 0.0
+        solver = isinstance(sch, DPMSolverMultistepScheduler)       # opt-in: DPM-Solver++ (2M) instead of the DDIM step
+        clip = 0.0 if solver else (sch.clip_sample_range if sch.clip_sample else 0.0)
+        first = sch.timesteps.index(steps[0]) if solver else 0      # a suffix (img2img) starts at order 1: there is no earlier m
+        m = torch.empty_like(x) if solver else None                 # the one extra buffer: the previous step's x0-prediction
         chw = x[0].numel()
         slab = torch.zeros(len(steps), 2, n, ddim_blocks(n, chw), dtype=torch.float32, device=dev) if cfg else None
         unet.engine.refresh_weights(cast_shadow=True)
@@ -143,7 +173,11 @@ class SDSampler:
         try:
             for i, t in enumerate(steps):
                 eps = self._ev._eps(torch.cat([x, x]) if cfg else x, t, emb)
-                cfg_ddim_step(eps, x, x, sch.coeffs(t), guidance_scale, clip, slab[i] if cfg else None)
+                if solver:
+                    co = sch.coeffs(first + i, first=(i == 0))
+                    cfg_dpmpp_step(eps, x, m if co[4] != 0.0 else None, x, m, co, guidance_scale, slab[i] if cfg else None)
+                else:
+                    cfg_ddim_step(eps, x, x, sch.coeffs(t), guidance_scale, clip, slab[i] if cfg else None)
         finally:
             if not self._hold:
                 self._ev = None                          # the captured graphs and their static buffers live for this call only
@@ -263,6 +297,7 @@ class SDSampler:
         defaults: the prompt embedding [1, L, X] optimised (AdamW, row 0's gradient masked) so that the text-conditional noise norm
         at the first target step goes down -- what validation_prompts[0] takes under using_augmented_prompt.  siss_amd/prompt_aug.py."""
         from . import prompt_aug
+        self._ddim_only("aug_prompt")
         return prompt_aug.aug_prompt(self, prompt, height, width, num_inference_steps, guidance_scale, negative_prompt,
                                      num_images_per_prompt, eta, generator, latents, prompt_embeds, negative_prompt_embeds,
                                      target_steps, lr, optim_iters, target_loss, print_optim, optim_epsilon, alpha, return_trace)
@@ -273,6 +308,7 @@ class SDSampler:
         """The reference's get_text_cond_grad (:325-445): per-token L2 norms [L] of the noise norm's gradient with respect to the TEXT
         embedding, averaged over the target steps.  siss_amd/prompt_aug.py."""
         from . import prompt_aug
+        self._ddim_only("get_text_cond_grad")
         return prompt_aug.get_text_cond_grad(self, prompt, height, width, num_inference_steps, guidance_scale, negative_prompt,
                                              num_images_per_prompt, eta, generator, latents, prompt_embeds, negative_prompt_embeds,
                                              target_steps, return_trace)

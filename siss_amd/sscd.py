@@ -217,8 +217,10 @@ class SSCDScore:
         _, u8, scores = self.model.embed_decoded(img, self.mean, self.std, ref=self.reference(img.device))
         return scores, u8
 
+    extra = None                # fields added to every record (pipeline.sampler: the sampler's name and step count)
+
     def record(self, prompt, scores, step):
-        return mn.record_mean(self.out_path, f"sscd_{prompt}", scores, step)
+        return mn.record_mean(self.out_path, f"sscd_{prompt}", scores, step, self.extra)
 
 
 class InjectionScore(SSCDScore):

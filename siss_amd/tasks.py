@@ -90,6 +90,28 @@ def _open_image_stores(task, cfg, datasets, device):
         print(f"[siss_amd] {store.name}: {store.n} images x {store.shape} uint8, {store.nbytes} bytes on {device}")
 
 
+def _inference_steps(cfg):
+    return int(((cfg.get("pipeline") or {}).get("num_inference_steps")) or 50)
+
+
+def _pipeline_sampler(cfg, base=None, **defaults):
+    """`pipeline.sampler` (OPT-IN, null by default): {name: dpmsolver++, solver_order, timestep_spacing, steps_offset} -> the
+    DPMSolverMultistepScheduler the evaluation sampling then runs pipeline.num_inference_steps steps of, or None -- the task's own
+    DDPM / DDIM sampling, launch for launch what it was.  base: where the betas come from (the task's noise scheduler; for SD the
+    checkpoint's scheduler_config.json).  Another name is a ValueError, an option the solver does not implement a
+    NotImplementedError.  Every record written from such samples carries {"sampler", "num_inference_steps"}: they are another
+    protocol than the reference's and must not be mixed with its numbers silently."""
+    from .scheduler import DPMSolverMultistepScheduler
+    solver = DPMSolverMultistepScheduler.from_sampler_config((cfg.get("pipeline") or {}).get("sampler"), base, **defaults)
+    if solver is not None:
+        solver.set_timesteps(_inference_steps(cfg))              # (a step count the grid cannot hold is refused here too)
+    return solver
+
+
+def _sampler_fields(cfg, solver):
+    return None if solver is None else solver.record_fields(_inference_steps(cfg))
+
+
 class _DeleteBase(Task):
     timestep_low = 999          # delete_celeb.py:593 hard-codes randint(999, 1000)
     inf_guard = False
@@ -174,6 +196,7 @@ class _DeleteBase(Task):
                                           "is written in the diffusers layout")
         if cfg.get("mixed_precision") not in (None, "null", "no", "bf16"):
             raise NotImplementedError(f"mixed_precision={cfg.get('mixed_precision')!r}: only null / bf16 (no loss scaler)")
+        _pipeline_sampler(cfg)                                   # pipeline.sampler: a bad name / option is refused before the first step
 
     def optimizer_args(self):
         """(lr, betas, eps, weight_decay) of the AdamW the reference instantiates from cfg.optimizer
@@ -237,7 +260,8 @@ class _DeleteBase(Task):
         ev.load_model(unet, sched)
         n = int(cfg.get("eval_batch_size") or 4)
         steps = int(((cfg.get("pipeline") or {}).get("num_inference_steps")) or 50)
-        imgs = ev.sample_images(n, num_inference_steps=steps, set_generator=True)            # [n, H, W, C] in [0, 1]
+        imgs = ev.sample_images(n, num_inference_steps=steps, set_generator=True,           # [n, H, W, C] in [0, 1]
+                                sampler=_pipeline_sampler(cfg, sched))
         inj = ((cfg.get("metrics") or {}).get("denoising_injections")) or {}
         t_inj = int(inj.get("timestep", 250))
         g = torch.Generator(device=device).manual_seed(self.seed())
@@ -608,12 +632,16 @@ class DeleteCeleb(_DeleteBase):
         def end():                                       # ... dropped with its graphs and static buffers before training goes on
             held.clear()
 
+        solver = _pipeline_sampler(cfg, sched)
+
         def sample(n):
-            imgs = held["ev"].sample_images(n, num_inference_steps=steps, generator=gen)
+            imgs = held["ev"].sample_images(n, num_inference_steps=steps, generator=gen, sampler=solver)
             return torch.from_numpy(imgs).permute(0, 3, 1, 2).to(device)
 
-        return FIDTracker(evaluator, os.path.join(cfg.output_dir, "fid_rank0.jsonl"), sample, fid.step_frequency,
-                          fid.num_imgs_to_generate, fid.batch_size, begin=begin, end=end)
+        tracker = FIDTracker(evaluator, os.path.join(cfg.output_dir, "fid_rank0.jsonl"), sample, fid.step_frequency,
+                             fid.num_imgs_to_generate, fid.batch_size, begin=begin, end=end)
+        tracker.extra = _sampler_fields(cfg, solver)
+        return tracker
 
 
 class DeleteTShirt(_DeleteBase):
@@ -673,11 +701,13 @@ class DeleteTShirt(_DeleteBase):
         tshirt = tshirt.to(device).float()
         steps = int(((cfg.get("pipeline") or {}).get("num_inference_steps")) or 50)
         gen = torch.Generator(device=device).manual_seed(self.seed())
+        solver = _pipeline_sampler(cfg, sched)
 
         def sample(n, batch_size):
             ev = Evaluator(cfg)
             ev.load_model(unet, sched)
-            out = [ev.sample_images(min(batch_size, n - s), num_inference_steps=steps, generator=gen) for s in range(0, n, batch_size)]
+            out = [ev.sample_images(min(batch_size, n - s), num_inference_steps=steps, generator=gen, sampler=solver)
+                   for s in range(0, n, batch_size)]
             return torch.from_numpy(np.concatenate(out)).permute(0, 3, 1, 2).to(device)
 
         inception = None
@@ -687,12 +717,14 @@ class DeleteTShirt(_DeleteBase):
             inception = ((lambda: hydra_lite.instantiate(node, classifier=classifier)) if node
                          else (lambda: InceptionScore(classifier)))
         isc = isc or {}
-        return TShirtMetrics(tshirt, os.path.join(cfg.output_dir, "metrics_rank0.jsonl"), sample,
-                             sampling_steps=cfg.get("sampling_steps") if frac else None,
-                             eval_images=int(cfg.get("eval_images") or 128), eval_batch_size=cfg.get("eval_batch_size"),
-                             inception=inception, is_every=isc.get("step_frequency"),
-                             is_images=int(isc.get("num_imgs_to_generate") or 1024), is_batch_size=isc.get("batch_size"),
-                             generator=torch.Generator().manual_seed(self.seed()))
+        tracker = TShirtMetrics(tshirt, os.path.join(cfg.output_dir, "metrics_rank0.jsonl"), sample,
+                                sampling_steps=cfg.get("sampling_steps") if frac else None,
+                                eval_images=int(cfg.get("eval_images") or 128), eval_batch_size=cfg.get("eval_batch_size"),
+                                inception=inception, is_every=isc.get("step_frequency"),
+                                is_images=int(isc.get("num_imgs_to_generate") or 1024), is_batch_size=isc.get("batch_size"),
+                                generator=torch.Generator().manual_seed(self.seed()))
+        tracker.extra = _sampler_fields(cfg, solver)
+        return tracker
 
 
 class DeleteSD(_DeleteBase):
@@ -1114,9 +1146,21 @@ class DeleteSD(_DeleteBase):
         else:
             raise FileNotFoundError("evaluation needs the empty prompt's embedding: no text_encoder/ in the checkpoint directory "
                                     "(pass allow_synthetic=true for a synthetic one)")
-        self.pipeline = SDSampler(unet, vae=vae, scheduler=DDIMScheduler.from_pretrained(path or None), vae_encoder=self.vae)
+        self.pipeline = SDSampler(unet, vae=vae, scheduler=self._sd_solver() or DDIMScheduler.from_pretrained(path or None),
+                                  vae_encoder=self.vae)
         self._negative_embeds = neg
         return self.pipeline
+
+    def _sd_solver(self):
+        """pipeline.sampler for the validation pipeline: the betas of the checkpoint's scheduler/scheduler_config.json (else the SD v1
+        values), "leading" spacing and that file's steps_offset where the key leaves them out -- the DDIM grid's conventions."""
+        from .scheduler import SD_V1_SCHEDULER
+        fn = os.path.join(str(self.cfg.get("pretrained_model_name_or_path") or ""), "scheduler", "scheduler_config.json")
+        base = SD_V1_SCHEDULER
+        if os.path.isfile(fn):
+            with open(fn) as f:
+                base = json.load(f)
+        return _pipeline_sampler(self.cfg, base, timestep_spacing="leading", steps_offset=int(base.get("steps_offset", 0)))
 
     def evaluate(self, unet, sched, forget_image, step, device):
         """The image and noise-norm part of log_validation (delete_sd.py:170-340): per validation prompt, eval_batches x
@@ -1142,6 +1186,11 @@ class DeleteSD(_DeleteBase):
         steps = int(((cfg.get("pipeline") or {}).get("num_inference_steps")) or 50)
         vp = cfg.get("validation_prompts") or [None]
         g = torch.Generator(device=device).manual_seed(self.seed())
+        from .scheduler import DPMSolverMultistepScheduler
+        fields = sampler.scheduler.record_fields(steps) if isinstance(sampler.scheduler, DPMSolverMultistepScheduler) else None
+        for tracker in (self.sscd, self.clip_iqa):               # pipeline.sampler: every record says which sampler made the images
+            if tracker is not None:
+                tracker.extra = fields
         out_type = "np" if sampler.vae is not None else "latent"
         if self.kmeans is not None:
             from .kmeans import DeletionFraction
@@ -1150,6 +1199,7 @@ class DeleteSD(_DeleteBase):
             out_type = "decoded"
             if self.fraction is None:
                 self.fraction = DeletionFraction(self.kmeans, os.path.join(cfg.output_dir, "metrics_rank0.jsonl"))
+                self.fraction.extra = fields
         if self.sscd is not None:
             if sampler.vae is None:
                 raise FileNotFoundError("metrics.sscd: the validation pipeline has no VAE decoder")
@@ -1195,7 +1245,7 @@ class DeleteSD(_DeleteBase):
                 rec = {"step": step, "prompt": i, "prompt_text": None if p is None else str(p),
                        "timesteps": sampler.scheduler.timesteps[::-1],
                        "text_noise_norm": np.mean(np.asarray(text_n), axis=0)[::-1].tolist(),
-                       "uncond_noise_norm": np.mean(np.asarray(uncond_n), axis=0)[::-1].tolist()}
+                       "uncond_noise_norm": np.mean(np.asarray(uncond_n), axis=0)[::-1].tolist(), **(fields or {})}
                 with open(os.path.join(cfg.output_dir, "noise_norms_rank0.jsonl"), "a") as f:
                     f.write(json.dumps(rec) + "\n")
             if self.injection is not None:
@@ -1257,6 +1307,7 @@ class TrainUnconditional(Task):
         if cfg.get("enable_xformers_memory_efficient_attention"):
             raise NotImplementedError("enable_xformers_memory_efficient_attention=true: xformers is not used here (the attention "
                                       "kernels are this package's own)")
+        _pipeline_sampler(cfg)                                   # pipeline.sampler: a bad name / option is refused before the first step
 
     def dataset(self, shape):
         cfg = self.cfg
@@ -1390,7 +1441,7 @@ class TrainUnconditional(Task):
         ev = self._evaluator
         n = int(cfg.get("eval_batch_size") or 16)
         with (ema.applied(unet) if ema is not None else contextlib.nullcontext()):
-            imgs = ev.sample_images(n)
+            imgs = ev.sample_images(n, sampler=_pipeline_sampler(cfg, sched))
         imgs = (np.clip(imgs, 0, 1) * 255).astype(np.uint8)
         if imgs.shape[-1] == 1:
             imgs = np.repeat(imgs, 3, axis=-1)

@@ -30,12 +30,13 @@ DOCS = {
     'clip_iqa.hip': "The SD image-quality score (delete_sd.py:222-223,:264-267: torchmetrics' CLIPImageQualityAssessment, the OpenAI CLIP RN50\n * image tower against the anchors \"Good photo.\" / \"Bad photo.\"), f32: the convolutions and the q / c_proj projections run on\n * siss_metric_conv, the preprocessing on siss_sscd_preprocess above; these are the anti-aliasing average pool, the attention pool with the\n * query folded into the key projection and the value projection taken after the pooling (no T x E x E product, no token tensor), and\n * the score; sums in f64 or in fixed orders, no atomics.",
     'prompt_grad.hip': "Prompt-embedding gradients and the augmented prompt (data/src/local_sd_pipeline.py:325-445 get_text_cond_grad, :474-663\n * aug_prompt of the reference: autograd through the UNet with respect to encoder_hidden_states, torch.norm, torch.optim.AdamW): a\n * cross-attention site's text gradient dK W_k + dV W_v with f32 output, the fixed-order sum over sites and samples, the noise-norm\n * loss with its cotangent, and the embedding's masked / penalised AdamW step.",
     'injection.hip': "The img2img entry of the SD pipeline (data/src/local_sd_pipeline.py:250-323 prepare_latents_img2img: latent_dist.sample()\n * of the VAE encoder's moments, * scaling_factor, torch.cat to the batch, DDIMScheduler.add_noise at the first timestep): the noised\n * starting latents of the inject-then-denoise check in one streaming launch.",
+    'dpm_solver.hip': "The opt-in DPM-Solver++ (2M) evaluation sampler (siss_amd/scheduler.py DPMSolverMultistepScheduler; no counterpart in the\n * reference, whose samplers are diffusers' DDPMScheduler / DDIMScheduler at 50 steps): classifier-free guidance, the x0-prediction and the\n * first / second order multistep update in one streaming launch per sampling step, with the noise norms of siss_cfg_ddim_step.",
     'latent_cache.hip': "The latent cache of the SD task (siss_amd/latent_cache.py; delete_sd.py:879-888 vae.encode(x).latent_dist.sample() *\n * vae.config.scaling_factor, once per micro-batch and batch): the frozen encoder's posterior moments of the dataset stay on the device and a\n * micro-batch of latents is one gather-and-sample launch over the rows its indices name.",
     'image_store.hip': "The image store of the pixel-space tasks (siss_amd/image_store.py; the DataLoader in front of delete_celeb.py:571-580 and\n * train_unconditional.py:366-372: decode, ToTensor / Normalize, stack and a host-to-device copy of f32 images per micro-batch): the dataset\n * stays on the device as uint8 and a micro-batch of images is one table-gather launch over the rows its indices name.",
     'timeemb.hip': "Sinusoidal timestep embedding (diffusers Timesteps/get_timestep_embedding), TimestepEmbedding MLP and\n * ResnetBlock2D.time_emb_proj linears (M = batch rows), forward and backward.",
 }
 ORDER = ['siss_loss.hip', 'gemm_nt.hip', 'gemm_tn.hip', 'groupnorm.hip', 'conv_small.hip', 'attention.hip', 'attn1h.hip', 'flash_attn.hip', 'transformer.hip',
-         'timeemb.hip', 'elementwise.hip', 'optimizer.hip', 'train_state.hip', 'likelihood.hip', 'membership.hip', 'metric_conv.hip', 'metric_train.hip', 'inception.hip', 'kmeans.hip', 'sscd.hip', 'clip_iqa.hip', 'prompt_grad.hip', 'injection.hip', 'latent_cache.hip', 'image_store.hip', 'f32_path.hip']
+         'timeemb.hip', 'elementwise.hip', 'optimizer.hip', 'train_state.hip', 'likelihood.hip', 'membership.hip', 'metric_conv.hip', 'metric_train.hip', 'inception.hip', 'kmeans.hip', 'sscd.hip', 'clip_iqa.hip', 'prompt_grad.hip', 'injection.hip', 'dpm_solver.hip', 'latent_cache.hip', 'image_store.hip', 'f32_path.hip']
 HEAD = '''/* siss_hip.h -- C ABI of libsiss_hip.so: the MI355X (gfx950) kernels of the SISS unlearning step.
  *
  * GENERATED by tools/gen_header.py from the .hip sources under siss_amd/csrc -- edit the sources, then regenerate.

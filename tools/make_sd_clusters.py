@@ -13,7 +13,11 @@ Label 1 is the cluster with the smaller mean distance of its members to their ce
 of one image), or with --mem-image PATH the cluster whose centre is nearest to that image.
 
     python tools/make_sd_clusters.py --n 256 [--batch 8] [--steps 50] [--prompt "..."] [--from-dir] [--mem-image PATH]
+                                     [--sampler dpmsolver++ [--solver-order 2]]
                                      [--config-name delete_sd] [--config-path config] [key=value ...]
+
+--sampler dpmsolver++ samples with the opt-in DPM-Solver++ (2M) solver (pipeline.sampler of config/delete_sd.yaml) in --steps
+steps instead of DDIM; clustering_info.json then says so ("sampler", "num_inference_steps").
 
 The prompt defaults to validation_prompts[0].  Sampling needs the checkpoint directory (unet/, vae/, text_encoder/ + tokenizer/
 or a .pt prompt embedding), as the validation pass of delete_sd does."""
@@ -115,11 +119,21 @@ def main(argv=None, fit=None):
     ap.add_argument("--from-dir", action="store_true")
     ap.add_argument("--mem-image", default=None)
     ap.add_argument("--n-init", type=int, default=4)
+    ap.add_argument("--sampler", default=None, help="dpmsolver++: the opt-in solver instead of DDIM (pipeline.sampler)")
+    ap.add_argument("--solver-order", type=int, default=2)
     ap.add_argument("overrides", nargs="*")
     a = ap.parse_args(argv)
     import torch
     from siss_amd import hydra_lite
     cfg = hydra_lite.compose(a.config_name, a.config_path, a.overrides)
+    fields = {}
+    if a.sampler is not None:                               # the validation pipeline reads the key; a bad name is refused there
+        cfg.pipeline = dict(cfg.get("pipeline") or {}, num_inference_steps=a.steps,
+                            sampler=dict(name=a.sampler, solver_order=a.solver_order))
+        from siss_amd.scheduler import DPMSolverMultistepScheduler
+        DPMSolverMultistepScheduler.from_sampler_config(cfg.pipeline.sampler)      # (a name / order it does not have: refused now)
+        if not a.from_dir:
+            fields ={"sampler": f"{a.sampler}{a.solver_order}m", "num_inference_steps": a.steps}
     df = cfg.get("data_files") or {}
     img_dir, labels_path, info_path = df.get("img_dir"), df.get("labels_path"), df.get("clustering_info_path")
     if not (img_dir and labels_path and info_path):
@@ -149,7 +163,7 @@ def main(argv=None, fit=None):
     with open(str(labels_path), "w") as f:
         json.dump(labels, f, indent=1)
     with open(str(info_path), "w") as f:
-        json.dump(info, f, indent=1)
+        json.dump({**info, **fields}, f, indent=1)
     KMeansClassifier(centres).save(clf_path)
     print(f"{len(labels)} images of {shape}: frac_deletion {info['frac_deletion']:.4f}, mem_idx {info['mem_idx']}; wrote {labels_path}, "
           f"{info_path}, {clf_path}")
