@@ -24,13 +24,42 @@ struct StepScalars {   // lives in device memory; 16 floats
     float pad3[4];
 };
 
+// A list of stretches of a flat buffer (the TRAINABLE parameters of a subset update), in siss_zero_ranges' form: 16-byte granules, n
+// starts followed by the n + 1 prefix sums of the lengths.  at(i): the buffer granule of granule i of the compacted index space -- a
+// binary search in a table of a few KB (L1 / L2 hits), skipped while a thread's next granule lies in the stretch of its last one.
+// A granule at or beyond `limit` (a table that does not describe the buffer) is reported as -1 and never touched.
+struct RangeWalk {
+    const long* start; const long* pre; long limit; int n, lo;
+    __device__ RangeWalk(const long* tab, int n_, long limit_) : start(tab), pre(tab + n_), limit(limit_), n(n_), lo(0) {}
+    __device__ long at(long i) {
+        if (i < pre[lo] || i >= pre[lo + 1]) {
+            int a = 0, b = n - 1;
+            while (a < b) {
+                const int mid = (a + b + 1) >> 1;
+                if (pre[mid] <= i) a = mid; else b = mid - 1;
+            }
+            lo = a;
+        }
+        const long g = start[lo] + (i - pre[lo]);
+        return g >= 0 && g < limit ? g : -1;
+    }
+};
+
+// RANGES: n is the length of the COMPACTED buffer (4 floats per listed granule): grid, thread -> index map and the order of every
+// sum are those of the whole-buffer pass over a buffer of that length; only the address of granule i differs (tab, of nr stretches,
+// in a buffer of buf_vec granules).  Nothing outside the stretches is read.
+template <bool RANGES>
 __global__ __launch_bounds__(kThreads) void norms_kernel(const float* __restrict__ gx,
                                                          const float* __restrict__ ga, long n,
-                                                         double* __restrict__ partials) {
+                                                         double* __restrict__ partials, const long* __restrict__ tab, int nr,
+                                                         long buf_vec) {
     __shared__ double sh[3 * kThreads / 64];
     double sxx = 0, saa = 0, sxa = 0;
     const long nvec = n / 4;
-    for (long i = (long)blockIdx.x * kThreads + threadIdx.x; i < nvec; i += (long)gridDim.x * kThreads) {
+    RangeWalk walk(tab, nr, buf_vec);
+    for (long k = (long)blockIdx.x * kThreads + threadIdx.x; k < nvec; k += (long)gridDim.x * kThreads) {
+        long i = k;
+        if constexpr (RANGES) { i = walk.at(k); if (i < 0) continue; }
         f32x4_t x = reinterpret_cast<const f32x4_t*>(gx)[i];
         f32x4_t a = reinterpret_cast<const f32x4_t*>(ga)[i];
         float pxx = 0, paa = 0, pxa = 0;
@@ -38,7 +67,7 @@ __global__ __launch_bounds__(kThreads) void norms_kernel(const float* __restrict
         for (int j = 0; j < 4; ++j) { pxx += x[j] * x[j]; paa += a[j] * a[j]; pxa += x[j] * a[j]; }
         sxx += pxx; saa += paa; sxa += pxa;
     }
-    if (blockIdx.x == 0)
+    if (!RANGES && blockIdx.x == 0)                     // (a compacted buffer is whole granules: no tail)
         for (long i = nvec * 4 + threadIdx.x; i < n; i += kThreads) {
             sxx += (double)gx[i] * gx[i]; saa += (double)ga[i] * ga[i]; sxa += (double)gx[i] * ga[i];
         }
@@ -93,11 +122,13 @@ __global__ void scalars_kernel(const double* __restrict__ partials, int nblk, in
 }
 
 // pass 2: g = clip * (g_x - s g_a); torch.optim.AdamW single-tensor update order.
+// RANGES: as in norms_kernel -- the same update on the listed stretches, and no byte of p, m, v, shadow or g_out written outside them.
+template <bool RANGES>
 __global__ __launch_bounds__(kThreads) void recombine_adamw_kernel(
     const float* __restrict__ gx, const float* __restrict__ ga, float* __restrict__ p,
     float* __restrict__ m, float* __restrict__ v, bf16_t* __restrict__ shadow,
     float* __restrict__ g_out, long n, float lr, float beta1, float beta2, float eps, float wd,
-    const StepScalars* __restrict__ sc) {
+    const StepScalars* __restrict__ sc, const long* __restrict__ tab, int nr, long buf_vec) {
     const float s = sc->scale, clip = sc->clip_coef, bc1 = sc->bc1, bc2s = sc->bc2_sqrt;
     const float step_size = lr / bc1;
     const float decay = 1.f - lr * wd;
@@ -111,7 +142,10 @@ __global__ __launch_bounds__(kThreads) void recombine_adamw_kernel(
         pp = __fsub_rn(pp, __fmul_rn(step_size, mm / den));
         return g;
     };
-    for (long i = (long)blockIdx.x * kThreads + threadIdx.x; i < nvec; i += (long)gridDim.x * kThreads) {
+    RangeWalk walk(tab, nr, buf_vec);
+    for (long k = (long)blockIdx.x * kThreads + threadIdx.x; k < nvec; k += (long)gridDim.x * kThreads) {
+        long i = k;
+        if constexpr (RANGES) { i = walk.at(k); if (i < 0) continue; }
         f32x4_t x = reinterpret_cast<const f32x4_t*>(gx)[i], a = reinterpret_cast<const f32x4_t*>(ga)[i];
         f32x4_t pp = reinterpret_cast<f32x4_t*>(p)[i], mm = reinterpret_cast<f32x4_t*>(m)[i],
                 vv = reinterpret_cast<f32x4_t*>(v)[i], gg;
@@ -123,7 +157,7 @@ __global__ __launch_bounds__(kThreads) void recombine_adamw_kernel(
         if (g_out) reinterpret_cast<f32x4_t*>(g_out)[i] = gg;
         if (shadow) reinterpret_cast<u32x2_t*>(shadow)[i] = u32x2_t{pack_bf2(pp[0], pp[1]), pack_bf2(pp[2], pp[3])};
     }
-    if (blockIdx.x == 0)
+    if (!RANGES && blockIdx.x == 0)
         for (long i = nvec * 4 + threadIdx.x; i < n; i += kThreads) {
             float P = p[i], M = m[i], V = v[i];
             const float g = upd(gx[i], ga[i], P, M, V);
@@ -340,7 +374,7 @@ int siss_grad_norms_scale(const float* gx, const float* ga, long n, int mode, fl
     SISS_CHECK_ARG(((uintptr_t)gx | (uintptr_t)ga) % 16 == 0);
     hipStream_t s = (hipStream_t)stream;
     const int nblk = grid_for(n);
-    norms_kernel<<<nblk, kThreads, 0, s>>>(gx, ga, n, partials);
+    norms_kernel<false><<<nblk, kThreads, 0, s>>>(gx, ga, n, partials, nullptr, 0, 0);
     scalars_kernel<<<1, kThreads, 0, s>>>(partials, nblk, mode, knob, max_norm, beta1, beta2,
                                     reinterpret_cast<StepScalars*>(scalars));
     SISS_LAUNCH_RET();
@@ -354,7 +388,7 @@ int siss_grad_norm_partials(const float* gx, const float* ga, long n, double* pa
     SISS_CHECK_ARG(gx && ga && partials && nblk_out && n > 0);
     SISS_CHECK_ARG(((uintptr_t)gx | (uintptr_t)ga) % 16 == 0);
     const int nblk = grid_for(n);
-    norms_kernel<<<nblk, kThreads, 0, (hipStream_t)stream>>>(gx, ga, n, partials);
+    norms_kernel<false><<<nblk, kThreads, 0, (hipStream_t)stream>>>(gx, ga, n, partials, nullptr, 0, 0);
     *nblk_out = nblk;
     SISS_LAUNCH_RET();
 }
@@ -374,9 +408,45 @@ int siss_recombine_clip_adamw(const float* gx, const float* ga, float* p, float*
     SISS_CHECK_ARG(gx && ga && p && m && v && scalars && n > 0);
     SISS_CHECK_ARG(((uintptr_t)gx | (uintptr_t)ga | (uintptr_t)p | (uintptr_t)m | (uintptr_t)v) % 16 == 0);
     SISS_CHECK_ARG(!shadow || (uintptr_t)shadow % 8 == 0);
-    recombine_adamw_kernel<<<grid_for(n), kThreads, 0, (hipStream_t)stream>>>(
+    recombine_adamw_kernel<false><<<grid_for(n), kThreads, 0, (hipStream_t)stream>>>(
         gx, ga, p, m, v, reinterpret_cast<bf16_t*>(shadow), g_out, n, lr, beta1, beta2, eps, wd,
-        reinterpret_cast<const StepScalars*>(scalars));
+        reinterpret_cast<const StepScalars*>(scalars), nullptr, 0, 0);
+    SISS_LAUNCH_RET();
+}
+
+// The pair above on a SUBSET of a flat buffer of n floats (the trainable parameters: SISSStepper(trainable=...)).  tab: DEVICE table
+// in siss_zero_ranges' form -- nranges starts followed by the nranges + 1 prefix sums of the lengths (longs, 16-byte granules;
+// total_granules = the last prefix sum); the stretches must not overlap and must lie inside the buffer.  Pass 1: the three sums run
+// over the listed stretches ONLY (nothing else is read: a NaN in a frozen gradient reaches no scalar), into the same slabs
+// (siss_opt_partials_words), folded into the same scalar block with the same modes.  Grid, thread -> element map and summation order
+// are those of siss_grad_norms_scale over a buffer of 4 * total_granules floats: one stretch covering the whole buffer gives its
+// result bit for bit.  No atomics: bitwise repeatable.
+int siss_grad_norms_scale_ranges(const float* gx, const float* ga, long n, const long* tab, int nranges, long total_granules,
+                                 int mode, float knob, float max_norm, float beta1, float beta2, double* partials, float* scalars,
+                                 void* stream) {
+    SISS_CHECK_ARG(gx && ga && partials && scalars && tab && n > 0 && mode >= 0 && mode <= 2);
+    SISS_CHECK_ARG(nranges > 0 && total_granules > 0 && total_granules <= n / 4);
+    SISS_CHECK_ARG(((uintptr_t)gx | (uintptr_t)ga) % 16 == 0 && (uintptr_t)tab % 8 == 0);
+    hipStream_t s = (hipStream_t)stream;
+    const int nblk = grid_for(4 * total_granules);
+    norms_kernel<true><<<nblk, kThreads, 0, s>>>(gx, ga, 4 * total_granules, partials, tab, nranges, n / 4);
+    scalars_kernel<<<1, kThreads, 0, s>>>(partials, nblk, mode, knob, max_norm, beta1, beta2,
+                                    reinterpret_cast<StepScalars*>(scalars));
+    SISS_LAUNCH_RET();
+}
+
+// Pass 2 on the same table: recombine / clip / AdamW on the listed stretches; p, m, v, shadow and g_out are written there and
+// nowhere else (the frozen parameters, their moments and their bf16 shadow keep every byte).
+int siss_recombine_clip_adamw_ranges(const float* gx, const float* ga, float* p, float* m, float* v, void* shadow, float* g_out,
+                                     long n, const long* tab, int nranges, long total_granules, float lr, float beta1, float beta2,
+                                     float eps, float wd, const float* scalars, void* stream) {
+    SISS_CHECK_ARG(gx && ga && p && m && v && scalars && tab && n > 0);
+    SISS_CHECK_ARG(nranges > 0 && total_granules > 0 && total_granules <= n / 4);
+    SISS_CHECK_ARG(((uintptr_t)gx | (uintptr_t)ga | (uintptr_t)p | (uintptr_t)m | (uintptr_t)v) % 16 == 0 && (uintptr_t)tab % 8 == 0);
+    SISS_CHECK_ARG((!shadow || (uintptr_t)shadow % 8 == 0) && (!g_out || (uintptr_t)g_out % 16 == 0));
+    recombine_adamw_kernel<true><<<grid_for(4 * total_granules), kThreads, 0, (hipStream_t)stream>>>(
+        gx, ga, p, m, v, reinterpret_cast<bf16_t*>(shadow), g_out, 4 * total_granules, lr, beta1, beta2, eps, wd,
+        reinterpret_cast<const StepScalars*>(scalars), tab, nranges, n / 4);
     SISS_LAUNCH_RET();
 }
 

@@ -10,6 +10,7 @@ unchanged.  The fast path is ``siss_amd.step.SISSStepper`` (one dual-cotangent b
 """
 import json
 import os
+import weakref
 
 import torch
 
@@ -48,7 +49,14 @@ class _UNetFn(torch.autograd.Function):
             return tuple(grads)
         dx = torch.empty(sample.shape, dtype=torch.float32, device=sample.device) if want_dx else None
         eng.ps.grads[0].zero_()
-        eng.backward(gout.contiguous().float(), nsets=1, **({"dx": dx} if want_dx else {}))
+        # the products this pass may drop follow the parameters' CURRENT requires_grad flags (what _accumulate_param_grads hands out),
+        # not the selection a SISSStepper left on the engine when it was built
+        prev = eng.wgrads.frozen
+        eng.wgrads.set_frozen(m._flag_subset())
+        try:
+            eng.backward(gout.contiguous().float(), nsets=1, **({"dx": dx} if want_dx else {}))
+        finally:
+            eng.wgrads.set_frozen(prev)
         m._accumulate_param_grads()
         if want_dx:
             grads[2] = dx.to(sample.dtype)
@@ -82,6 +90,7 @@ class UNet2DModel:
         self._fwd_token = None
         ps = self.engine.ps
         self._params = {n: torch.nn.Parameter(ps.p(n)) for n in ps.specs}   # views of the flat master (native layout)
+        self.engine.owner = weakref.ref(self)            # (SISSStepper(trainable="requires_grad") reads the flags above)
 
     # ---- nn.Module-like surface -------------------------------------------------
     def named_parameters(self):
@@ -105,6 +114,24 @@ class UNet2DModel:
             p.requires_grad_(flag)
         return self
 
+    def trainable_names(self):
+        """The names of the parameters whose requires_grad is set, in named_parameters() order: what
+        SISSStepper(trainable="requires_grad") updates."""
+        return [n for n, p in self._params.items() if p.requires_grad]
+
+    def _flag_subset(self):
+        """The requires_grad flags as a siss_amd.trainable.Subset (None: every parameter, or none, takes a gradient -- nothing to drop),
+        rebuilt only when a flag has changed."""
+        names = self.trainable_names()
+        if not names or len(names) == len(self._params):
+            return None
+        if getattr(self, "_flag_key", None) != tuple(names):
+            from .trainable import Subset
+            from .unet import ALIGN
+            ps = self.engine.ps
+            self._flag_key, self._flag_sub = tuple(names), Subset(ps.specs, names, ps.total, ALIGN)
+        return self._flag_sub
+
     def _anchor_node(self):
         """The anchor's gradient-accumulation node: whether the running backward pass executes it tells a full backward
         (parameter gradients wanted) from torch.autograd.grad(out, sample) (the same test torch.utils.checkpoint makes)."""
@@ -114,6 +141,8 @@ class UNet2DModel:
     def _accumulate_param_grads(self):
         ps = self.engine.ps
         for n, p in self._params.items():
+            if not p.requires_grad:                      # a frozen parameter's .grad stays as it is (None), as in torch
+                continue
             sp = ps.specs[n]
             g = ps.grads[0, sp.off:sp.off + sp.numel].view(sp.native_shape)
             if p.grad is None:

@@ -26,14 +26,30 @@ class FlatAdamW:
         self.scalars = torch.zeros(lib.query("siss_opt_scalars_words"), dtype=torch.float32, device=dev)
         self.last_grad = None
 
-    def launch(self, grads, *, scaling_norm=None, eta=None, inf_guard=False, want_grad=False):
-        """Enqueue both passes (no host sync).  grads: [2, P] f32 = (g_x, g_a)."""
+    def launch(self, grads, *, scaling_norm=None, eta=None, inf_guard=False, want_grad=False, ranges=None):
+        """Enqueue both passes (no host sync).  grads: [2, P] f32 = (g_x, g_a).  ranges: (device table, stretches, granules) of a
+        trainable subset (siss_amd.trainable.Subset.table) -- norms, scaling factor, clip and update over the listed stretches
+        only, every other byte of p / m / v / shadow untouched; the caller keeps the table alive (a captured step holds its address)."""
         n = self.p.numel()
         assert grads.dtype == torch.float32 and grads.shape == (2, n) and grads.is_contiguous()
         if eta is not None:
             mode, knob = MODE_ERASEDIFF, float(eta)
         else:
             mode, knob = (MODE_NORM_FIX_INF_GUARD if inf_guard else MODE_NORM_FIX), float(scaling_norm)
+        if ranges is not None:
+            if want_grad and (self.last_grad is None):
+                self.last_grad = torch.zeros_like(self.p)    # (written on the stretches only: zero elsewhere)
+            if not lib.has("siss_recombine_clip_adamw_ranges"):
+                raise RuntimeError("this libsiss_hip.so has no siss_recombine_clip_adamw_ranges: a trainable subset needs the "
+                                   "subset kernels of csrc/optimizer.hip (there is no fall-back to the full update)")
+            tab, nr, granules = ranges
+            assert tab.dtype == torch.int64 and tab.device == self.p.device and tab.numel() == 2 * nr + 1 and n % 4 == 0
+            lib.call("siss_grad_norms_scale_ranges", grads[0], grads[1], n, tab, nr, granules, mode, knob, self.max_grad_norm,
+                     self.betas[0], self.betas[1], self.partials, self.scalars)
+            lib.call("siss_recombine_clip_adamw_ranges", grads[0], grads[1], self.p, self.m, self.v, self.shadow,
+                     self.last_grad if want_grad else None, n, tab, nr, granules, self.lr, self.betas[0], self.betas[1],
+                     self.eps, self.wd, self.scalars)
+            return
         lib.call("siss_grad_norms_scale", grads[0], grads[1], n, mode, knob, self.max_grad_norm,
                  self.betas[0], self.betas[1], self.partials, self.scalars)
         if want_grad and (self.last_grad is None):
@@ -42,13 +58,16 @@ class FlatAdamW:
                  self.last_grad if want_grad else None, n, self.lr, self.betas[0], self.betas[1],
                  self.eps, self.wd, self.scalars)
 
-    def launch_sharded(self, gx_shard, ga_shard, lo, hi, group, *, scaling_norm=None, eta=None, inf_guard=False):
+    def launch_sharded(self, gx_shard, ga_shard, lo, hi, group, *, scaling_norm=None, eta=None, inf_guard=False, ranges=None):
         """The same update on THIS rank's parameter shard [lo, hi) (sharded data-parallel exchange):
         gx_shard / ga_shard are the rank-summed gradients of the shard.  The three norm sums are all-reduced (24 bytes),
         so every rank forms the same scaling factor and clip coefficient as the replicated update; p / m / v / shadow are
         touched on [lo, hi) only -- the caller all-gathers the parameters afterwards."""
         import ctypes
         import torch.distributed as dist
+        if ranges is not None:
+            raise NotImplementedError("FlatAdamW.launch_sharded with a trainable subset: the sharded exchange splits the WHOLE buffer "
+                                      "over the ranks; a subset update takes the all-reduce exchange (launch(ranges=...))")
         n = hi - lo
         assert gx_shard.numel() == n and ga_shard.numel() == n and gx_shard.dtype == torch.float32
         if eta is not None:

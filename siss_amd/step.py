@@ -41,7 +41,13 @@ class SISSStepper:
     def __init__(self, engine: UNetEngine, alphas_cumprod, *, lr, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=1e-2, scaling_norm=None, eta=None, lambd=0.5, train_batch_size,
                  grad_accum=1, max_grad_norm=1.0, loss_fn=SISS, inf_guard=False, process_group=None,
-                 mixed_precision="bf16", superfactor=1.0, superfactor_decay=None):
+                 mixed_precision="bf16", superfactor=1.0, superfactor_decay=None, trainable=None):
+        """trainable: None (every parameter: the reference's protocol), an iterable of parameter names, or "requires_grad" (the flags
+        of the parameters of the UNet2DModel / UNet2DConditionModel that owns the engine).  With a subset the norms, the scaling
+        factor, the clip and the AdamW update run over the trainable tensors only; the rest keep every byte.  The selection (the
+        flags included) is read ONCE, here, and set on the engine (UNetEngine.set_trainable), where it stays until another stepper is
+        built over the engine: flags changed afterwards do not change what this stepper updates.  (A loss.backward() through the
+        class surface drops products by the flags as they are at that backward, not by this selection.)"""
         self.e = engine
         if hasattr(engine, "check_trainable"):
             engine.check_trainable()                # a site without a backward kernel is refused here, not inside the first step
@@ -77,6 +83,10 @@ class SISSStepper:
             SISSStepper._warned_fp32 = True
         self.opt = FlatAdamW(engine.ps.flat, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                              max_grad_norm=max_grad_norm, shadow=None if f32_engine else engine.ps.shadow)
+        self.subset = self._subset(trainable)
+        engine.set_trainable(self.subset)
+        # (the table is built once and lives as long as the stepper: a captured step holds its address)
+        self._ranges = None if self.subset is None else self.subset.table(dev)
         self._micro = 0
         self.last = None
         self._pending = []
@@ -87,8 +97,41 @@ class SISSStepper:
         self.exchange = os.environ.get("SISS_DP_EXCHANGE", "allreduce")      # serial mode: "allreduce" | "sharded"
         self._state_shard = None                # (lo, hi) while AdamW's moments are current on this rank's shard only
         assert self.exchange in EXCHANGES
-        self.set_overlap(self.dp_on and engine.ps.split < engine.ps.total
-                         and os.environ.get("SISS_DP_OVERLAP", "1") != "0")
+        overlap = self.dp_on and engine.ps.split < engine.ps.total and os.environ.get("SISS_DP_OVERLAP", "1") != "0"
+        if self.subset is not None and self.dp_on:
+            # the exchange of a subset step: ONE grouped collective over the trainable pieces after the backward pass
+            if overlap:
+                print("[siss_amd] trainable subset: the overlapped early-tail gradient exchange is off (one grouped all-reduce of the "
+                      "trainable pieces after the backward pass)")
+                overlap = False
+            if self.exchange == "sharded":
+                print("[siss_amd] trainable subset: the sharded exchange splits the whole buffer over the ranks; using the all-reduce")
+                self.exchange = "allreduce"
+        self.set_overlap(overlap)
+
+    def _subset(self, trainable):
+        """SISSStepper(trainable=...) as a siss_amd.trainable.Subset of the engine's flat buffer (None: the full update)."""
+        if trainable is None:
+            return None
+        from .trainable import Subset, from_flags
+        from .unet import ALIGN
+        ps = self.e.ps
+        if isinstance(trainable, str):
+            if trainable != "requires_grad":
+                raise ValueError(f"trainable={trainable!r}: None, an iterable of parameter names or 'requires_grad'")
+            owner = getattr(self.e, "owner", None)
+            model = owner() if owner is not None else None
+            if model is None:
+                raise ValueError("trainable='requires_grad' reads the flags of the UNet2DModel / UNet2DConditionModel that owns the "
+                                 "engine; this engine has none -- pass the parameter names")
+            trainable = from_flags(model.named_parameters())
+        names = list(trainable)
+        if len(set(names)) == len(ps.specs) and all(n in ps.specs for n in names):
+            return None                                 # every parameter: the full update
+        if not lib.has("siss_recombine_clip_adamw_ranges"):
+            raise RuntimeError("this libsiss_hip.so has no siss_recombine_clip_adamw_ranges: a trainable subset needs the subset "
+                               "kernels of csrc/optimizer.hip (there is no fall-back to the full update)")
+        return Subset(ps.specs, names, ps.total, ALIGN)
 
     def set_overlap(self, on, exchange=None):
         """Overlapped (tail all-reduce started from inside the backward) or serial (one exchange after it: RCCL's
@@ -98,6 +141,9 @@ class SISSStepper:
         if exchange is not None:
             assert exchange in EXCHANGES
             self.exchange = exchange
+        if self.subset is not None and self.dp_on and (self.overlap or self.exchange == "sharded"):
+            raise NotImplementedError("a trainable subset exchanges its gradients in one grouped all-reduce after the backward "
+                                      "pass: set_overlap(False, 'allreduce')")
         self.e.on_early_grads_final = self._early_allreduce if self.overlap else None
 
     def _gather_optimizer_state(self):
@@ -121,8 +167,8 @@ class SISSStepper:
         """Measure, don't guess: the overlapped exchange shares the chip with the persistent one-block-per-CU GEMMs of
         the high-resolution backward, and whether RCCL's workgroups cost those kernels more than the overlap hides
         depends on the node.  Times `iters` steps each way (max over ranks) and keeps the faster setting."""
-        if not self.dp_on or self.e.ps.split >= self.e.ps.total:
-            return self.overlap
+        if not self.dp_on or self.e.ps.split >= self.e.ps.total or self.subset is not None:
+            return self.overlap                      # (a subset has one exchange mode: nothing to choose)
         import time
         dist = torch.distributed
         results = {}
@@ -359,7 +405,10 @@ class SISSStepper:
         if self.dp_on and not sharded:
             # the exchange of the step: sum of [g_x ; g_a] over ranks (RCCL over xGMI) -- one flat buffer; with
             # the overlap hook the early-final tail is already in flight and only the head remains
-            if self.overlap and self._pending:
+            if self.subset is not None:
+                # ONE grouped collective: the trainable pieces (merged across small frozen gaps) of both gradient sets
+                allreduce_pieces([g[k, a:b] for k in range(g.shape[0]) for a, b in self.subset.pieces()], self.pg)
+            elif self.overlap and self._pending:
                 split = self.e.ps.split                 # ... the second (and last) grouped collective of the step: the heads
                 self._pending.append(allreduce_pieces([g[k, :split] for k in range(g.shape[0])], self.pg, async_op=True))
                 for w in self._pending:
@@ -382,7 +431,7 @@ class SISSStepper:
             all_gather_params(self.e.ps.flat, lo, hi, self.pg)
             self.e.refresh_weights(cast_shadow=True)
             return
-        self.opt.launch(g, **okw)
+        self.opt.launch(g, ranges=self._ranges, **okw)
         self.e.refresh_weights(lazy=True)               # (the dgrad weight copies: beside the next forward pass)
 
     def step(self, x0, a0, noise, t, u, conditioning=None, erase_target=None):
@@ -414,6 +463,13 @@ class SISSStepper:
             host, done = dev.clone(), None
         return _PendingStats(host, done, keys, sizes, last.get("subscore"), last.get("superfactor") if "superfactor" in last else None,
                              self.opt.stats_from)
+
+    def trainable_counts(self):
+        """(trainable_params, trainable_tensors) of every log line: the parameters the optimizer updates."""
+        if self.subset is not None:
+            return self.subset.params, self.subset.tensors
+        specs = self.e.ps.specs
+        return sum(int(sp.numel) for sp in specs.values()), len(specs)
 
 
 class _PendingStats:

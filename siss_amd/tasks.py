@@ -197,6 +197,52 @@ class _DeleteBase(Task):
         if cfg.get("mixed_precision") not in (None, "null", "no", "bf16"):
             raise NotImplementedError(f"mixed_precision={cfg.get('mixed_precision')!r}: only null / bf16 (no loss scaler)")
         _pipeline_sampler(cfg)                                   # pipeline.sampler: a bad name / option is refused before the first step
+        # deletion.trainable: a malformed entry, an entry that matches no parameter of the configured UNet and a selection of every
+        # parameter (said, then the full update) are settled here, from the parameter names the configuration implies
+        from .trainable import select
+        pats = self.trainable_patterns()
+        if pats is not None:
+            select(self.unet_param_names(), pats)
+
+    # -- deletion.trainable: null | [regular expressions over the diffusers parameter names] (OPT-IN; siss_amd/trainable.py) -----------
+    def trainable_patterns(self):
+        """The compiled expressions of deletion.trainable, or None (absent / null: every parameter, the reference's protocol).  Refused:
+        anything but a list, an empty list, an entry that does not compile."""
+        from .trainable import parse_patterns
+        return parse_patterns((self.cfg.get("deletion") or {}).get("trainable"))
+
+    unet_engine = "siss_amd.unet.UNetEngine"
+
+    def unet_config_source(self):
+        """(config.json of the checkpoint load_unet() will read, or None; the configuration class): load_unet()'s own choice."""
+        cfg = self.cfg
+        path = cfg.get("checkpoint_path")
+        if path and os.path.isdir(str(path)):
+            sub = (cfg.get("subfolders") or {}).get("unet")
+            d = os.path.join(str(path), sub) if sub else str(path)
+            if not os.path.exists(os.path.join(d, "config.json")) and os.path.exists(os.path.join(str(path), "unet")):
+                d = os.path.join(str(path), "unet")                      # (UNet2DModel.from_pretrained's fall-back)
+            return os.path.join(d, "config.json"), UNet2DConfig
+        return None, UNet2DConfig
+
+    def unet_param_names(self):
+        """The diffusers parameter names of the UNet load_unet() will build, from its configuration alone (no device, no weights):
+        the checkpoint's config.json when the checkpoint is on disk, else cfg.unet or the task's default architecture."""
+        import importlib
+        fn, cls = self.unet_config_source()
+        if fn is not None:
+            ucfg = cls.from_json(fn)
+        else:
+            raw = {k: v for k, v in (self.cfg.get("unet") or {}).items() if not k.startswith("_")}
+            ucfg = cls.from_dict(raw) if raw else self.default_unet()
+        mod, name = self.unet_engine.rsplit(".", 1)
+        return getattr(importlib.import_module(mod), name).param_names(ucfg)
+
+    def trainable_names(self, unet):
+        """The parameter names deletion.trainable selects in the loaded `unet` (None: the full update -- no key, or a selection of
+        everything).  check_supported() has refused an unmatched entry already; this is the same selection on the model's own names."""
+        from .trainable import select
+        return select([n for n, _ in unet.named_parameters()], self.trainable_patterns(), announce=False)
 
     def optimizer_args(self):
         """(lr, betas, eps, weight_decay) of the AdamW the reference instantiates from cfg.optimizer
@@ -470,7 +516,7 @@ class _DeleteBase(Task):
             loss_fn=d.loss_fn, inf_guard=self.inf_guard, process_group=pg,
             mixed_precision=cfg.get("mixed_precision"),
             superfactor=float((d.loss_params or {}).get("superfactor", 1.0)),
-            superfactor_decay=d.get("superfactor_decay"))
+            superfactor_decay=d.get("superfactor_decay"), trainable=self.trainable_names(unet))
         shape = (unet.config.in_channels, unet.config.sample_size, unet.config.sample_size)
         ds_all, ds_del = self.datasets(shape)
         self.open_image_stores(ds_all, ds_del, device)
@@ -503,6 +549,7 @@ class _DeleteBase(Task):
         def write_log(handle, meta):
             st = handle.get()
             st["global_step"], st["lr"], st["elapsed_s"] = meta          # (elapsed: stamped when the step was queued)
+            st["trainable_params"], st["trainable_tensors"] = stepper.trainable_counts()
             log.write(json.dumps(st) + "\n")
             log.flush()
             if rank == 0:
@@ -843,6 +890,14 @@ class DeleteSD(_DeleteBase):
         m.engine.init_random(seed=self.seed())
         print(f"[siss_amd] allow_random_init: {path!r}/unet not on disk, RANDOM-INIT weights of the same architecture")
         return m
+
+    unet_engine = "siss_amd.unet_cond.UNetCondEngine"
+
+    def unet_config_source(self):
+        path = self.cfg.get("pretrained_model_name_or_path")
+        if path and os.path.isdir(os.path.join(str(path), "unet")):
+            return os.path.join(str(path), "unet", "config.json"), UNet2DConditionConfig
+        return None, UNet2DConditionConfig
 
     def load_scheduler(self):
         # the SD v1 scheduler_config.json: scaled-linear betas 0.00085 -> 0.012 (delete_sd.py:412)

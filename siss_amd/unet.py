@@ -225,6 +225,11 @@ class UNetEngine:
     sparse_fill = True
     sparse_min_floats = 16384  # ... stretches of at least this many floats (the rest is simply filled)
     pair_min_rows = 280000     # ... of at least this many reduction rows per set (CelebA-HQ B = 16: the 256 x 256 level)
+    # With a trainable SUBSET (set_trainable: SISSStepper(trainable=...)) a weight-gradient product whose every output -- dW, dbias,
+    # dbias2 -- lies in frozen stretches of the gradient buffer is dropped: neither queued, paired nor launched (WgradQueue.job).
+    # False: the backward pass is launch for launch the full update's, and the optimizer simply never reads the frozen part.
+    # What it buys is measured by tools/bench_trainable.py (docs/experiments.md).
+    skip_frozen_wgrad = True
 
     def __init__(self, cfg: UNet2DConfig, device="cuda", dtype=torch.bfloat16, f32_fused=False):
         """dtype = torch.float32: the f32 PARITY MODE (`mixed_precision: null` of the reference's YAMLs; csrc/f32_path.hip) -- every
@@ -264,6 +269,7 @@ class UNetEngine:
         self.on_early_grads_final = None
         self._side, self._side_mark = None, None
         self.wgrads = WgradQueue(self)
+        self.trainable = None                               # siss_amd.trainable.Subset, or None: every parameter
         self._prep_pending, self._wT_stale = False, False
         self._fill_key, self._fill_plan, self._fill_plans, self._fill_tables = None, None, {}, []
         self._vjp, self._dx, self._vjp_sums = False, None, None
@@ -312,6 +318,15 @@ class UNetEngine:
             self._mha_check(S, D, training=True)
 
     # ------------------------------------------------------------------ parameters
+    @classmethod
+    def param_names(cls, cfg):
+        """The diffusers parameter names of a configuration, in named_parameters() order, without building an engine (no device, no
+        library): what a task needs to judge deletion.trainable before it loads anything."""
+        e = object.__new__(cls)
+        e.cfg, e.ps = cfg, ParamStore()
+        e._declare_params()
+        return list(e.ps.specs)
+
     def _early_blocks(self):
         """Down blocks whose backward runs before the (long) high-resolution tail: the lower half of the ladder."""
         n = len(self.cfg.block_out_channels)
@@ -760,6 +775,8 @@ class UNetEngine:
         wq = self.wgrads
         job = wq.job(dy.data, dy.c, x.data, ldx or getattr(x, "ld", x.c), dW_view, co, ci, shifts, coffs, nsets=self.nsets,
                      rows_per_set=rows_per_set, row_begin=rb, row_end=re, x_set_rows=x_set_rows, dbias=dbias, dbias2=dbias2)
+        if job is None:                                 # every output frozen: dropped
+            return
         if self.group_rows and re - rb <= self.group_rows and isinstance(dy, Act):
             wq.queue(job, hold=dy)
             wq.flush_if_full()
@@ -954,7 +971,9 @@ class UNetEngine:
                 if not self._vjp:
                     job = self.wgrads.job(dyt, C, xin, C, dW, C, C, nsets=ns, rows_per_set=si * S, row_begin=0, row_end=si * S,
                                           x_set_rows=si * S if B == nb else 0, dbias=ps.g(wname + ".bias", gb))
-                    if self.group_attn and self.group_rows:
+                    if job is None:
+                        pass
+                    elif self.group_attn and self.group_rows:
                         self.wgrads.queue(job)          # (its operands are buffers of this site's own: `own` above)
                     else:
                         self.wgrads.launch(job, ops._nsplits(tiles, 1, ns, si * S, False))
@@ -1050,7 +1069,9 @@ class UNetEngine:
             if not self._vjp:
                 job = self.wgrads.job(dqkv, 3 * C, hn, C, dW, 3 * C, C, nsets=ns, rows_per_set=si * S, row_begin=0, row_end=si * S,
                                       x_set_rows=si * S if B == nb else 0, dbias=ps.g(pre + ".to_q.bias", gb))
-                if grouped:
+                if job is None:                          # to_q, to_k and to_v all frozen
+                    pass
+                elif grouped:
                     self.wgrads.queue(job)
                     self.wgrads.flush_if_full()
                 else:
@@ -1205,7 +1226,10 @@ class UNetEngine:
             dW4 = self._buf((pre if queued else "up") + ".dW4", (self.nsets, 4, 4, C, C))
             dWt, nsets_ = ps.grads[gb:, ps.specs[wname].off:], self.nsets
             fold = lambda: lib.call("siss_upsample_phase_wgrad_fold", dW4, dWt, ps.total, nsets_, C, C)
-            if not self._vjp:
+            # (the phase products write a scratch; what they produce is the fold's target and the bias gradient)
+            if not self._vjp and self.wgrads.all_frozen((dWt, 9 * C * C, ps.total, nsets_), (ps.g(pre + ".conv.bias", gb), C, ps.total, nsets_)):
+                self.wgrads.dropped += 4
+            elif not self._vjp:
                 dW4.zero_()
                 # (the scratch's set stride is 16 C^2, the bias gradient's the flat buffer's)
                 jobs = [self.wgrads.job(z.data[:, plane * C:], 4 * C, x.data, ldx, dW4[:, plane], C, C, phase_shifts(plane), [0] * 4,
@@ -1420,7 +1444,9 @@ class UNetEngine:
                 job = self.wgrads.job(col.data, kc, a.data, c0, ps.grads[gb:, ps.specs["conv_out.weight"].off:], 9 * co, c0,
                                       nsets=self.nsets, rows_per_set=rows_per_set, row_begin=rb, row_end=re, nsplits=0,
                                       x_set_rows=rows_per_set if a.n == nb else 0)
-                if self.pair_top and not self.f32 and re - rb >= self.pair_min_rows:
+                if job is None:
+                    pass
+                elif self.pair_top and not self.f32 and re - rb >= self.pair_min_rows:
                     self.wgrads.wait_for_partner(job, col)
                 else:
                     self.wgrads.launch(job, ops._nsplits(1, 1, self.nsets, re - rb, False))
@@ -1471,7 +1497,15 @@ class UNetEngine:
         return (self.group_rows, self.group_max, self.group_attn, self.pair_top, self.pair_min_rows, self.fold_shortcut, self.sc_in_gn,
                 self.sc_in_gn_min_px, self.subpixel_up,
                 self.subpixel_min_px, self.subpixel_queue, self.fused_attn, self.sparse_min_floats, self.wgrad_side, self.side_follow,
-                self.on_early_grads_final is not None)
+                self.on_early_grads_final is not None,
+                self.skip_frozen_wgrad and self.trainable is not None and self.trainable.signature())
+
+    def set_trainable(self, subset):
+        """subset: siss_amd.trainable.Subset over this engine's ParamStore (None: every parameter).  The weight-gradient queue drops
+        the products that only feed frozen stretches (skip_frozen_wgrad); forward, data gradients, zero_grad and the gradients fused
+        kernels form on the side (GroupNorm / LayerNorm affine, bias sums inside other launches) are unchanged."""
+        self.trainable = subset
+        self.wgrads.set_frozen(subset)
 
     def _overwritten(self):
         """The drained overwrite log as sorted (first float, floats) stretches of the gradient buffer; None if unusable."""

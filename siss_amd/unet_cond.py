@@ -162,7 +162,9 @@ class UNetCondEngine(UNetEngine):
         tiles = (-(-n_out // 128)) * (-(-k_in // 128))
         job = self.wgrads.job(dy, n_out, xin, k_in, dW, n_out, k_in, nsets=ns, rows_per_set=rps, row_begin=0, row_end=rps,
                               x_set_rows=rps if rows_x == rows2 else 0, dbias=ps.g(wname + ".bias", gb) if bias else None)
-        if self.group_attn and self.group_rows:
+        if job is None:                                 # weight and bias frozen: no product, the data gradient below as ever
+            pass
+        elif self.group_attn and self.group_rows:
             # queued for a grouped launch: dy lives in a per-site buffer (see transformer())
             self.wgrads.queue(job)
             self.wgrads.flush_if_full()

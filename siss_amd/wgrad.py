@@ -22,6 +22,8 @@ class WgradQueue:
         self.eng, self.launcher = eng, launcher
         self.side_busy, self.side_held, self.side_release = False, {}, []
         self.side_phase = False
+        self.frozen = None                               # siss_amd.trainable.Subset: the stretches of a gradient set somebody reads
+        self.issued = self.dropped = 0                   # products described and kept / dropped since the engine was built
         self.reset()
 
     def reset(self):
@@ -37,12 +39,40 @@ class WgradQueue:
     def _call(self, name, *args, **kw):
         return (self.launcher or lib.call)(name, *args, **kw)
 
+    # ------------------------------------------------------------------ products nobody reads
+    def set_frozen(self, subset):
+        """subset (siss_amd.trainable.Subset, or None: every parameter is read): the optimizer reads the listed stretches of each
+        gradient set and nothing else, so a product whose EVERY output lies outside them is dropped by job() -- while the engine's
+        skip_frozen_wgrad is set."""
+        self.frozen = subset
+
+    def all_frozen(self, *outputs):
+        """outputs: (tensor or address or None, floats per set, floats between sets, sets).  True when each is a window of the
+        engine's gradient buffer that no listed stretch touches, in every set (an output anywhere else -- a scratch -- is read by
+        somebody: False)."""
+        fz, g = self.frozen, self.eng.ps.grads
+        if fz is None or not getattr(self.eng, "skip_frozen_wgrad", True):
+            return False
+        base, total, nfloats = g.data_ptr(), g.shape[1], g.numel()
+        for t, n, stride, sets in outputs:
+            a = t.data_ptr() if torch.is_tensor(t) else t
+            if not a:
+                continue
+            for s in range(sets):
+                off, rem = divmod(a - base, 4)
+                off += s * stride
+                if rem or off < 0 or off + n > nfloats or off // total != (off + n - 1) // total or not fz.is_frozen(off % total, n):
+                    return False
+        return True
+
     # ------------------------------------------------------------------ describing a product
     def job(self, Y, ldy, X, ldx, dW, N, C, shifts=(0,), coffs=(0,), *, nsets, rows_per_set, row_begin, row_end, x_set_rows,
             nsplits=None, dbias=None, dbias2=None, set_stride=None, bias_set_stride=0):
         """dW[set] (+)= Y^T X over rows [row_begin, row_end) of every set, as a siss_tn_job.  Y, X, dW, dbias, dbias2: tensors or
         raw addresses.  nsplits None: the library chooses -- and overwrites instead of accumulating in the first micro-batch of
-        a step (wgrad_overwrite).  set_stride None: dW is a window of the flat gradient buffer."""
+        a step (wgrad_overwrite).  set_stride None: dW is a window of the flat gradient buffer.  Returns None for a product that is
+        DROPPED: dW, dbias and dbias2 all lie in frozen stretches of the gradient buffer (set_frozen) -- the caller neither queues,
+        pairs nor launches it."""
         eng = self.eng
         addr = lambda t: t.data_ptr() if torch.is_tensor(t) else t
         pad9 = lambda v: (lib.I * 9)(*v, *([0] * (9 - len(v))))
@@ -55,6 +85,12 @@ class WgradQueue:
                       zero_page=zp.data_ptr(), dbias=addr(dbias), dbias2=addr(dbias2), shifts=pad9(shifts), coffs=pad9(coffs),
                       bias_set_stride=bias_set_stride)
         j.operands = (Y, X, dW, dbias, dbias2)            # (the job holds addresses: the tensors live as long as it does)
+        if self.frozen is not None:
+            bs = bias_set_stride or j.set_stride
+            if self.all_frozen((j.dW, len(shifts) * N * C, j.set_stride, nsets), (j.dbias, N, bs, nsets), (j.dbias2, N, bs, nsets)):
+                self.dropped += 1
+                return None
+        self.issued += 1
         return j
 
     # ------------------------------------------------------------------ running one
