@@ -125,6 +125,14 @@ def _load_yaml(config_path, name):
         return yaml.safe_load(f) or {}
 
 
+def _flow_mapping(val):
+    """Hydra's override grammar takes `{rank:4,targets:[attn]}` as a mapping; YAML's flow mapping wants `key: value`.  The space is
+    put in after every key of a value that is written as a mapping."""
+    if val.lstrip().startswith("{"):
+        return re.sub(r"([{,]\s*[\w.\-]+):(?=\S)", r"\1: ", val)
+    return val
+
+
 def compose(config_name, config_path="config", overrides=()):
     """Hydra-style composition: ``defaults`` first (in order), ``_self_`` where listed (last if absent)."""
     raw = _load_yaml(config_path, config_name)
@@ -151,7 +159,7 @@ def compose(config_name, config_path="config", overrides=()):
             if cur.get(p) is None:            # a null placeholder (metrics.fraction_deletion: null) takes children like an absent key
                 cur[p] = {}
             cur = cur[p]
-        cur[parts[-1]] = yaml.safe_load(val)
+        cur[parts[-1]] = yaml.safe_load(_flow_mapping(val))
     cfg = Cfg(merged)
     object.__setattr__(cfg, "_raw", merged)
     return cfg

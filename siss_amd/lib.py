@@ -73,7 +73,8 @@ F32_SAME = {"siss_zero_ranges", "siss_upsample_phase_wgrad_fold", "siss_timestep
             "siss_ddpm_step", "siss_cfg_ddim_step", "siss_cfg_dpmpp_step", "siss_pflow_drift_div", "siss_slab_rowsum_f64", "siss_rk_combine", "siss_rk_norm", "siss_pair_noise", "siss_pair_sqerr", "siss_metric_conv", "siss_metric_maxpool3", "siss_inc_avgpool", "siss_inc_global_avg", "siss_inc_preprocess", "siss_fid_stats_update", "siss_kmeans_decoded", "siss_kmeans_finalize", "siss_kmeans_assign", "siss_kmeans_update", "siss_sscd_preprocess", "siss_sscd_gem", "siss_sscd_normalize_score", "siss_clipiqa_avgpool", "siss_clipiqa_token_mean", "siss_clipiqa_fold_query", "siss_clipiqa_scores", "siss_clipiqa_pool", "siss_clipiqa_head_value", "siss_clipiqa_score", "siss_quick_gelu_f32", "siss_grad_norms_scale", "siss_grad_norm_partials", "siss_grad_scalars", "siss_recombine_clip_adamw",
             "siss_grad_norms_scale_ranges", "siss_recombine_clip_adamw_ranges",
             "siss_grad_norm_single", "siss_clip_adamw_ema", "siss_ema_advance", "siss_ema_step", "siss_swap_f32",
-            "siss_ctx_dgrad", "siss_ctx_reduce", "siss_noise_norm_cot", "siss_prompt_embed_update", "siss_latent_inject", "siss_latent_sample", "siss_image_gather"}
+            "siss_ctx_dgrad", "siss_ctx_reduce", "siss_noise_norm_cot", "siss_prompt_embed_update", "siss_latent_inject", "siss_latent_sample", "siss_image_gather",
+            "siss_lora_project", "siss_lora_merge"}
 for _b, _f in F32_ENTRY.items():          # the header's promise "same argument lists", checked once instead of assumed
     if SIGNATURES[_b] != SIGNATURES[_f]:
         raise TypeError(f"{_f} does not have the argument types of {_b} in {HEADER}")

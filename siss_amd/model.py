@@ -178,6 +178,29 @@ class UNet2DModel:
     def load_state_dict(self, sd, strict=True):
         self.engine.load_state_dict(sd, strict)
 
+    # ---- LoRA adapters (siss_amd/lora.py) -----------------------------------------
+    def load_lora(self, directory, scale=1.0):
+        """Merge the adapter saved under `directory` (LoRAState.save) into the loaded weights: W0 + scale * (alpha / r) B A on every
+        target, through siss_lora_merge, and refresh the operand copies -- the adapter evaluated on the stock checkpoint.  The
+        weights as they are NOW are kept as W0 until unload_lora().  Returns the LoRAState."""
+        from .lora import LoRAState
+        if getattr(self, "_lora", None) is not None:
+            raise RuntimeError("load_lora: an adapter is merged already -- unload_lora() first")
+        st = LoRAState.load(self.engine, directory)
+        st.merge(scale)
+        self.engine.refresh_weights()
+        self._lora = st
+        return st
+
+    def unload_lora(self):
+        """Put W0 back, bit for bit, on the targets of the adapter load_lora() merged."""
+        st = getattr(self, "_lora", None)
+        if st is None:
+            raise RuntimeError("unload_lora: no adapter is merged")
+        st.merge(0.0)
+        self.engine.refresh_weights()
+        self._lora = None
+
     @classmethod
     def from_pretrained(cls, path, subfolder=None, device="cuda", compute_dtype=torch.bfloat16, **unused):
         from safetensors.torch import load_file

@@ -41,14 +41,26 @@ class SISSStepper:
     def __init__(self, engine: UNetEngine, alphas_cumprod, *, lr, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=1e-2, scaling_norm=None, eta=None, lambd=0.5, train_batch_size,
                  grad_accum=1, max_grad_norm=1.0, loss_fn=SISS, inf_guard=False, process_group=None,
-                 mixed_precision="bf16", superfactor=1.0, superfactor_decay=None, trainable=None):
+                 mixed_precision="bf16", superfactor=1.0, superfactor_decay=None, trainable=None, lora=None):
         """trainable: None (every parameter: the reference's protocol), an iterable of parameter names, or "requires_grad" (the flags
         of the parameters of the UNet2DModel / UNet2DConditionModel that owns the engine).  With a subset the norms, the scaling
         factor, the clip and the AdamW update run over the trainable tensors only; the rest keep every byte.  The selection (the
         flags included) is read ONCE, here, and set on the engine (UNetEngine.set_trainable), where it stays until another stepper is
         built over the engine: flags changed afterwards do not change what this stepper updates.  (A loss.backward() through the
-        class surface drops products by the flags as they are at that backward, not by this selection.)"""
+        class surface drops products by the flags as they are at that backward, not by this selection.)
+
+        lora: None, or a siss_amd.lora.LoRAState over this engine (opt-in, not the reference's protocol): the base weights stay frozen
+        and the optimizer runs on the adapters' flat buffer -- after the backward pass the weight gradients of the targets are
+        projected to (dA, dB) of both sets, the norms / scaling factor / clip / AdamW run in adapter space, and one merge pass rewrites
+        the targets' stretches of the master and its shadow.  Only the targets' weight-gradient products run; no full-size m / v."""
         self.e = engine
+        self.lora = lora
+        if lora is not None:
+            if trainable is not None:
+                raise ValueError("SISSStepper(lora=..., trainable=...): a LoRA run trains the adapters of its targets and nothing else")
+            if lora.engine is not engine:
+                raise ValueError("SISSStepper(lora=...): the LoRAState was built over another engine")
+            trainable = list(lora.names)
         if hasattr(engine, "check_trainable"):
             engine.check_trainable()                # a site without a backward kernel is refused here, not inside the first step
         dev = engine.device
@@ -81,12 +93,17 @@ class SISSStepper:
                           "match an fp32 run to bf16 tolerance; UNetEngine(cfg, device, dtype=torch.float32) is the f32 path",
                           RuntimeWarning, stacklevel=2)
             SISSStepper._warned_fp32 = True
-        self.opt = FlatAdamW(engine.ps.flat, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
-                             max_grad_norm=max_grad_norm, shadow=None if f32_engine else engine.ps.shadow)
+        if lora is None:
+            self.opt = FlatAdamW(engine.ps.flat, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                 max_grad_norm=max_grad_norm, shadow=None if f32_engine else engine.ps.shadow)
+        else:
+            # the adapters' buffer is the optimizer's: m / v of L floats, no shadow (the merge writes the operand copies)
+            self.opt = FlatAdamW(lora.p, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
+                                 shadow=None)
         self.subset = self._subset(trainable)
         engine.set_trainable(self.subset)
         # (the table is built once and lives as long as the stepper: a captured step holds its address)
-        self._ranges = None if self.subset is None else self.subset.table(dev)
+        self._ranges = None if self.subset is None or lora is not None else self.subset.table(dev)
         self._micro = 0
         self.last = None
         self._pending = []
@@ -98,7 +115,16 @@ class SISSStepper:
         self._state_shard = None                # (lo, hi) while AdamW's moments are current on this rank's shard only
         assert self.exchange in EXCHANGES
         overlap = self.dp_on and engine.ps.split < engine.ps.total and os.environ.get("SISS_DP_OVERLAP", "1") != "0"
-        if self.subset is not None and self.dp_on:
+        if lora is not None and self.dp_on:
+            # the exchange of a LoRA step: ONE all-reduce of the adapters' [2, L] gradient pair after the projection (linear: the same sum)
+            if overlap:
+                print("[siss_amd] lora: the overlapped early-tail gradient exchange is off (one all-reduce of the adapter gradients "
+                      "after the backward pass)")
+                overlap = False
+            if self.exchange == "sharded":
+                print("[siss_amd] lora: the sharded exchange splits the whole buffer over the ranks; using the all-reduce")
+                self.exchange = "allreduce"
+        elif self.subset is not None and self.dp_on:
             # the exchange of a subset step: ONE grouped collective over the trainable pieces after the backward pass
             if overlap:
                 print("[siss_amd] trainable subset: the overlapped early-tail gradient exchange is off (one grouped all-reduce of the "
@@ -128,6 +154,8 @@ class SISSStepper:
         names = list(trainable)
         if len(set(names)) == len(ps.specs) and all(n in ps.specs for n in names):
             return None                                 # every parameter: the full update
+        if self.lora is not None:                       # (the adapter-space update needs no subset kernels: the full ones on lora.p)
+            return Subset(ps.specs, names, ps.total, ALIGN)
         if not lib.has("siss_recombine_clip_adamw_ranges"):
             raise RuntimeError("this libsiss_hip.so has no siss_recombine_clip_adamw_ranges: a trainable subset needs the subset "
                                "kernels of csrc/optimizer.hip (there is no fall-back to the full update)")
@@ -141,6 +169,9 @@ class SISSStepper:
         if exchange is not None:
             assert exchange in EXCHANGES
             self.exchange = exchange
+        if self.lora is not None and self.dp_on and (self.overlap or self.exchange == "sharded"):
+            raise NotImplementedError("a LoRA step exchanges its adapter gradients in one all-reduce after the backward pass: "
+                                      "set_overlap(False, 'allreduce')")
         if self.subset is not None and self.dp_on and (self.overlap or self.exchange == "sharded"):
             raise NotImplementedError("a trainable subset exchanges its gradients in one grouped all-reduce after the backward "
                                       "pass: set_overlap(False, 'allreduce')")
@@ -278,6 +309,8 @@ class SISSStepper:
         for dst, src in zip((self.opt.p, self.opt.m, self.opt.v, self.opt.scalars), saved):
             dst.copy_(src)
         self.superfactor, self.last, self._micro = saved_state
+        if self.lora is not None:
+            self.lora.merge()                           # (opt.p is the adapters' buffer: the master follows it)
         self.e.refresh_weights(cast_shadow=True)
         if graph is None:
             self.set_overlap(*prev)
@@ -397,6 +430,8 @@ class SISSStepper:
         self._pending.append(allreduce_pieces([ps.grads[k, ps.split:] for k in range(ps.grads.shape[0])], self.pg, async_op=True))
 
     def _sync_and_update(self):
+        if self.lora is not None:
+            return self._lora_update()
         g = self.e.ps.grads
         sharded = (self.dp_on and self.exchange == "sharded" and not self.overlap
                    and can_shard(g.shape[1], self.world))
@@ -434,6 +469,20 @@ class SISSStepper:
         self.opt.launch(g, ranges=self._ranges, **okw)
         self.e.refresh_weights(lazy=True)               # (the dgrad weight copies: beside the next forward pass)
 
+    def _lora_update(self):
+        """The update of a LoRA step: project -> (all-reduce of the adapter gradients) -> norms / recombine / clip / AdamW on the
+        adapters -> merge -> operand copies.  Same stream, persistent tables, no host sync, no allocation: capturable like the rest."""
+        lora = self.lora
+        single = self.loss_fn in (NEG_GRAD, NAIVE)
+        lora.project(nsets=1 if single else 2)
+        if self.dp_on:
+            allreduce_flat_grads(lora.g, self.pg)       # (the projection is linear: the sum of the ranks' dW projected = this sum)
+        self.opt.launch(lora.g, scaling_norm=self.scaling_norm if not single else 1.0,
+                        eta=self.eta if self.loss_fn == ERASEDIFF else None, inf_guard=self.inf_guard or single)
+        lora.merge()
+        lora.steps += 1
+        self.e.refresh_weights(lazy=True)               # every derived operand copy comes out of the refresh that follows AdamW today
+
     def step(self, x0, a0, noise, t, u, conditioning=None, erase_target=None):
         """GA=1 convenience."""
         assert self.ga == 1
@@ -466,6 +515,8 @@ class SISSStepper:
 
     def trainable_counts(self):
         """(trainable_params, trainable_tensors) of every log line: the parameters the optimizer updates."""
+        if self.lora is not None:
+            return self.lora.params, self.lora.tensors
         if self.subset is not None:
             return self.subset.params, self.subset.tensors
         specs = self.e.ps.specs

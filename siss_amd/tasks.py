@@ -203,6 +203,29 @@ class _DeleteBase(Task):
         pats = self.trainable_patterns()
         if pats is not None:
             select(self.unet_param_names(), pats)
+        # deletion.lora: a malformed mapping, a rank outside 1..64, a target that matches nothing or is no linear / 1x1 weight, and the key
+        # together with deletion.trainable are settled here too
+        lcfg = self.lora_config()
+        if lcfg is not None:
+            from .lora import select_targets
+            select_targets(self.unet_param_specs(), lcfg.patterns)
+
+    # -- deletion.lora: null | {rank, alpha, targets, seed} (OPT-IN; siss_amd/lora.py) ------------------------------------------------
+    def lora_config(self):
+        """The parsed deletion.lora (siss_amd.lora.LoRAConfig), or None (absent / null: no adapter, today's run)."""
+        from .lora import parse_lora
+        d = self.cfg.get("deletion") or {}
+        return parse_lora(d.get("lora"), trainable=d.get("trainable"))
+
+    def lora_state(self, unet):
+        """The LoRAState of the loaded `unet` under deletion.lora (None without the key)."""
+        lcfg = self.lora_config()
+        if lcfg is None:
+            return None
+        from .lora import LoRAState, select_targets
+        st = LoRAState(unet.engine, select_targets(unet.engine.ps.specs, lcfg.patterns), lcfg.rank, lcfg.alpha, lcfg.seed)
+        st.base = str(self.cfg.get("checkpoint_path") or self.cfg.get("pretrained_model_name_or_path") or "") or None
+        return st
 
     # -- deletion.trainable: null | [regular expressions over the diffusers parameter names] (OPT-IN; siss_amd/trainable.py) -----------
     def trainable_patterns(self):
@@ -228,6 +251,10 @@ class _DeleteBase(Task):
     def unet_param_names(self):
         """The diffusers parameter names of the UNet load_unet() will build, from its configuration alone (no device, no weights):
         the checkpoint's config.json when the checkpoint is on disk, else cfg.unet or the task's default architecture."""
+        return list(self.unet_param_specs())
+
+    def unet_param_specs(self):
+        """{name: PSpec} of the same UNet, from its configuration alone."""
         import importlib
         fn, cls = self.unet_config_source()
         if fn is not None:
@@ -236,7 +263,7 @@ class _DeleteBase(Task):
             raw = {k: v for k, v in (self.cfg.get("unet") or {}).items() if not k.startswith("_")}
             ucfg = cls.from_dict(raw) if raw else self.default_unet()
         mod, name = self.unet_engine.rsplit(".", 1)
-        return getattr(importlib.import_module(mod), name).param_names(ucfg)
+        return getattr(importlib.import_module(mod), name).param_specs(ucfg)
 
     def trainable_names(self, unet):
         """The parameter names deletion.trainable selects in the loaded `unet` (None: the full update -- no key, or a selection of
@@ -516,7 +543,8 @@ class _DeleteBase(Task):
             loss_fn=d.loss_fn, inf_guard=self.inf_guard, process_group=pg,
             mixed_precision=cfg.get("mixed_precision"),
             superfactor=float((d.loss_params or {}).get("superfactor", 1.0)),
-            superfactor_decay=d.get("superfactor_decay"), trainable=self.trainable_names(unet))
+            superfactor_decay=d.get("superfactor_decay"), trainable=self.trainable_names(unet), lora=self.lora_state(unet))
+        lora = stepper.lora
         shape = (unet.config.in_channels, unet.config.sample_size, unet.config.sample_size)
         ds_all, ds_del = self.datasets(shape)
         self.open_image_stores(ds_all, ds_del, device)
@@ -550,6 +578,8 @@ class _DeleteBase(Task):
             st = handle.get()
             st["global_step"], st["lr"], st["elapsed_s"] = meta          # (elapsed: stamped when the step was queued)
             st["trainable_params"], st["trainable_tensors"] = stepper.trainable_counts()
+            if lora is not None:
+                st["lora_rank"], st["lora_alpha"], st["lora_params"], st["lora_tensors"] = lora.rank, lora.alpha, lora.params, lora.tensors
             log.write(json.dumps(st) + "\n")
             log.flush()
             if rank == 0:
@@ -596,6 +626,9 @@ class _DeleteBase(Task):
         self.close_image_stores()
         if rank == 0 and cfg.get("save_final", True):
             unet.save_pretrained(os.path.join(cfg.output_dir, "unet"))
+            if lora is not None:                    # the adapter, beside the merged model
+                lora.steps = n_steps
+                lora.save(os.path.join(cfg.output_dir, "lora"))
         return stepper
 
     def deletion_sampler(self, ds, B):
@@ -1363,6 +1396,9 @@ class TrainUnconditional(Task):
             raise NotImplementedError("enable_xformers_memory_efficient_attention=true: xformers is not used here (the attention "
                                       "kernels are this package's own)")
         _pipeline_sampler(cfg)                                   # pipeline.sampler: a bad name / option is refused before the first step
+        if (cfg.get("deletion") or {}).get("lora") is not None:
+            raise NotImplementedError("deletion.lora: LoRA adapters belong to the unlearning tasks (delete_celeb / delete_tshirt / "
+                                      "delete_sd); the pre-training task updates every parameter")
 
     def dataset(self, shape):
         cfg = self.cfg

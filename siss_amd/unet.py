@@ -322,10 +322,16 @@ class UNetEngine:
     def param_names(cls, cfg):
         """The diffusers parameter names of a configuration, in named_parameters() order, without building an engine (no device, no
         library): what a task needs to judge deletion.trainable before it loads anything."""
+        return list(cls.param_specs(cfg))
+
+    @classmethod
+    def param_specs(cls, cfg):
+        """{name: PSpec} of a configuration, the same way (offsets as declared, before any relayout): what a task needs to judge
+        deletion.lora's targets (a PSpec's kind and native shape) before it loads anything."""
         e = object.__new__(cls)
         e.cfg, e.ps = cfg, ParamStore()
         e._declare_params()
-        return list(e.ps.specs)
+        return e.ps.specs
 
     def _early_blocks(self):
         """Down blocks whose backward runs before the (long) high-resolution tail: the lower half of the ladder."""

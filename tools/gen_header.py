@@ -33,10 +33,11 @@ DOCS = {
     'dpm_solver.hip': "The opt-in DPM-Solver++ (2M) evaluation sampler (siss_amd/scheduler.py DPMSolverMultistepScheduler; no counterpart in the\n * reference, whose samplers are diffusers' DDPMScheduler / DDIMScheduler at 50 steps): classifier-free guidance, the x0-prediction and the\n * first / second order multistep update in one streaming launch per sampling step, with the noise norms of siss_cfg_ddim_step.",
     'latent_cache.hip': "The latent cache of the SD task (siss_amd/latent_cache.py; delete_sd.py:879-888 vae.encode(x).latent_dist.sample() *\n * vae.config.scaling_factor, once per micro-batch and batch): the frozen encoder's posterior moments of the dataset stay on the device and a\n * micro-batch of latents is one gather-and-sample launch over the rows its indices name.",
     'image_store.hip': "The image store of the pixel-space tasks (siss_amd/image_store.py; the DataLoader in front of delete_celeb.py:571-580 and\n * train_unconditional.py:366-372: decode, ToTensor / Normalize, stack and a host-to-device copy of f32 images per micro-batch): the dataset\n * stays on the device as uint8 and a micro-batch of images is one table-gather launch over the rows its indices name.",
+    'lora.hip': "Opt-in LoRA unlearning on the UNet's linear projections (siss_amd/lora.py, `deletion.lora`; no counterpart in the reference,\n * whose runs update every parameter): the engine runs on the merged weight W = W0 + s B A, so these are the chain rule from the weight\n * gradients of both sets to the adapter's (dB = s dW A^T, dA = s B^T dW) and the merge back into the f32 master and its bf16 shadow,\n * each ONE launch over a device job table of all targets; f32 MFMA products in fixed orders, no atomics.",
     'timeemb.hip': "Sinusoidal timestep embedding (diffusers Timesteps/get_timestep_embedding), TimestepEmbedding MLP and\n * ResnetBlock2D.time_emb_proj linears (M = batch rows), forward and backward.",
 }
 ORDER = ['siss_loss.hip', 'gemm_nt.hip', 'gemm_tn.hip', 'groupnorm.hip', 'conv_small.hip', 'attention.hip', 'attn1h.hip', 'flash_attn.hip', 'transformer.hip',
-         'timeemb.hip', 'elementwise.hip', 'optimizer.hip', 'train_state.hip', 'likelihood.hip', 'membership.hip', 'metric_conv.hip', 'metric_train.hip', 'inception.hip', 'kmeans.hip', 'sscd.hip', 'clip_iqa.hip', 'prompt_grad.hip', 'injection.hip', 'dpm_solver.hip', 'latent_cache.hip', 'image_store.hip', 'f32_path.hip']
+         'timeemb.hip', 'elementwise.hip', 'optimizer.hip', 'train_state.hip', 'likelihood.hip', 'membership.hip', 'metric_conv.hip', 'metric_train.hip', 'inception.hip', 'kmeans.hip', 'sscd.hip', 'clip_iqa.hip', 'prompt_grad.hip', 'injection.hip', 'dpm_solver.hip', 'latent_cache.hip', 'image_store.hip', 'lora.hip', 'f32_path.hip']
 HEAD = '''/* siss_hip.h -- C ABI of libsiss_hip.so: the MI355X (gfx950) kernels of the SISS unlearning step.
  *
  * GENERATED by tools/gen_header.py from the .hip sources under siss_amd/csrc -- edit the sources, then regenerate.
