@@ -6,7 +6,6 @@ log_metrics (fraction -> deletion_steps -> Inception Score trigger) that the tas
 The network runs in f32, in eval mode (BatchNorm with its running statistics, folded into the convolutions at load time in f64);
 there is no CPU path: a missing kernel library raises.
 """
-import json
 import math
 import os
 import time
@@ -15,6 +14,7 @@ from collections import OrderedDict
 import torch
 
 from . import metric_net as mn
+from .records import append_jsonl, finite_or_none
 from .metric_net import conv_splits  # noqa: F401  (tests/test_hip_sscd.py reads the split-K choice from here)
 
 BN_EPS = 1e-5
@@ -184,11 +184,6 @@ class TShirtClassifier:
         return matches.float().mean().item(), matches
 
 
-def _finite(v):
-    v = float(v)
-    return v if math.isfinite(v) else None
-
-
 class TShirtMetrics:
     """The metric half of delete_tshirt.py's log_metrics (:438-482) for one rank: at a global step that is a multiple of
     `sampling_steps` the T-shirt fraction of `eval_images` samples (the first step where it is 0 becomes `deletion_steps`); at a
@@ -213,7 +208,7 @@ class TShirtMetrics:
         rec = {"global_step": int(global_step)}
         if self.sampling_steps and global_step % self.sampling_steps == 0:
             frac, _ = TShirtClassifier.get_tshirt_frequency(self.sample(self.eval_images, self.eval_batch_size), self.tshirt)
-            rec["deletion_class_fraction"] = _finite(frac)
+            rec["deletion_class_fraction"] = finite_or_none(frac)
             if frac == 0 and self.deletion_steps is None:
                 self.deletion_steps = rec["deletion_steps"] = int(global_step)
         if self.inception is not None and ((self.is_every and global_step % self.is_every == 0) or self.deletion_steps == global_step):
@@ -225,11 +220,9 @@ class TShirtMetrics:
                 calc = self.inception()
                 calc.update(kept)
                 mean, std = calc.compute(generator=self.generator)
-            rec.update(is_mean=_finite(mean), is_std=_finite(std), is_images=int(kept.shape[0]))
+            rec.update(is_mean=finite_or_none(mean), is_std=finite_or_none(std), is_images=int(kept.shape[0]))
         if len(rec) == 1:
             return None
         rec["seconds"] = time.perf_counter() - t0
         rec.update(self.extra or {})
-        with open(self.out_path, "a") as f:
-            f.write(json.dumps(rec) + "\n")
-        return rec
+        return append_jsonl(self.out_path, rec)

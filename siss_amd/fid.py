@@ -10,7 +10,6 @@ is no CPU path: a missing kernel library raises.  Images handed to the metric on
 what `compute()` moves to the host is the D x D product of the two covariances, once per evaluation.  (In the task loop the samples
 themselves make one round trip before that: `Evaluator.sample_images` returns host arrays, as the reference's pipeline does.)
 """
-import json
 import math
 import os
 import time
@@ -20,6 +19,7 @@ import torch
 
 from . import lib
 from . import metric_net as mn
+from .records import append_jsonl, finite_or_none
 
 BN_EPS = 1e-3
 FEATURES = 2048
@@ -375,9 +375,7 @@ class FIDTracker:
                 self.end()                               # (`end()` after the last batch: the sampler's buffers go before training resumes)
         fake, real = int(fc.fake_features_num_samples), int(fc.real_features_num_samples)
         fid = float(self.evaluator.compute(reset=True))
-        rec = {"global_step": int(global_step), "fid": fid if math.isfinite(fid) else None, "fake_images": fake, "real_images": real,
+        rec = {"global_step": int(global_step), "fid": finite_or_none(fid), "fake_images": fake, "real_images": real,
                "seconds": time.perf_counter() - t0, **(self.extra or {})}
         print(f"FID: {fid}")
-        with open(self.out_path, "a") as f:
-            f.write(json.dumps(rec) + "\n")
-        return rec
+        return append_jsonl(self.out_path, rec)

@@ -15,13 +15,13 @@ Deviations from scikit-learn, on purpose:
     more pass with identical results and an n_iter_ one higher);
   * centres are held in f32 (sklearn keeps f64 for f64 input): they agree to half an f32 ulp.
 """
-import json
 import os
 
 import numpy as np
 import torch
 
 from . import lib
+from .records import append_jsonl
 
 MAX_CLUSTERS = 16           # csrc/kmeans.hip: 1 <= K <= 16
 MAX_ROWS = (1 << 24) - 1    # uint32 feature sums: 255 * rows < 2^32
@@ -275,12 +275,22 @@ def fit(u8_rows, n_clusters=2, init="k-means++", max_iter=300, n_init=1, generat
 class DeletionFraction:
     """delete_sd.py:269-275 for one rank: `record(prompt, labels, step)` takes the labels of one validation prompt's images,
     appends {global_step, deletion_fraction_<i>} to `out_path` and adds deletion_steps_<i> = step the FIRST time that prompt's
-    fraction is 0 (the reference writes it into the run summary once)."""
+    fraction is 0 (the reference writes it into the run summary once).  `score_decoded` / `score_u8` are the classifier's labels in
+    the shape the other scorers of the SD evaluation have (metric_net.score_chain)."""
 
     def __init__(self, classifier, out_path):
         self.classifier, self.out_path = classifier, out_path
         self.deletion_steps = {}
         self.extra = None                                # fields added to every record (pipeline.sampler: name and step count)
+
+    def score_decoded(self, img):
+        """(labels [n], uint8 images [n, H, W, 3]), both on the device, of the decoder's output (one fused launch, then the labels)."""
+        u8, labels, _ = self.classifier.from_decoded(img)
+        return labels, u8
+
+    def score_u8(self, u8):
+        """Labels [n] (device) of uint8 images [n, H, W, 3]."""
+        return self.classifier.predict(u8)[1]
 
     def record(self, prompt, labels, step):
         labels = torch.as_tensor(labels)
@@ -289,6 +299,4 @@ class DeletionFraction:
         if frac == 0 and prompt not in self.deletion_steps:
             self.deletion_steps[prompt] = rec[f"deletion_steps_{prompt}"] = int(step)
         rec.update(self.extra or {})
-        with open(self.out_path, "a") as f:
-            f.write(json.dumps(rec) + "\n")
-        return rec
+        return append_jsonl(self.out_path, rec)

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import lib
+from .records import append_jsonl
 
 # scipy.integrate RK45 (scipy/integrate/_ivp/rk.py, 1.15): the Dormand-Prince 5(4) pair and the step controller's constants
 RK45_C = (0.0, 1 / 5, 3 / 10, 4 / 5, 8 / 9, 1.0)
@@ -305,13 +306,11 @@ class LikelihoodEvaluator:
 
 def log_likelihood(evaluator, model, image, global_step, path, generator):
     """One evaluation of the forget image, appended to `path` as a JSON line {global_step, bpd, nfe, seconds} (tasks.py)."""
-    import json
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     bpd, _, nfe = evaluator.evaluate_likelihood(model, image.unsqueeze(0) if image.dim() == 3 else image, generator=generator)
     rec = dict(global_step=int(global_step), bpd=float(bpd[0]), nfe=int(nfe), seconds=time.perf_counter() - t0)
-    with open(path, "a") as f:
-        f.write(json.dumps(rec) + "\n")
+    append_jsonl(path, rec)
     print(f"[siss_amd] likelihood at step {global_step}: {rec['bpd']:.4f} bits/dim ({nfe} function evaluations, "
           f"{rec['seconds']:.1f} s)")
     return rec

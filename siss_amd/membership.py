@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import lib
+from .records import append_jsonl
 
 
 def build_work_table(all_indices, deletion_indices, num_noise_samples, timesteps, dedupe=True):
@@ -176,7 +177,6 @@ class MembershipLoss:
 
 def log_membership(metric, timesteps, global_step, path):
     """One evaluation, appended to `path` as a JSON line with the reference's wandb keys (delete_celeb.py:516-518): one host read."""
-    import json
     import time
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -188,8 +188,7 @@ def log_membership(metric, timesteps, global_step, path):
         rec[f"all_membership_loss_t={int(t)}"] = a
         rec[f"deletion_membership_loss_t={int(t)}"] = d
         rec[f"membership_ratio_t={int(t)}"] = d / a
-    with open(path, "a") as f:
-        f.write(json.dumps(rec) + "\n")
+    append_jsonl(path, rec)
     print(f"[siss_amd] membership loss at step {global_step}: " +
           ", ".join(f"t={int(t)}: ratio {rec[f'membership_ratio_t={int(t)}']:.4f}" for t in timesteps) + f" ({rec['seconds']:.1f} s)")
     return rec

@@ -4,8 +4,6 @@ csrc/metric_conv.hip: the BN fold and the weight packing, the split-K choice, th
 nn.Module surface with its strict state dict (`MetricNet`) and the chunked run over images (`ChunkedImageNet`).  What is a network's
 own -- layer tables, init, forward wiring, its own kernels -- stays in its module.  There is no CPU path: a missing kernel library raises.
 """
-import json
-import math
 import os
 import zipfile
 from collections import OrderedDict
@@ -13,6 +11,7 @@ from collections import OrderedDict
 import torch
 
 from . import lib
+from .records import append_jsonl, finite_or_none
 
 BK = 32                     # K step of metric_conv_kernel: input channel strides and packed weight rows are multiples of it
 
@@ -139,11 +138,16 @@ def read_state_dict(path, what):
 def record_mean(out_path, key, scores, step, extra=None):
     """Append {global_step, key: the mean of the scores in f64 on the host (null when not finite)} to `out_path`; returns the record.
     extra: fields added to it (the sampler's name and step count when the images came from the opt-in pipeline.sampler)."""
-    value = float(torch.as_tensor(scores).detach().cpu().double().mean())
-    rec = {"global_step": int(step), key: value if math.isfinite(value) else None, **(extra or {})}
-    with open(out_path, "a") as f:
-        f.write(json.dumps(rec) + "\n")
-    return rec
+    value = torch.as_tensor(scores).detach().cpu().double().mean()
+    return append_jsonl(out_path, {"global_step": int(step), key: finite_or_none(value), **(extra or {})})
+
+
+def score_chain(scorers, img):
+    """The scorers that share one set of uint8 bytes, in their order, on one decoder output: the first makes the bytes with its fused
+    `score_decoded(img) -> (result, u8)`, every later one takes them through `score_u8(u8) -> result` (one fused entry, the `_u8`
+    entry for the rest).  Returns ([result per scorer], u8).  The methods are looked up now, at the call."""
+    first, u8 = scorers[0].score_decoded(img)
+    return [first] + [s.score_u8(u8) for s in scorers[1:]], u8
 
 
 def _named(k, names):

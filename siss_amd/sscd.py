@@ -16,6 +16,7 @@ import torch
 
 from . import lib
 from . import metric_net as mn
+from .records import append_jsonl, finite_or_none
 
 BN_EPS = 1e-5
 BLOCKS = (3, 4, 6, 3)
@@ -231,11 +232,6 @@ class InjectionScore(SSCDScore):
     the host."""
 
     def record(self, scores, step, timestep):
-        import json
         s = torch.as_tensor(scores).detach().cpu().double().reshape(-1)
-        finite = lambda v: v if math.isfinite(v) else None
-        rec = {"global_step": int(step), "timestep": int(timestep), "sscd_mean": finite(float(s.mean())),
-               "sscd_max": finite(float(s.max())), "sscd": [finite(v) for v in s.tolist()]}
-        with open(self.out_path, "a") as f:
-            f.write(json.dumps(rec) + "\n")
-        return rec
+        return append_jsonl(self.out_path, {"global_step": int(step), "timestep": int(timestep), "sscd_mean": finite_or_none(s.mean()),
+                                            "sscd_max": finite_or_none(s.max()), "sscd": [finite_or_none(v) for v in s.tolist()]})

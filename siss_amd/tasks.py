@@ -18,14 +18,65 @@ import torch
 from . import hydra_lite
 from .config import UNet2DConditionConfig, UNet2DConfig
 from .data import IndexBatch, InfiniteSampler, Prefetcher, RepeatedSampler, SyntheticImages, batches, index_batches
+from .records import LaggedLog, append_jsonl
 from .scheduler import DDPMScheduler
 from .step import SISSStepper
 
 
 class Task(ABC):
+    default_unet = staticmethod(UNet2DConfig.celebahq256)
+    unet_engine = "siss_amd.unet.UNetEngine"
+
+    def __init__(self, cfg):
+        self.cfg = cfg
+
     @abstractmethod
     def run(self):
         pass
+
+    def compute_dtype(self):
+        """`mixed_precision: null` -- the reference's shipped default: fp32 everywhere (delete_celeb.yaml:103) -- runs the f32 engine
+        (every tensor and product f32: the parity mode, 1/16 of the bf16 MFMA rate at best); `bf16` the bf16 MFMA path."""
+        mp = self.cfg.get("mixed_precision")
+        if mp == "bf16":
+            return torch.bfloat16
+        if mp not in (None, "no", "null", "None"):
+            # the reference's YAML lists fp16 / fp8 as choices of accelerate; there is no fp16 path here (and no loss scaler in the
+            # reference's loop either): refuse instead of silently running something else
+            raise NotImplementedError(f"mixed_precision={mp!r}: this build computes in 'bf16' or in f32 (null / 'no'); "
+                                      "fp16 / fp8 are not provided")
+        print("[siss_amd] mixed_precision is null / 'no': true f32 compute for the UNet, the loss and the optimizer (the reference's "
+              "default; a parity mode here, far slower than mixed_precision=bf16, which is what the benchmark runs; the SD front end -- "
+              "VAE / text encoder -- stays bf16)")
+        return torch.float32
+
+    # -- the UNet's configuration, resolved in one place: what load_unet() builds from ---------------------------------------------
+    def unet_checkpoint(self):
+        """The directory whose config.json and weights load_unet() reads, or None (no checkpoint on disk: cfg.unet / default_unet)."""
+        return None
+
+    def unet_config(self):
+        """The configuration of the UNet the task builds, from the host alone (no device, no weights): the checkpoint's config.json
+        when the checkpoint is on disk, else cfg.unet without its `_`-prefixed keys, else the task's default architecture."""
+        cls = type(self.default_unet())
+        d = self.unet_checkpoint()
+        if d is not None:
+            return cls.from_json(os.path.join(d, "config.json"))
+        raw = {k: v for k, v in (self.cfg.get("unet") or {}).items() if not k.startswith("_")}
+        return cls.from_dict(raw) if raw else self.default_unet()
+
+    def unet_param_specs(self):
+        """{name: PSpec} of that UNet, from its configuration alone."""
+        import importlib
+        mod, name = self.unet_engine.rsplit(".", 1)
+        return getattr(importlib.import_module(mod), name).param_specs(self.unet_config())
+
+    def unet_param_names(self):
+        """The diffusers parameter names of that UNet."""
+        return list(self.unet_param_specs())
+
+    def _image_channels(self):
+        return self.unet_config().in_channels
 
 
 def _dist():
@@ -94,6 +145,35 @@ def _inference_steps(cfg):
     return int(((cfg.get("pipeline") or {}).get("num_inference_steps")) or 50)
 
 
+def _positive_int(v):
+    return isinstance(v, int) and not isinstance(v, bool) and v > 0
+
+
+def _scheduler_kwargs(cfg):
+    sc = cfg.get("scheduler") or {}
+    return {k: sc[k] for k in ("num_train_timesteps", "beta_start", "beta_end", "beta_schedule", "prediction_type") if k in sc}
+
+
+def _start_hooks(built):
+    """The loop's metric hooks [(every, fn)] from an iterable of them (a generator: the next one is built only when it is asked
+    for), each called with step 0 -- before the first optimizer step -- as it arrives.  None is no hook; (None, None) says that
+    metric was the whole run (membership_loss.plot_params): None is returned, and nothing later is built or called."""
+    hooks = []
+    for hook in built:
+        if hook == (None, None):
+            return None
+        if hook is not None:
+            hook[1](0)
+            hooks.append(hook)
+    return hooks
+
+
+def _run_hooks(hooks, global_step):
+    for every, fn in hooks:
+        if global_step % every == 0:
+            fn(global_step)
+
+
 def _pipeline_sampler(cfg, base=None, **defaults):
     """`pipeline.sampler` (OPT-IN, null by default): {name: dpmsolver++, solver_order, timestep_spacing, steps_offset} -> the
     DPMSolverMultistepScheduler the evaluation sampling then runs pipeline.num_inference_steps steps of, or None -- the task's own
@@ -115,34 +195,24 @@ def _sampler_fields(cfg, solver):
 class _DeleteBase(Task):
     timestep_low = 999          # delete_celeb.py:593 hard-codes randint(999, 1000)
     inf_guard = False
-    default_unet = staticmethod(UNet2DConfig.celebahq256)
-
-    def __init__(self, cfg):
-        self.cfg = cfg
 
     # -- pieces a subclass may override --------------------------------------------------------
-    def compute_dtype(self):
-        """`mixed_precision: null` -- the reference's shipped default: fp32 everywhere (delete_celeb.yaml:103) -- runs the f32 engine
-        (every tensor and product f32: the parity mode, 1/16 of the bf16 MFMA rate at best); `bf16` the bf16 MFMA path."""
-        mp = self.cfg.get("mixed_precision")
-        if mp == "bf16":
-            return torch.bfloat16
-        if mp not in (None, "no", "null", "None"):
-            # the reference's YAML lists fp16 / fp8 as choices of accelerate; there is no fp16 path here (and no loss scaler in the
-            # reference's loop either): refuse instead of silently running something else
-            raise NotImplementedError(f"mixed_precision={mp!r}: this build computes in 'bf16' or in f32 (null / 'no'); "
-                                      "fp16 / fp8 are not provided")
-        print("[siss_amd] mixed_precision is null / 'no': true f32 compute for the UNet, the loss and the optimizer (the reference's "
-              "default; a parity mode here, far slower than mixed_precision=bf16, which is what the benchmark runs; the SD front end -- "
-              "VAE / text encoder -- stays bf16)")
-        return torch.float32
+    def unet_checkpoint(self):
+        path = str(self.cfg.get("checkpoint_path") or "")
+        if not os.path.isdir(path):
+            return None
+        sub = (self.cfg.get("subfolders") or {}).get("unet")
+        d = os.path.join(path, sub) if sub else path
+        if not os.path.exists(os.path.join(d, "config.json")) and os.path.exists(os.path.join(path, "unet")):
+            d = os.path.join(path, "unet")                           # (UNet2DModel.from_pretrained's fall-back)
+        return d
 
     def load_unet(self, device):
         from .model import UNet2DModel
         cfg = self.cfg
         path = cfg.get("checkpoint_path")
         dt = self.compute_dtype()
-        if path and os.path.isdir(str(path)):
+        if self.unet_checkpoint() is not None:
             sub = (cfg.get("subfolders") or {}).get("unet")
             return UNet2DModel.from_pretrained(path, subfolder=sub, device=device, compute_dtype=dt)
         # The reference hard-fails here (DDPMPipeline.from_pretrained, delete_celeb.py:181).  Random-init weights of the
@@ -151,17 +221,13 @@ class _DeleteBase(Task):
             raise FileNotFoundError(
                 f"checkpoint_path {path!r} is not a directory on disk (no network: hub ids cannot be fetched); "
                 "pass allow_random_init=true to train random-init weights of the configured architecture instead")
-        ucfg = {k: v for k, v in (cfg.get("unet") or {}).items() if not k.startswith("_")}
-        m = UNet2DModel(UNet2DConfig.from_dict(ucfg) if ucfg else self.default_unet(), device=device, compute_dtype=dt)
+        m = UNet2DModel(self.unet_config(), device=device, compute_dtype=dt)
         m.engine.init_random(seed=int(cfg.random_seed))
         print(f"[siss_amd] allow_random_init: checkpoint {path!r} not on disk, RANDOM-INIT weights of the same architecture")
         return m
 
     def load_scheduler(self):
-        sc = self.cfg.get("scheduler") or {}
-        kw = {k: sc[k] for k in ("num_train_timesteps", "beta_start", "beta_end", "beta_schedule", "prediction_type")
-              if k in sc}
-        return DDPMScheduler(**kw)
+        return DDPMScheduler(**_scheduler_kwargs(self.cfg))
 
     def datasets(self, shape):
         cfg = self.cfg
@@ -234,37 +300,6 @@ class _DeleteBase(Task):
         from .trainable import parse_patterns
         return parse_patterns((self.cfg.get("deletion") or {}).get("trainable"))
 
-    unet_engine = "siss_amd.unet.UNetEngine"
-
-    def unet_config_source(self):
-        """(config.json of the checkpoint load_unet() will read, or None; the configuration class): load_unet()'s own choice."""
-        cfg = self.cfg
-        path = cfg.get("checkpoint_path")
-        if path and os.path.isdir(str(path)):
-            sub = (cfg.get("subfolders") or {}).get("unet")
-            d = os.path.join(str(path), sub) if sub else str(path)
-            if not os.path.exists(os.path.join(d, "config.json")) and os.path.exists(os.path.join(str(path), "unet")):
-                d = os.path.join(str(path), "unet")                      # (UNet2DModel.from_pretrained's fall-back)
-            return os.path.join(d, "config.json"), UNet2DConfig
-        return None, UNet2DConfig
-
-    def unet_param_names(self):
-        """The diffusers parameter names of the UNet load_unet() will build, from its configuration alone (no device, no weights):
-        the checkpoint's config.json when the checkpoint is on disk, else cfg.unet or the task's default architecture."""
-        return list(self.unet_param_specs())
-
-    def unet_param_specs(self):
-        """{name: PSpec} of the same UNet, from its configuration alone."""
-        import importlib
-        fn, cls = self.unet_config_source()
-        if fn is not None:
-            ucfg = cls.from_json(fn)
-        else:
-            raw = {k: v for k, v in (self.cfg.get("unet") or {}).items() if not k.startswith("_")}
-            ucfg = cls.from_dict(raw) if raw else self.default_unet()
-        mod, name = self.unet_engine.rsplit(".", 1)
-        return getattr(importlib.import_module(mod), name).param_specs(ucfg)
-
     def trainable_names(self, unet):
         """The parameter names deletion.trainable selects in the loaded `unet` (None: the full update -- no key, or a selection of
         everything).  check_supported() has refused an unmatched entry already; this is the same selection on the model's own names."""
@@ -332,8 +367,7 @@ class _DeleteBase(Task):
         ev = Evaluator(cfg)
         ev.load_model(unet, sched)
         n = int(cfg.get("eval_batch_size") or 4)
-        steps = int(((cfg.get("pipeline") or {}).get("num_inference_steps")) or 50)
-        imgs = ev.sample_images(n, num_inference_steps=steps, set_generator=True,           # [n, H, W, C] in [0, 1]
+        imgs = ev.sample_images(n, num_inference_steps=_inference_steps(cfg), set_generator=True,           # [n, H, W, C] in [0, 1]
                                 sampler=_pipeline_sampler(cfg, sched))
         inj = ((cfg.get("metrics") or {}).get("denoising_injections")) or {}
         t_inj = int(inj.get("timestep", 250))
@@ -392,21 +426,6 @@ class _DeleteBase(Task):
     membership_supported = True
     injection = None            # the injection check's scorer / settings (check_injection_score), None when not configured
 
-    def _image_channels(self):
-        """The UNet's in_channels as far as the host can tell before it is loaded: cfg.unet.in_channels, else the checkpoint's
-        config.json when it is on disk, else the task's default architecture."""
-        cfg = self.cfg
-        ch = (cfg.get("unet") or {}).get("in_channels")
-        if ch is not None:
-            return ch
-        path = str(cfg.get("checkpoint_path") or "")
-        sub = (cfg.get("subfolders") or {}).get("unet") or ""
-        for fn in (os.path.join(path, sub, "config.json"), os.path.join(path, "unet", "config.json")):
-            if os.path.isfile(fn):
-                with open(fn) as f:
-                    return json.load(f).get("in_channels", 3)
-        return self.default_unet().in_channels
-
     def check_injection_score(self):
         """metrics.denoising_injections.sscd: {model_path, data_transforms} (null / absent: nothing): the SSCD similarity of the
         denoised injections with the forget image.  Needs model_path on disk (or allow_random_init=true, there or at the top level:
@@ -431,10 +450,13 @@ class _DeleteBase(Task):
             raise FileNotFoundError(f"{what}: metrics.denoising_injections.img_path {img!r} (the forget image the injections are "
                                     "compared with) is not a file on disk")
         model = _load_sscd(path, sc.get("allow_random_init") or cfg.get("allow_random_init"), what)
-        if not cfg.get("eval_every"):
-            print(f"[siss_amd] {what} is set but eval_every is not: the score is taken at evaluations only")
+        self._note_eval_every(what, "the score is taken")
         from .sscd import InjectionScore
         return InjectionScore(model, str(img), os.path.join(str(cfg.output_dir), "injection_rank0.jsonl"), mean, std)
+
+    def _note_eval_every(self, what, happens):
+        if not self.cfg.get("eval_every"):
+            print(f"[siss_amd] {what} is set but eval_every is not: {happens} at evaluations only")
 
     def check_membership(self, n_all=None, n_deletion=None):
         """metrics.membership_loss needs class_cfg, a positive step_frequency (unless plot_params stops the run before the first
@@ -449,15 +471,14 @@ class _DeleteBase(Task):
         cc = ml.get("class_cfg")
         if not cc:
             raise ValueError("metrics.membership_loss needs class_cfg (metrics.class_membership.MembershipLoss and its sample counts)")
-        positive = lambda v: isinstance(v, int) and not isinstance(v, bool) and v > 0
         T = int((cfg.get("scheduler") or {}).get("num_train_timesteps", 1000))
         plot = ml.get("plot_params")
         if plot:
-            if not positive(plot.get("time_frequency")):
+            if not _positive_int(plot.get("time_frequency")):
                 raise ValueError(f"metrics.membership_loss.plot_params.time_frequency={plot.get('time_frequency')!r}: a positive "
                                  "timestep stride is needed")
         else:
-            if not positive(ml.get("step_frequency")):
+            if not _positive_int(ml.get("step_frequency")):
                 raise ValueError(f"metrics.membership_loss.step_frequency={ml.get('step_frequency')!r}: a positive step count is needed")
             ts = ml.get("timesteps")
             if not isinstance(ts, list) or len(ts) == 0:
@@ -466,7 +487,7 @@ class _DeleteBase(Task):
             if bad:
                 raise ValueError(f"metrics.membership_loss.timesteps: {bad} outside [0, num_train_timesteps = {T})")
         for key in ("num_image_samples", "num_noise_samples", "eval_batch_size"):
-            if not positive(cc.get(key)):
+            if not _positive_int(cc.get(key)):
                 raise ValueError(f"metrics.membership_loss.class_cfg.{key}={cc.get(key)!r}: a positive count is needed")
         n = cc.get("num_image_samples")
         for what, have in (("dataset_all", n_all), ("dataset_deletion", n_deletion)):
@@ -508,6 +529,18 @@ class _DeleteBase(Task):
     def deletion_metrics(self, unet, sched, forget_image, device):
         """The tracker of the configured deletion metrics (a callable of global_step), or None: none here."""
         return None
+
+    def metric_hooks(self, unet, sched, ds_all, ds_del, device, rank=0):
+        """The loop's metric hooks (every, fn) | None | (None, None), generated in the loop's order: likelihood, the task's
+        deletion_metrics (a tracker that owns its schedule enters as (1, tracker)), membership.  fn(global_step) runs at step 0 and at
+        every multiple of `every`; (None, None) ends the run (_start_hooks).  Rank 0 measures; the others only learn that it ended."""
+        if rank != 0:
+            yield (None, None) if (self.check_membership() or {}).get("plot_params") else None
+            return
+        yield self.likelihood_metric(unet, ds_del[0], device)
+        tracker = self.deletion_metrics(unet, sched, ds_del[0], device)
+        yield None if tracker is None else (1, tracker)
+        yield self.membership_metric(unet, sched, ds_all, ds_del, device)
 
     def fill_cfg(self):
         """Placeholders of the config that are read from files before anything else (delete_sd.py:342-348): none here."""
@@ -553,40 +586,31 @@ class _DeleteBase(Task):
         n_steps = int(cfg.training_steps) * max(1, len(d.get("img_name") or [1]))
         cond = self.conditioning(B, device)
         os.makedirs(cfg.output_dir, exist_ok=True)
-        log = open(os.path.join(cfg.output_dir, f"train_log_rank{rank}.jsonl"), "a")
-        g = torch.Generator(device=device).manual_seed(seed + rank)
-        T = sched.config.num_train_timesteps
-        t0 = time.perf_counter()
-        eval_every = int(cfg.get("eval_every") or 0)
-        pending = None
-        likelihood = self.likelihood_metric(unet, ds_del[0], device) if rank == 0 else None
-        if likelihood is not None:
-            likelihood[1](0)                             # before the first optimizer step
-        metrics = self.deletion_metrics(unet, sched, ds_del[0], device) if rank == 0 else None
-        if metrics is not None:
-            metrics(0)
-        membership = self.membership_metric(unet, sched, ds_all, ds_del, device) if rank == 0 else None
-        if ((cfg.get("metrics") or {}).get("membership_loss") or {}).get("plot_params"):
-            it_all.close()                               # the curve is the run (delete_celeb.py:444-462 exits here)
-            self.close_image_stores()
-            log.close()
-            return stepper
-        if membership is not None:
-            membership[1](0)
 
-        def write_log(handle, meta):
+        def record(handle, meta):
             st = handle.get()
             st["global_step"], st["lr"], st["elapsed_s"] = meta          # (elapsed: stamped when the step was queued)
             st["trainable_params"], st["trainable_tensors"] = stepper.trainable_counts()
             if lora is not None:
                 st["lora_rank"], st["lora_alpha"], st["lora_params"], st["lora_tensors"] = lora.rank, lora.alpha, lora.params, lora.tensors
-            log.write(json.dumps(st) + "\n")
-            log.flush()
+            return st
+
+        def say(st, meta):
             if rank == 0:
                 print(f"step {meta[0]}/{n_steps}  |g_x| {st['norm_loss_x']:.4g}  |g_a| {st['norm_loss_a']:.4g}  "
                       f"s {st['scaling_factor']:.4g}")
 
-        try:
+        g = torch.Generator(device=device).manual_seed(seed + rank)
+        T = sched.config.num_train_timesteps
+        t0 = time.perf_counter()
+        eval_every = int(cfg.get("eval_every") or 0)
+        # (the last COMPLETED step reaches the log also when the next one raises or the job is interrupted: ADVICE r05)
+        with LaggedLog(os.path.join(cfg.output_dir, f"train_log_rank{rank}.jsonl"), record, say) as log:
+            hooks = _start_hooks(self.metric_hooks(unet, sched, ds_all, ds_del, device, rank))
+            if hooks is None:
+                it_all.close()                           # the curve is the run (delete_celeb.py:444-462 exits here)
+                self.close_image_stores()
+                return stepper
             for step in range(n_steps):
                 # lr_scheduler.step() after every optimizer step (delete_celeb.py:770); accelerate's wrapper advances the
                 # schedule once per PROCESS per optimizer step (AcceleratedScheduler, split_batches=False)
@@ -598,30 +622,12 @@ class _DeleteBase(Task):
                     t = torch.randint(self.timestep_low, T, (B,), device=device, generator=g)
                     u = torch.rand(B, device=device, generator=g)
                     stepper.micro_step(x0, a0, noise, t, u, cond)
-                # the step's scalars travel to the host behind its kernels; they are read (and logged) once the NEXT step is queued,
-                # so the device never waits for the host between steps (same lines, written one step later)
-                handle, meta = stepper.stats_async(), (step + 1, stepper.opt.lr, time.perf_counter() - t0)
-                if pending is not None:
-                    write_log(*pending)
-                pending = (handle, meta)
+                log.push(stepper.stats_async(), (step + 1, stepper.opt.lr, time.perf_counter() - t0))
                 if eval_every and (step + 1) % eval_every == 0:
-                    write_log(*pending)                 # every rank flushes at an evaluation step (the logs stay in step)
-                    pending = None
+                    log.flush()                         # every rank flushes at an evaluation step (the logs stay in step)
                     if rank == 0:
                         self.evaluate(unet, sched, ds_del[0], step + 1, device)
-                if likelihood is not None and (step + 1) % likelihood[0] == 0:
-                    likelihood[1](step + 1)
-                if metrics is not None:
-                    metrics(step + 1)
-                if membership is not None and (step + 1) % membership[0] == 0:
-                    membership[1](step + 1)
-        finally:
-            # the last COMPLETED optimizer step reaches the log also when the next one raises or the job is interrupted
-            if pending is not None:
-                try:
-                    write_log(*pending)
-                except Exception:
-                    pass
+                _run_hooks(hooks, step + 1)
         it_all.close()
         self.close_image_stores()
         if rank == 0 and cfg.get("save_final", True):
@@ -666,15 +672,14 @@ class DeleteCeleb(_DeleteBase):
         cc = fid.get("class_cfg")
         if not cc:
             raise ValueError("metrics.fid needs class_cfg (metrics.fid.FIDEvaluator and its inception_batch_size)")
-        positive = lambda v: isinstance(v, int) and not isinstance(v, bool) and v > 0
-        if not positive(fid.get("step_frequency")):
+        if not _positive_int(fid.get("step_frequency")):
             raise ValueError(f"metrics.fid.step_frequency={fid.get('step_frequency')!r}: a positive step count is needed")
         n = fid.get("num_imgs_to_generate")
-        if not positive(n) or n < 2:
+        if not _positive_int(n) or n < 2:
             raise ValueError(f"metrics.fid.num_imgs_to_generate={n!r}: at least 2 images are needed (the covariance of one is undefined)")
-        if not positive(fid.get("batch_size")):
+        if not _positive_int(fid.get("batch_size")):
             raise ValueError(f"metrics.fid.batch_size={fid.get('batch_size')!r}: a positive batch size is needed")
-        ch = (cfg.get("unet") or {}).get("in_channels", 3)
+        ch = self._image_channels()
         if ch != 3:
             raise ValueError(f"metrics.fid: the Inception-v3 takes 3-channel images, the UNet has in_channels={ch!r}")
         ckpt = str(cc.get("inception_ckpt") or DEFAULT_CKPT)
@@ -701,7 +706,7 @@ class DeleteCeleb(_DeleteBase):
         from .sampler import Evaluator
         evaluator = hydra_lite.instantiate(fid.class_cfg, device=device)
         evaluator.load_celeb()
-        steps = int(((cfg.get("pipeline") or {}).get("num_inference_steps")) or 50)
+        steps = _inference_steps(cfg)
         gen = torch.Generator(device=device).manual_seed(self.seed())
         held = {}
 
@@ -739,7 +744,7 @@ class DeleteTShirt(_DeleteBase):
         m = cfg.get("metrics") or {}
         if m.get("fraction_deletion"):
             ss = cfg.get("sampling_steps")
-            if not isinstance(ss, int) or isinstance(ss, bool) or ss <= 0:
+            if not _positive_int(ss):
                 raise ValueError(f"metrics.fraction_deletion=true needs a positive sampling_steps (the reference's key: the T-shirt "
                                  f"fraction runs every sampling_steps optimizer steps); got sampling_steps={ss!r}")
         isc = m.get("inception_score")
@@ -748,7 +753,7 @@ class DeleteTShirt(_DeleteBase):
             if not cc:
                 raise ValueError("metrics.inception_score needs metrics.classifier_cfg (the classifier the score is taken with)")
             freq = isc.get("step_frequency")
-            if not isinstance(freq, int) or isinstance(freq, bool) or freq <= 0:
+            if not _positive_int(freq):
                 raise ValueError(f"metrics.inception_score.step_frequency={freq!r}: a positive step count is needed")
             ckpt = cc.get("classifier_ckpt")
             if ckpt is not None and not os.path.isfile(str(ckpt)):
@@ -779,7 +784,7 @@ class DeleteTShirt(_DeleteBase):
         else:
             tshirt = forget_image.float() * 0.5 + 0.5
         tshirt = tshirt.to(device).float()
-        steps = int(((cfg.get("pipeline") or {}).get("num_inference_steps")) or 50)
+        steps = _inference_steps(cfg)
         gen = torch.Generator(device=device).manual_seed(self.seed())
         solver = _pipeline_sampler(cfg, sched)
 
@@ -912,25 +917,22 @@ class DeleteSD(_DeleteBase):
         self.load_front_end(device)
         path = cfg.get("pretrained_model_name_or_path")
         dt = self.compute_dtype()                                # (the frozen VAE / text encoder front end stays on the bf16 path)
-        if path and os.path.isdir(os.path.join(str(path), "unet")):
+        if self.unet_checkpoint() is not None:
             return UNet2DConditionModel.from_pretrained(path, subfolder="unet", device=device, compute_dtype=dt)   # delete_sd.py:458-462
         if not cfg.get("allow_random_init"):                     # the reference hard-fails (from_pretrained, delete_sd.py:458-462)
             raise FileNotFoundError(
                 f"pretrained_model_name_or_path {path!r} has no unet/ directory on disk (no network: hub ids cannot be "
                 "fetched); pass allow_random_init=true to train random-init weights of the configured architecture instead")
-        ucfg = {k: v for k, v in (cfg.get("unet") or {}).items() if not k.startswith("_")}
-        m = UNet2DConditionModel(UNet2DConditionConfig.from_dict(ucfg) if ucfg else self.default_unet(), device=device, compute_dtype=dt)
+        m = UNet2DConditionModel(self.unet_config(), device=device, compute_dtype=dt)
         m.engine.init_random(seed=self.seed())
         print(f"[siss_amd] allow_random_init: {path!r}/unet not on disk, RANDOM-INIT weights of the same architecture")
         return m
 
     unet_engine = "siss_amd.unet_cond.UNetCondEngine"
 
-    def unet_config_source(self):
+    def unet_checkpoint(self):
         path = self.cfg.get("pretrained_model_name_or_path")
-        if path and os.path.isdir(os.path.join(str(path), "unet")):
-            return os.path.join(str(path), "unet", "config.json"), UNet2DConditionConfig
-        return None, UNet2DConditionConfig
+        return os.path.join(str(path), "unet") if path and os.path.isdir(os.path.join(str(path), "unet")) else None
 
     def load_scheduler(self):
         # the SD v1 scheduler_config.json: scaled-linear betas 0.00085 -> 0.012 (delete_sd.py:412)
@@ -1004,6 +1006,18 @@ class DeleteSD(_DeleteBase):
         self.sscd = self.check_sscd()
         self.clip_iqa = self.check_clip_iqa()
 
+    def _need_vae(self, what, does):
+        ckpt = str(self.cfg.get("pretrained_model_name_or_path") or "")
+        if not os.path.isdir(os.path.join(ckpt, "vae")):
+            raise FileNotFoundError(f"{what} {does}: no vae/ under {ckpt!r}")
+
+    def _need_mem_image(self, what):
+        mem = (self.cfg.get("data_files") or {}).get("mem_img_path")
+        if not mem or not os.path.isfile(str(mem)):
+            raise FileNotFoundError(f"{what}: data_files.mem_img_path {mem!r} (the memorized image; set from "
+                                    "clustering_info_path when deletion.frac_deletion is null) is not a file on disk")
+        return mem
+
     def check_clip_iqa(self):
         """metrics.clip_iqa (delete_sd.py:222-223,:264-267; null / absent / false: nothing; bare true: the mapping with no keys) needs
         model_path (OpenAI's RN50.pt, or a state dict of it) on disk -- or allow_random_init=true: a random-init network of the same
@@ -1020,9 +1034,7 @@ class DeleteSD(_DeleteBase):
         path = ci.get("model_path")
         if not path:
             raise ValueError("metrics.clip_iqa: model_path is needed (OpenAI's CLIP RN50.pt, or a state dict of it)")
-        ckpt = str(cfg.get("pretrained_model_name_or_path") or "")
-        if not os.path.isdir(os.path.join(ckpt, "vae")):
-            raise FileNotFoundError(f"metrics.clip_iqa scores decoded validation images: no vae/ under {ckpt!r}")
+        self._need_vae("metrics.clip_iqa", "scores decoded validation images")
         bs = int(ci.get("batch_size") or 16)
         if os.path.isfile(str(path)):
             model = CLIPIQAModel.load(str(path), batch_size=bs)
@@ -1034,7 +1046,7 @@ class DeleteSD(_DeleteBase):
             print(f"[siss_amd] allow_random_init: CLIP checkpoint {path!r} not on disk, RANDOM-INIT CLIP RN50: the CLIP-IQA figures "
                   "are NOT comparable with published ones")
         ids_path = ci.get("prompt_ids_path")
-        tok_dir = str(ci.get("tokenizer_path") or os.path.join(ckpt, "tokenizer"))
+        tok_dir = str(ci.get("tokenizer_path") or os.path.join(str(cfg.get("pretrained_model_name_or_path") or ""), "tokenizer"))
         if ids_path:
             if not os.path.isfile(str(ids_path)):
                 raise FileNotFoundError(f"metrics.clip_iqa.prompt_ids_path {ids_path!r} is not a file on disk")
@@ -1051,8 +1063,7 @@ class DeleteSD(_DeleteBase):
             raise ValueError(f"metrics.clip_iqa: prompt ids [2, {ids.shape[1]}] reaching {int(ids.max())} do not fit the text tower "
                              f"({model.context_length} positions, vocabulary {model.vocab_size}): prompt_ids_path / tokenizer_path "
                              "belong to another model")
-        if not cfg.get("eval_every"):
-            print("[siss_amd] metrics.clip_iqa is set but eval_every is not: the score is taken at evaluations only")
+        self._note_eval_every("metrics.clip_iqa", "the score is taken")
         return CLIPIQAScore(model, ids, os.path.join(str(cfg.output_dir), "metrics_rank0.jsonl"))
 
     def check_sscd(self):
@@ -1070,16 +1081,10 @@ class DeleteSD(_DeleteBase):
         if not path:
             raise ValueError(f"metrics.sscd={sc!r}: model_path is needed (sscd_disc_mixup.torchscript.pt, or a state dict of it)")
         mean, std = _sscd_normalize(sc.get("data_transforms"), "metrics.sscd")
-        ckpt = str(cfg.get("pretrained_model_name_or_path") or "")
-        if not os.path.isdir(os.path.join(ckpt, "vae")):
-            raise FileNotFoundError(f"metrics.sscd embeds decoded validation images: no vae/ under {ckpt!r}")
-        mem = (cfg.get("data_files") or {}).get("mem_img_path")
-        if not mem or not os.path.isfile(str(mem)):
-            raise FileNotFoundError(f"metrics.sscd: data_files.mem_img_path {mem!r} (the memorized image; set from "
-                                    "clustering_info_path when deletion.frac_deletion is null) is not a file on disk")
+        self._need_vae("metrics.sscd", "embeds decoded validation images")
+        mem = self._need_mem_image("metrics.sscd")
         model = _load_sscd(path, sc.get("allow_random_init") or cfg.get("allow_random_init"), "metrics.sscd")
-        if not cfg.get("eval_every"):
-            print("[siss_amd] metrics.sscd is set but eval_every is not: the score is taken at evaluations only")
+        self._note_eval_every("metrics.sscd", "the score is taken")
         return SSCDScore(model, str(mem), os.path.join(str(cfg.output_dir), "metrics_rank0.jsonl"), mean, std)
 
     def check_injection_score(self):
@@ -1098,28 +1103,21 @@ class DeleteSD(_DeleteBase):
         strength = inj.get("strength", 0.5)
         if not number(strength) or not strength > 0:
             raise ValueError(f"metrics.denoising_injections.strength={strength!r}: a positive number is needed")
-        steps = int(((cfg.get("pipeline") or {}).get("num_inference_steps")) or 50)
+        steps = _inference_steps(cfg)
         if int(steps * strength) < 1:
             raise ValueError(f"metrics.denoising_injections.strength={strength!r} of pipeline.num_inference_steps={steps} leaves no "
                              "denoising step (strength * num_inference_steps < 1)")
         n = inj.get("num_images", 1)
-        if not isinstance(n, int) or isinstance(n, bool) or n <= 0:
+        if not _positive_int(n):
             raise ValueError(f"metrics.denoising_injections.num_images={n!r}: a positive count is needed")
         vp = cfg.get("validation_prompts") or [None]
         prompt = inj.get("prompt", 0)
         if not isinstance(prompt, int) or isinstance(prompt, bool) or not 0 <= prompt < len(vp):
             raise ValueError(f"metrics.denoising_injections.prompt={prompt!r}: an index into validation_prompts ({len(vp)} entries) "
                              "is needed")
-        ckpt = str(cfg.get("pretrained_model_name_or_path") or "")
-        if not os.path.isdir(os.path.join(ckpt, "vae")):
-            raise FileNotFoundError(f"metrics.denoising_injections encodes the memorized image and decodes the result: no vae/ "
-                                    f"under {ckpt!r}")
-        mem = (cfg.get("data_files") or {}).get("mem_img_path")
-        if not mem or not os.path.isfile(str(mem)):
-            raise FileNotFoundError(f"metrics.denoising_injections: data_files.mem_img_path {mem!r} (the memorized image; set from "
-                                    "clustering_info_path when deletion.frac_deletion is null) is not a file on disk")
-        if not cfg.get("eval_every"):
-            print("[siss_amd] metrics.denoising_injections is set but eval_every is not: the check runs at evaluations only")
+        self._need_vae("metrics.denoising_injections", "encodes the memorized image and decodes the result")
+        mem = self._need_mem_image("metrics.denoising_injections")
+        self._note_eval_every("metrics.denoising_injections", "the check runs")
         return dict(strength=float(strength), num_images=n, prompt=prompt, mem_img_path=str(mem))
 
     def check_fraction_deletion(self):
@@ -1137,9 +1135,7 @@ class DeleteSD(_DeleteBase):
                              "the .npz tools/make_sd_clusters.py writes)")
         if not os.path.isfile(str(path)):
             raise FileNotFoundError(f"metrics.fraction_deletion.classifier_path {path!r} is not a file on disk")
-        ckpt = str(cfg.get("pretrained_model_name_or_path") or "")
-        if not os.path.isdir(os.path.join(ckpt, "vae")):
-            raise FileNotFoundError(f"metrics.fraction_deletion classifies decoded validation images: no vae/ under {ckpt!r}")
+        self._need_vae("metrics.fraction_deletion", "classifies decoded validation images")
         from .kmeans import KMeansClassifier
         clf = KMeansClassifier.load(str(path))
         res = int(cfg.get("resolution") or 512)
@@ -1149,8 +1145,7 @@ class DeleteSD(_DeleteBase):
         if clf.n_clusters != 2:
             raise ValueError(f"metrics.fraction_deletion: {clf.n_clusters} clusters; the deletion fraction is the mean label, a "
                              "fraction only for two (label 1 = memorized)")
-        if not cfg.get("eval_every"):
-            print("[siss_amd] metrics.fraction_deletion is set but eval_every is not: the fraction is taken at evaluations only")
+        self._note_eval_every("metrics.fraction_deletion", "the fraction is taken")
         return clf
 
     def datasets(self, shape):
@@ -1255,87 +1250,61 @@ class DeleteSD(_DeleteBase):
         eval_batch_size images (DDIM, pipeline.num_inference_steps or 50 steps, guidance 7.5) from ONE generator seeded from
         cfg.seed per evaluation (:213-218), written as a PNG grid (nrow = int(sqrt(N)), :246), and the per-step text-conditional
         and unconditional noise norms averaged over the images, index 0 = the smallest timestep (:284-291), appended to
-        noise_norms_rank0.jsonl.  Opt-in through eval_every; its own RNG; the engine's weights are only read.  With
-        metrics.fraction_deletion the decoder's output goes to the k-means classifier on the device (one fused launch yields the grid's
-        uint8 images and the distances, one more the labels): {global_step, deletion_fraction_<i>} per prompt -- the mean label over
-        the eval_batches x eval_batch_size images (:271-273) -- is appended to metrics_rank0.jsonl, with deletion_steps_<i> on the
-        first evaluation whose fraction is 0 (:274-275).  With metrics.sscd the same uint8 images go through the SSCD network
-        (sscd.SSCDScore: from the classifier's bytes when the fraction is on too, else bytes and embeddings in one pass from the
-        decoder's output) and {global_step, sscd_<i>} -- the mean cosine with the memorized image's embedding (:277-283) -- is appended
-        to the same file.  With metrics.clip_iqa the same uint8 images go through the CLIP RN50 (clip_iqa.CLIPIQAScore: from the bytes
-        the other two metrics made when one of them is on, else bytes and scores in one pass) and {global_step, clip_iqa_<i>} -- the
-        mean probability of "Good photo." against "Bad photo." (:264-267) -- is appended as well; only the scores, the labels and
-        the grid's bytes leave the device.  With metrics.denoising_injections the memorized image is then injected and denoised
-        (evaluate_injection)."""
+        noise_norms_rank0.jsonl.  Opt-in through eval_every; its own RNG; the engine's weights are only read.  The configured scorers
+        of the decoder's output run as one chain (metric_net.score_chain) in the order fraction, SSCD, CLIP-IQA: the first makes the
+        grid's uint8 images in its fused launch, the others read those bytes, and each appends one record per prompt to
+        metrics_rank0.jsonl -- {global_step, deletion_fraction_<i>}: the mean k-means label over the images (:271-273), with
+        deletion_steps_<i> on the first evaluation whose fraction is 0 (:274-275); {global_step, sscd_<i>}: the mean cosine with the
+        memorized image's embedding (:277-283); {global_step, clip_iqa_<i>}: the mean probability of "Good photo." against "Bad
+        photo." (:264-267).  Only the scores, the labels and the grid's bytes leave the device.  With metrics.denoising_injections
+        the memorized image is then injected and denoised (evaluate_injection)."""
         import numpy as np
         cfg = self.cfg
         sampler = self.pipeline or self._validation_pipeline(unet, device)
         nb, bs = int(cfg.get("eval_batches") or 8), int(cfg.get("eval_batch_size") or 1)
-        steps = int(((cfg.get("pipeline") or {}).get("num_inference_steps")) or 50)
+        steps = _inference_steps(cfg)
         vp = cfg.get("validation_prompts") or [None]
         g = torch.Generator(device=device).manual_seed(self.seed())
+        from .metric_net import score_chain
         from .scheduler import DPMSolverMultistepScheduler
         fields = sampler.scheduler.record_fields(steps) if isinstance(sampler.scheduler, DPMSolverMultistepScheduler) else None
-        for tracker in (self.sscd, self.clip_iqa):               # pipeline.sampler: every record says which sampler made the images
-            if tracker is not None:
-                tracker.extra = fields
-        out_type = "np" if sampler.vae is not None else "latent"
-        if self.kmeans is not None:
+        if self.kmeans is not None and self.fraction is None:
             from .kmeans import DeletionFraction
-            if sampler.vae is None:
-                raise FileNotFoundError("metrics.fraction_deletion: the validation pipeline has no VAE decoder")
-            out_type = "decoded"
-            if self.fraction is None:
-                self.fraction = DeletionFraction(self.kmeans, os.path.join(cfg.output_dir, "metrics_rank0.jsonl"))
-                self.fraction.extra = fields
-        if self.sscd is not None:
-            if sampler.vae is None:
-                raise FileNotFoundError("metrics.sscd: the validation pipeline has no VAE decoder")
-            out_type = "decoded"
-        if self.clip_iqa is not None:
-            if sampler.vae is None:
-                raise FileNotFoundError("metrics.clip_iqa: the validation pipeline has no VAE decoder")
-            out_type = "decoded"
+            self.fraction = DeletionFraction(self.kmeans, os.path.join(cfg.output_dir, "metrics_rank0.jsonl"))
+        # the scorers of the decoder's output in the order of their records: the first makes the uint8 bytes, the others read them
+        active = [(what, scorer) for what, scorer in (("metrics.fraction_deletion", self.fraction), ("metrics.sscd", self.sscd),
+                                                      ("metrics.clip_iqa", self.clip_iqa)) if scorer is not None]
+        if active and sampler.vae is None:
+            raise FileNotFoundError(f"{active[0][0]}: the validation pipeline has no VAE decoder")
+        for _, scorer in active:
+            scorer.extra = fields                               # pipeline.sampler: every record says which sampler made the images
+        out_type = "decoded" if active else "np" if sampler.vae is not None else "latent"
         with sampler.holding_graphs():
             for i, p in enumerate(vp):
                 e = self._prompt_embedding(p, device)
-                imgs, text_n, uncond_n, labels, scores, iqa = [], [], [], [], [], []
+                imgs, text_n, uncond_n, results = [], [], [], [[] for _ in active]
                 for _ in range(nb):
                     im, st = sampler(e, negative_prompt_embeds=self._negative_embeds, num_inference_steps=steps,
                                      guidance_scale=7.5, num_images_per_prompt=bs, generator=g, output_type=out_type)
-                    if out_type == "decoded":
-                        if self.kmeans is not None:
-                            im, lab, _ = self.kmeans.from_decoded(im)   # uint8 [n, H, W, 3] + labels, still on the device
-                            labels.append(lab)
-                            if self.sscd is not None:
-                                scores.append(self.sscd.score_u8(im))   # the same bytes through the network
-                        elif self.sscd is not None:
-                            sc, im = self.sscd.score_decoded(im)        # bytes and embeddings in one pass
-                            scores.append(sc)
-                        else:
-                            sc, im = self.clip_iqa.score_decoded(im)    # bytes and probabilities in one pass
-                            iqa.append(sc)
-                        if self.clip_iqa is not None and (self.kmeans is not None or self.sscd is not None):
-                            iqa.append(self.clip_iqa.score_u8(im))      # the same bytes through the CLIP RN50
+                    if active:
+                        out, im = score_chain([scorer for _, scorer in active], im)     # uint8 [n, H, W, 3], still on the device
+                        for got, one in zip(results, out):
+                            got.append(one)
                         imgs.extend(list(im.cpu().numpy()))
                     elif out_type == "np":
                         imgs.extend(list(im))
                     text_n.extend(st["text_noise_norm"])
                     uncond_n.extend(st["uncond_noise_norm"])
-                if labels:
-                    self.fraction.record(i, torch.cat(labels).cpu(), step)
-                if scores:
-                    self.sscd.record(i, torch.cat(scores).cpu(), step)
-                if iqa:
-                    self.clip_iqa.record(i, torch.cat(iqa).cpu(), step)
+                for (_, scorer), got in zip(active, results):
+                    if got:
+                        scorer.record(i, torch.cat(got).cpu(), step)
                 if imgs:
                     _grid(imgs, int(np.sqrt(len(imgs)))).save(os.path.join(cfg.output_dir, f"validation_p{i}_step{step}.png"))
                 rec = {"step": step, "prompt": i, "prompt_text": None if p is None else str(p),
                        "timesteps": sampler.scheduler.timesteps[::-1],
                        "text_noise_norm": np.mean(np.asarray(text_n), axis=0)[::-1].tolist(),
                        "uncond_noise_norm": np.mean(np.asarray(uncond_n), axis=0)[::-1].tolist(), **(fields or {})}
-                with open(os.path.join(cfg.output_dir, "noise_norms_rank0.jsonl"), "a") as f:
-                    f.write(json.dumps(rec) + "\n")
+                append_jsonl(os.path.join(cfg.output_dir, "noise_norms_rank0.jsonl"), rec)
             if self.injection is not None:
                 self.evaluate_injection(sampler, step, device, steps)
 
@@ -1374,10 +1343,7 @@ class TrainUnconditional(Task):
     the plain eps-MSE step (siss_amd/train.py) with the EMA of the weights, a sample grid from the EMA weights every `sampling_steps`,
     a resumable `checkpoint-<global_step>/` every `checkpointing_steps` (siss_amd/checkpoint.py), `unet/` and `unet_ema/` at the end."""
 
-    def __init__(self, cfg):
-        self.cfg = cfg
-
-    compute_dtype = _DeleteBase.compute_dtype
+    default_unet = staticmethod(UNet2DConfig.mnist_tshirt)
     train_store = None          # image_store on: the ImageStore of the training set (siss_amd/image_store.py)
 
     def check_supported(self):
@@ -1427,12 +1393,9 @@ class TrainUnconditional(Task):
         seed = int(cfg.random_seed)
         torch.manual_seed(seed)
         dt = self.compute_dtype()
-        ucfg = {k: v for k, v in (cfg.get("unet") or {}).items() if not k.startswith("_")}
-        unet = UNet2DModel(UNet2DConfig.from_dict(ucfg) if ucfg else UNet2DConfig.mnist_tshirt(), device=device, compute_dtype=dt)
+        unet = UNet2DModel(self.unet_config(), device=device, compute_dtype=dt)     # (cfg.unet / the default: checkpoint_path is a state to resume)
         unet.engine.init_random(seed=seed)
-        sc = cfg.get("scheduler") or {}
-        sched = DDPMScheduler(**{k: sc[k] for k in ("num_train_timesteps", "beta_start", "beta_end", "beta_schedule",
-                                                    "prediction_type") if k in sc})
+        sched = DDPMScheduler(**_scheduler_kwargs(cfg))
         ecfg = cfg.get("ema") or {}
         ema = None
         if ecfg.get("use_ema"):                                  # train_unconditional.py:186-194
@@ -1466,20 +1429,21 @@ class TrainUnconditional(Task):
                 raise ValueError(f"{path}: the directory name says step {global_step}, its state.json {state['global_step']}")
             sampler.epoch, sampler.position, lr_pos = int(state["epoch"]), int(state["position"]), int(state["lr_position"])
         os.makedirs(cfg.output_dir, exist_ok=True)
-        log = open(os.path.join(cfg.output_dir, "train_log_rank0.jsonl"), "a")
         sampling_steps, ckpt_steps = int(cfg.get("sampling_steps") or 0), int(cfg.get("checkpointing_steps") or 0)
         limit = cfg.get("checkpoints_total_limit")
         t0 = time.perf_counter()
-        pending = None
 
-        def write_log(handle, meta):
+        def record(handle, meta):
             st = handle.get()
             st["step"], st["epoch"], st["elapsed_s"] = meta
-            log.write(json.dumps(st) + "\n")
-            log.flush()
+            return st
+
+        def say(st, meta):
             print(f"step {meta[0]}/{max_steps}  loss {st['loss']:.4g}  lr {st['lr']:.3g}  |g| {st['pre_clip_norm']:.4g}")
 
-        try:
+        # (on the way out the log writes the last completed step and closes, then the store does)
+        with (contextlib.closing(store) if store is not None else contextlib.nullcontext()), \
+                LaggedLog(os.path.join(cfg.output_dir, "train_log_rank0.jsonl"), record, say) as log:
             for epoch, pos, idx in sampler:
                 # lr_scheduler.step() (:414): accelerate's wrapper advances the schedule once per optimizer step that really happens,
                 # not per micro-batch (AcceleratedScheduler under accumulate()); lr_pos counts those
@@ -1495,10 +1459,7 @@ class TrainUnconditional(Task):
                     continue
                 global_step += 1
                 lr_pos += 1
-                handle, meta = stepper.stats_async(), (global_step, epoch, time.perf_counter() - t0)
-                if pending is not None:
-                    write_log(*pending)
-                pending = (handle, meta)
+                log.push(stepper.stats_async(), (global_step, epoch, time.perf_counter() - t0))
                 if sampling_steps and global_step % sampling_steps == 0:
                     self.sample_grid(unet, ema, sched, global_step)
                 if ckpt_steps and global_step % ckpt_steps == 0:
@@ -1506,15 +1467,6 @@ class TrainUnconditional(Task):
                                dict(global_step=global_step, epoch=sampler.epoch + (sampler.position == len(sampler)),
                                     position=sampler.position % len(sampler), lr_position=lr_pos, generator=g),
                                limit=None if limit is None else int(limit))
-        finally:
-            if pending is not None:
-                try:
-                    write_log(*pending)
-                except Exception:
-                    pass
-            log.close()
-            if store is not None:
-                store.close()
         unet.save_pretrained(os.path.join(cfg.output_dir, (cfg.get("subfolders") or {}).get("unet") or "unet"))
         if ema is not None:
             ema.save_pretrained(os.path.join(cfg.output_dir, (cfg.get("subfolders") or {}).get("unet_ema") or "unet_ema"))
