@@ -11,6 +11,8 @@
 // Here: siss_gemm_nt_f32, siss_gemm_tn_f32, siss_groupnorm_fwd_ld_f32, siss_groupnorm_bwd_ld_f32, siss_conv_out_fprop_f32.
 // The data-movement, softmax and weight-copy kernels are templates on the element type in their own files.
 #include "common.h"
+#include "gn_host.h"
+#include "tn_job.h"
 
 namespace {
 
@@ -501,28 +503,58 @@ __global__ void rowdot_f32_kernel(const float* __restrict__ a, const float* __re
         out[i] = t; }
 }
 
+// ---- host side: one function per kernel family validates and launches
+// An NT product with the defaults: one panel (shift = coff = 0: kNoShiftF) over rows without pixel structure, alpha = 1, nothing optional
+NTF ntf(const void* A, long lda, const void* W, void* C, long ldc, int M, int N, int Kp, int npanels = 1, int rows_per_image = 1,
+        int Hp = 0, int Wp = 0) {
+    NTF p = {};
+    p.A = (const float*)A; p.lda = lda; p.W = (const float*)W; p.C = (float*)C; p.ldc = ldc; p.M = M; p.N = N; p.Kp = Kp;
+    p.npanels = npanels; p.rows_per_image = rows_per_image; p.Hp = Hp; p.Wp = Wp; p.alpha = 1.f;
+    return p;
+}
+// Every f32 NT product: siss_gemm_nt_f32's checks (vacuous where an entry point has ntf's defaults), the panels (HOST arrays), one launch
+int nt_f32(NTF p, const int* shifts, const int* coffs, int batch, void* stream) {
+    SISS_CHECK_ARG(p.A && p.W && p.C && shifts && coffs && p.M > 0 && p.N > 0 && p.Kp > 0 && p.Kp % 16 == 0);
+    SISS_CHECK_ARG(p.npanels >= 1 && p.npanels <= kMaxPanelsF && batch >= 1 && batch <= 65535 && p.rows_per_image > 0);
+    SISS_CHECK_ARG(p.lda % 4 == 0 && ((uintptr_t)p.A | (uintptr_t)p.W) % 16 == 0 && (p.Hp == 0 || (long)p.Hp * p.Wp == p.rows_per_image));
+    for (int i = 0; i < p.npanels; ++i) { p.shift[i] = shifts[i]; p.coff[i] = coffs[i]; SISS_CHECK_ARG(p.coff[i] % 4 == 0); }
+    SISS_CHECK_ARG(cdiv(p.N, 64) <= 65535);
+    gemm_nt_f32_kernel<<<dim3(cdiv(p.M, 16), cdiv(p.N, 64), batch), 256, 0, (hipStream_t)stream>>>(p);
+    SISS_LAUNCH_RET();
+}
+const int kNoShiftF = 0;
+
+// Every f32 GroupNorm backward (`partial` is accepted and not used: a block owns its (sample, group))
+int gn_bwd_f32(const GNBwdCall& c, int s2d) {
+    SISS_CHECK_ARG(c.dy && c.x && c.gamma && c.beta && c.mean && c.rstd && c.dx && c.dgamma && c.dbeta);
+    SISS_CHECK_ARG(c.n2 > 0 && c.nx > 0 && c.set_images > 0 && c.n2 % c.set_images == 0 && c.n2 % c.nx == 0 && c.C % c.G == 0 && c.nx <= 65535);
+    SISS_CHECK_ARG(!c.dx2 || (c.split_c > 0 && c.split_c < c.C));
+    SISS_CHECK_ARG(c.ldx == 0 || c.ldx >= c.C);
+    SISS_CHECK_ARG(!s2d || (c.dx2 && c.H % 2 == 0 && c.W % 2 == 0));
+    gn_bwd_f32_kernel<<<dim3(c.G, c.nx), kGT, 0, (hipStream_t)c.stream>>>(
+        (const float*)c.dy, (const float*)c.x, c.gamma, c.beta, c.mean, c.rstd, (float*)c.dx, (const float*)c.accum, (const float*)c.accum2,
+        (float*)c.dx2, c.split_c, c.accumulate2, c.dgamma, c.dbeta, c.colsum, c.colsum_ld, c.n2 / c.nx, c.nx, c.set_images, c.set_stride,
+        c.H, c.W, c.C, c.G, c.silu, c.dy_compact, c.ldx ? c.ldx : c.C, s2d);
+    SISS_LAUNCH_RET();
+}
+
 }  // namespace
 
 extern "C" {
+
+int siss_gemm_tn_bs_f32(const void* Y, long ldy, const void* X, long ldx, float* dW, long set_stride, int N, int C, int npanels,
+                        const int* shifts, const int* coffs, int nsets, int rows_per_set, long x_set_rows, int row_begin, int row_end,
+                        int nsplits, const void* zero_page, float* dbias, float* dbias2, long bias_set_stride, void* stream);   // (below)
 
 // siss_gemm_nt with f32 tensors (A, W, C, R f32; lda / ldc / ldr / strides in elements), same argument list and epilogue.
 int siss_gemm_nt_f32(const void* A, long lda, const void* W, void* C, long ldc, const float* bias, const float* rowbias, long ldrb,
                      const void* R, long ldr, int M, int N, int Kp, int npanels, const int* shifts, const int* coffs,
                      int rows_per_image, int Hp, int Wp, float alpha, int batch, long strideA, long strideW, long strideC,
                      void* stream) {
-    SISS_CHECK_ARG(A && W && C && shifts && coffs && M > 0 && N > 0 && Kp > 0 && Kp % 16 == 0);
-    SISS_CHECK_ARG(npanels >= 1 && npanels <= kMaxPanelsF && batch >= 1 && batch <= 65535 && rows_per_image > 0);
-    SISS_CHECK_ARG(lda % 4 == 0 && ((uintptr_t)A | (uintptr_t)W) % 16 == 0 && (Hp == 0 || (long)Hp * Wp == rows_per_image));
-    NTF p;
-    p.A = (const float*)A; p.W = (const float*)W; p.C = (float*)C; p.bias = bias; p.rowbias = rowbias; p.R = (const float*)R;
-    p.rowsub = nullptr; p.lda = lda; p.ldc = ldc; p.ldr = ldr; p.ldrb = ldrb; p.strideA = strideA; p.strideW = strideW;
-    p.strideC = strideC; p.M = M; p.N = N; p.Kp = Kp; p.npanels = npanels; p.rows_per_image = rows_per_image; p.Hp = Hp; p.Wp = Wp;
-    p.mul_r = 0; p.d2s = 0; p.alpha_cols = 0; p.alpha = alpha;
-    for (int i = 0; i < kMaxPanelsF; ++i) { p.shift[i] = i < npanels ? shifts[i] : 0; p.coff[i] = i < npanels ? coffs[i] : 0; }
-    for (int i = 0; i < npanels; ++i) SISS_CHECK_ARG(p.coff[i] % 4 == 0);
-    SISS_CHECK_ARG(cdiv(N, 64) <= 65535);
-    gemm_nt_f32_kernel<<<dim3(cdiv(M, 16), cdiv(N, 64), batch), 256, 0, (hipStream_t)stream>>>(p);
-    SISS_LAUNCH_RET();
+    NTF p = ntf(A, lda, W, C, ldc, M, N, Kp, npanels, rows_per_image, Hp, Wp);
+    p.bias = bias; p.rowbias = rowbias; p.ldrb = ldrb; p.R = (const float*)R; p.ldr = ldr; p.alpha = alpha;
+    p.strideA = strideA; p.strideW = strideW; p.strideC = strideC;
+    return nt_f32(p, shifts, coffs, batch, stream);
 }
 
 // siss_gemm_tn with f32 operands (Y, X f32; dW f32 as ever).  nsplits is accepted for the signature's sake: -1 = overwrite, anything
@@ -530,18 +562,8 @@ int siss_gemm_nt_f32(const void* A, long lda, const void* W, void* C, long ldc, 
 int siss_gemm_tn_f32(const void* Y, long ldy, const void* X, long ldx, float* dW, long set_stride, int N, int C, int npanels,
                      const int* shifts, const int* coffs, int nsets, int rows_per_set, long x_set_rows, int row_begin, int row_end,
                      int nsplits, const void* zero_page, float* dbias, float* dbias2, void* stream) {
-    (void)zero_page;
-    SISS_CHECK_ARG(Y && X && dW && shifts && coffs && N > 0 && C > 0 && npanels >= 1 && npanels <= kMaxPanelsF && nsets >= 1);
-    SISS_CHECK_ARG(row_begin >= 0 && row_end > row_begin && row_end <= rows_per_set && (long)npanels * nsets <= 65535);
-    TNF p;
-    p.Y = (const float*)Y; p.X = (const float*)X; p.dW = dW; p.dbias = dbias; p.dbias2 = dbias ? dbias2 : nullptr;
-    p.ldy = ldy; p.ldx = ldx; p.set_stride = set_stride; p.bias_stride = set_stride; p.x_set_rows = x_set_rows; p.N = N; p.C = C; p.npanels = npanels;
-    p.nsets = nsets; p.rows_per_set = rows_per_set; p.row_begin = row_begin; p.row_end = row_end; p.overwrite = nsplits == -1;
-    for (int i = 0; i < kMaxPanelsF; ++i) { p.shift[i] = i < npanels ? shifts[i] : 0; p.coff[i] = i < npanels ? coffs[i] : 0; }
-    hipStream_t st = (hipStream_t)stream;
-    gemm_tn_f32_kernel<<<dim3(cdiv(C, 64), cdiv(N, 16), npanels * nsets), 256, 0, st>>>(p);
-    if (dbias) tn_bias_f32_kernel<<<dim3(cdiv(N, 64), nsets), 64, 0, st>>>(p);
-    SISS_LAUNCH_RET();
+    return siss_gemm_tn_bs_f32(Y, ldy, X, ldx, dW, set_stride, N, C, npanels, shifts, coffs, nsets, rows_per_set, x_set_rows, row_begin,
+                               row_end, nsplits, zero_page, dbias, dbias2, set_stride, stream);
 }
 
 // siss_groupnorm_fwd_ld with f32 tensors (`partial` is accepted and not used: a block owns its (sample, group)).
@@ -562,16 +584,8 @@ int siss_groupnorm_bwd_ld_f32(const void* dy, const void* x, const float* gamma,
                               int accumulate2, float* dgamma, float* dbeta, float* colsum, long colsum_ld, float* partial, int n2,
                               int nx, int set_images, long set_stride, int H, int W, int C, int G, int silu, int dy_compact, int ldx,
                               void* stream) {
-    (void)partial;
-    SISS_CHECK_ARG(dy && x && gamma && beta && mean && rstd && dx && dgamma && dbeta);
-    SISS_CHECK_ARG(n2 > 0 && nx > 0 && set_images > 0 && n2 % set_images == 0 && n2 % nx == 0 && C % G == 0 && nx <= 65535);
-    SISS_CHECK_ARG(!dx2 || (split_c > 0 && split_c < C));
-    SISS_CHECK_ARG(ldx == 0 || ldx >= C);
-    gn_bwd_f32_kernel<<<dim3(G, nx), kGT, 0, (hipStream_t)stream>>>(
-        (const float*)dy, (const float*)x, gamma, beta, mean, rstd, (float*)dx, (const float*)accum, (const float*)accum2, (float*)dx2,
-        split_c, accumulate2, dgamma, dbeta, colsum, colsum_ld, n2 / nx, nx, set_images, set_stride, H, W, C, G, silu, dy_compact,
-        ldx ? ldx : C, 0);
-    SISS_LAUNCH_RET();
+    return gn_bwd_f32(gn_bwd_call(dy, x, gamma, beta, mean, rstd, dx, accum, accum2, dx2, split_c, accumulate2, dgamma, dbeta, colsum,
+                                  colsum_ld, partial, n2, nx, set_images, set_stride, H, W, C, G, silu, dy_compact, ldx, stream), 0);
 }
 
 // siss_conv_out_fprop with an f32 activation.
@@ -726,53 +740,34 @@ int siss_rowdot_f32(const void* a, const void* b, float* out, long rows, long ro
 // siss_gemm_nt_mulsub with f32 tensors: C = R o (alpha (acc - rowsub[row])) (the attention backward's dS from one product)
 int siss_gemm_nt_mulsub_f32(const void* A, long lda, const void* W, void* C, long ldc, const void* R, long ldr, const float* rowsub,
                             int M, int N, int Kp, float alpha, int batch, long strideA, long strideW, long strideC, void* stream) {
-    SISS_CHECK_ARG(A && W && C && R && rowsub && M > 0 && N > 0 && Kp > 0 && Kp % 16 == 0 && batch >= 1 && batch <= 65535);
-    SISS_CHECK_ARG(lda % 4 == 0 && ((uintptr_t)A | (uintptr_t)W) % 16 == 0 && cdiv(N, 64) <= 65535);
-    NTF p;
-    p.A = (const float*)A; p.W = (const float*)W; p.C = (float*)C; p.bias = nullptr; p.rowbias = nullptr; p.R = (const float*)R;
-    p.rowsub = rowsub; p.lda = lda; p.ldc = ldc; p.ldr = ldr; p.ldrb = 0; p.strideA = strideA; p.strideW = strideW; p.strideC = strideC;
-    p.M = M; p.N = N; p.Kp = Kp; p.npanels = 1; p.rows_per_image = 1; p.Hp = 0; p.Wp = 0; p.mul_r = 1; p.d2s = 0; p.alpha_cols = 0;
-    p.alpha = alpha;
-    for (int i = 0; i < kMaxPanelsF; ++i) { p.shift[i] = 0; p.coff[i] = 0; }
-    gemm_nt_f32_kernel<<<dim3(cdiv(M, 16), cdiv(N, 64), batch), 256, 0, (hipStream_t)stream>>>(p);
-    SISS_LAUNCH_RET();
+    SISS_CHECK_ARG(R && rowsub);
+    NTF p = ntf(A, lda, W, C, ldc, M, N, Kp);
+    p.R = (const float*)R; p.ldr = ldr; p.rowsub = rowsub; p.mul_r = 1; p.alpha = alpha;
+    p.strideA = strideA; p.strideW = strideW; p.strideC = strideC;
+    return nt_f32(p, &kNoShiftF, &kNoShiftF, batch, stream);
 }
-
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // f32 forms of the SCHEDULE SWITCHES of the bf16 engine (round 5): folded 1x1 shortcut (forward and dgrad), depth-to-space epilogue,
 // sub-pixel upsample pieces, grouped weight gradients.  Same argument lists as the bf16 launchers; each is the same arithmetic on
 // the simple f32 kernels above (a fold = one accumulation of two products = the second launch adds onto the first's result), so that
 // UNetEngine(dtype=float32, f32_fused=True) runs the schedule bench.py runs and is held against the fp32 oracle at 1e-4.
-static int nt_f32(const void* A, long lda, const void* W, void* C, long ldc, const float* bias, const float* rowbias, long ldrb,
-                  const void* R, long ldr, int M, int N, int Kp, int npanels, const int* shifts, const int* coffs, int rows_per_image,
-                  int Hp, int Wp, int d2s, void* stream) {
-    SISS_CHECK_ARG(A && W && C && shifts && coffs && M > 0 && N > 0 && Kp > 0 && Kp % 16 == 0);
-    SISS_CHECK_ARG(npanels >= 1 && npanels <= kMaxPanelsF && rows_per_image > 0);
-    SISS_CHECK_ARG(lda % 4 == 0 && ((uintptr_t)A | (uintptr_t)W) % 16 == 0 && (Hp == 0 || (long)Hp * Wp == rows_per_image));
-    NTF p;
-    p.A = (const float*)A; p.W = (const float*)W; p.C = (float*)C; p.bias = bias; p.rowbias = rowbias; p.R = (const float*)R;
-    p.rowsub = nullptr; p.lda = lda; p.ldc = ldc; p.ldr = ldr; p.ldrb = ldrb; p.strideA = 0; p.strideW = 0; p.strideC = 0;
-    p.M = M; p.N = N; p.Kp = Kp; p.npanels = npanels; p.rows_per_image = rows_per_image; p.Hp = Hp; p.Wp = Wp;
-    p.mul_r = 0; p.d2s = d2s; p.alpha_cols = 0; p.alpha = 1.f;
-    for (int i = 0; i < kMaxPanelsF; ++i) { p.shift[i] = i < npanels ? shifts[i] : 0; p.coff[i] = i < npanels ? coffs[i] : 0; }
-    for (int i = 0; i < npanels; ++i) SISS_CHECK_ARG(p.coff[i] % 4 == 0);
-    SISS_CHECK_ARG(cdiv(N, 64) <= 65535);
-    gemm_nt_f32_kernel<<<dim3(cdiv(M, 16), cdiv(N, 64), 1), 256, 0, (hipStream_t)stream>>>(p);
-    SISS_LAUNCH_RET();
-}
 
 // siss_gemm_nt_d2s / siss_gemm_nt_d2s_bias with f32 tensors
 int siss_gemm_nt_d2s_f32(const void* A, long lda, const void* W, void* C, long ldc, const void* R, long ldr, int M, int N, int Kp,
                          int npanels, const int* shifts, const int* coffs, int rows_per_image, int Hp, int Wp, int plane, void* stream) {
     SISS_CHECK_ARG(plane >= 0 && plane < 4 && Hp > 2 && Wp > 2);
-    return nt_f32(A, lda, W, C, ldc, nullptr, nullptr, 0, R, ldr, M, N, Kp, npanels, shifts, coffs, rows_per_image, Hp, Wp, 1 + plane, stream);
+    NTF p = ntf(A, lda, W, C, ldc, M, N, Kp, npanels, rows_per_image, Hp, Wp);
+    p.R = (const float*)R; p.ldr = ldr; p.d2s = 1 + plane;
+    return nt_f32(p, shifts, coffs, 1, stream);
 }
 int siss_gemm_nt_d2s_bias_f32(const void* A, long lda, const void* W, void* C, long ldc, const float* bias, int M, int N, int Kp,
                               int npanels, const int* shifts, const int* coffs, int rows_per_image, int Hp, int Wp, int plane,
                               void* stream) {
     SISS_CHECK_ARG(plane >= 0 && plane < 4 && Hp > 2 && Wp > 2);
-    return nt_f32(A, lda, W, C, ldc, bias, nullptr, 0, nullptr, 0, M, N, Kp, npanels, shifts, coffs, rows_per_image, Hp, Wp, 1 + plane, stream);
+    NTF p = ntf(A, lda, W, C, ldc, M, N, Kp, npanels, rows_per_image, Hp, Wp);
+    p.bias = bias; p.d2s = 1 + plane;
+    return nt_f32(p, shifts, coffs, 1, stream);
 }
 
 // siss_gemm_nt_d2s_phases with f32 tensors (round 6: the one-launch form of the four planes / phases is part of the schedule the f32
@@ -784,8 +779,9 @@ int siss_gemm_nt_d2s_phases_f32(const void* A, long lda, const void* W, void* C,
     for (int z = 0; z < 4; ++z) {
         const int np = phase_p0[z + 1] - phase_p0[z];
         SISS_CHECK_ARG(np >= 1);
-        const int rc = nt_f32(A, lda, (const float*)W + (long)phase_p0[z] * N * Kp, C, ldc, bias, nullptr, 0, R, ldr, M, N, Kp, np,
-                              shifts + phase_p0[z], coffs + phase_p0[z], rows_per_image, Hp, Wp, 1 + z, stream);
+        NTF p = ntf(A, lda, (const float*)W + (long)phase_p0[z] * N * Kp, C, ldc, M, N, Kp, np, rows_per_image, Hp, Wp);
+        p.bias = bias; p.R = (const float*)R; p.ldr = ldr; p.d2s = 1 + z;
+        const int rc = nt_f32(p, shifts + phase_p0[z], coffs + phase_p0[z], 1, stream);
         if (rc != SISS_OK) return rc;
     }
     return SISS_OK;
@@ -796,23 +792,27 @@ int siss_gemm_nt_d2s_phases_f32(const void* A, long lda, const void* W, void* C,
 int siss_conv3x3_sc_f32(const void* A, long lda, const void* W, void* C, long ldc, const float* bias, const float* rowbias, long ldrb,
                         const void* A2, long lda2, const void* W2, int K2, const float* bias2, int M, int N, int Kp, const int* shifts,
                         const int* coffs, int rows_per_image, int Hp, int Wp, float* qstats, int* written, void* stream) {
-    (void)qstats;
-    if (written) *written = 0;
+    if (written) *written = 0;       // (qstats is not used)
     SISS_CHECK_ARG(A2 && W2 && K2 > 0);
-    const int z = 0;
-    int rc = nt_f32(A2, lda2, W2, C, ldc, bias2, nullptr, 0, nullptr, 0, M, N, K2, 1, &z, &z, rows_per_image, Hp, Wp, 0, stream);
+    NTF sc = ntf(A2, lda2, W2, C, ldc, M, N, K2, 1, rows_per_image, Hp, Wp);
+    sc.bias = bias2;
+    const int rc = nt_f32(sc, &kNoShiftF, &kNoShiftF, 1, stream);
     if (rc != SISS_OK) return rc;
-    return nt_f32(A, lda, W, C, ldc, bias, rowbias, ldrb, C, ldc, M, N, Kp, 9, shifts, coffs, rows_per_image, Hp, Wp, 0, stream);
+    NTF p = ntf(A, lda, W, C, ldc, M, N, Kp, 9, rows_per_image, Hp, Wp);
+    p.bias = bias; p.rowbias = rowbias; p.ldrb = ldrb; p.R = (const float*)C; p.ldr = ldc;
+    return nt_f32(p, shifts, coffs, 1, stream);
 }
 // siss_conv3x3_dgrad_sc with f32 tensors: C = conv3x3^T(A; W) (+ R) and Cx = conv1x1^T(A; Wx), two launches over the same cotangent
 int siss_conv3x3_dgrad_sc_f32(const void* A, long lda, const void* W, void* C, long ldc, const void* R, long ldr, const void* Wx,
                               void* Cx, long ldcx, int Nx, int M, int N, int Kp, const int* shifts, const int* coffs, int rows_per_image,
                               int Hp, int Wp, void* stream) {
     SISS_CHECK_ARG(Wx && Cx && Nx > 0);
-    int rc = nt_f32(A, lda, W, C, ldc, nullptr, nullptr, 0, R, ldr, M, N, Kp, 9, shifts, coffs, rows_per_image, Hp, Wp, 0, stream);
+    NTF p = ntf(A, lda, W, C, ldc, M, N, Kp, 9, rows_per_image, Hp, Wp);
+    p.R = (const float*)R; p.ldr = ldr;
+    const int rc = nt_f32(p, shifts, coffs, 1, stream);
     if (rc != SISS_OK) return rc;
-    const int z = 0;
-    return nt_f32(A, lda, Wx, Cx, ldcx, nullptr, nullptr, 0, nullptr, 0, M, Nx, Kp, 1, &z, &z, rows_per_image, Hp, Wp, 0, stream);
+    NTF px = ntf(A, lda, Wx, Cx, ldcx, M, Nx, Kp, 1, rows_per_image, Hp, Wp);
+    return nt_f32(px, &kNoShiftF, &kNoShiftF, 1, stream);
 }
 
 // siss_gemm_tn_bs with f32 operands (bias gradients with a set stride of their own)
@@ -822,12 +822,11 @@ int siss_gemm_tn_bs_f32(const void* Y, long ldy, const void* X, long ldx, float*
     (void)zero_page;
     SISS_CHECK_ARG(Y && X && dW && shifts && coffs && N > 0 && C > 0 && npanels >= 1 && npanels <= kMaxPanelsF && nsets >= 1);
     SISS_CHECK_ARG(row_begin >= 0 && row_end > row_begin && row_end <= rows_per_set && (long)npanels * nsets <= 65535);
-    TNF p;
+    TNF p = {};
     p.Y = (const float*)Y; p.X = (const float*)X; p.dW = dW; p.dbias = dbias; p.dbias2 = dbias ? dbias2 : nullptr;
     p.ldy = ldy; p.ldx = ldx; p.set_stride = set_stride; p.bias_stride = bias_set_stride; p.x_set_rows = x_set_rows; p.N = N; p.C = C;
-    p.npanels = npanels; p.nsets = nsets; p.rows_per_set = rows_per_set; p.row_begin = row_begin; p.row_end = row_end;
-    p.overwrite = nsplits == -1;
-    for (int i = 0; i < kMaxPanelsF; ++i) { p.shift[i] = i < npanels ? shifts[i] : 0; p.coff[i] = i < npanels ? coffs[i] : 0; }
+    p.npanels = npanels; p.nsets = nsets; p.rows_per_set = rows_per_set; p.row_begin = row_begin; p.row_end = row_end; p.overwrite = nsplits == -1;
+    for (int i = 0; i < npanels; ++i) { p.shift[i] = shifts[i]; p.coff[i] = coffs[i]; }
     hipStream_t st = (hipStream_t)stream;
     gemm_tn_f32_kernel<<<dim3(cdiv(C, 64), cdiv(N, 16), npanels * nsets), 256, 0, st>>>(p);
     if (dbias) tn_bias_f32_kernel<<<dim3(cdiv(N, 64), nsets), 64, 0, st>>>(p);
@@ -836,19 +835,11 @@ int siss_gemm_tn_bs_f32(const void* Y, long ldy, const void* X, long ldx, float*
 
 // siss_gemm_tn_grouped with f32 operands: the job table walked on the host, one siss_gemm_tn_f32 per job (what the engine's wgrad
 // QUEUE -- deferred launches, held operands -- needs in the f32 mode; there is nothing to group for an instrument)
-struct siss_tn_job_f32 {
-    const void* Y; long ldy; const void* X; long ldx; float* dW; long set_stride;
-    int N, C, npanels, nsets, rows_per_set, row_begin, row_end, nsplits;
-    long x_set_rows;
-    const void* zero_page; float* dbias; float* dbias2;
-    int shifts[9]; int coffs[9];
-    long bias_set_stride;
-};
+
 int siss_gemm_tn_grouped_f32(const void* jobs, int njobs, void* stream) {
     SISS_CHECK_ARG(jobs && njobs > 0 && njobs <= 256);
-    const siss_tn_job_f32* js = (const siss_tn_job_f32*)jobs;
     for (int i = 0; i < njobs; ++i) {
-        const siss_tn_job_f32& j = js[i];
+        const siss_tn_job& j = ((const siss_tn_job*)jobs)[i];
         const int rc = siss_gemm_tn_bs_f32(j.Y, j.ldy, j.X, j.ldx, j.dW, j.set_stride, j.N, j.C, j.npanels, j.shifts, j.coffs, j.nsets,
                                            j.rows_per_set, j.x_set_rows, j.row_begin, j.row_end, j.nsplits, j.zero_page, j.dbias, j.dbias2,
                                            j.bias_set_stride ? j.bias_set_stride : j.set_stride, stream);
@@ -863,15 +854,8 @@ int siss_groupnorm_bwd_ld_s2d_f32(const void* dy, const void* x, const float* ga
                                   int accumulate2, float* dgamma, float* dbeta, float* colsum, long colsum_ld, float* partial, int n2,
                                   int nx, int set_images, long set_stride, int H, int W, int C, int G, int silu, int dy_compact, int ldx,
                                   void* stream) {
-    (void)partial;
-    SISS_CHECK_ARG(dy && x && gamma && beta && mean && rstd && dx && dx2 && dgamma && dbeta);
-    SISS_CHECK_ARG(n2 > 0 && nx > 0 && set_images > 0 && n2 % set_images == 0 && n2 % nx == 0 && C % G == 0 && nx <= 65535);
-    SISS_CHECK_ARG(split_c > 0 && split_c < C && H % 2 == 0 && W % 2 == 0 && (ldx == 0 || ldx >= C));
-    gn_bwd_f32_kernel<<<dim3(G, nx), kGT, 0, (hipStream_t)stream>>>(
-        (const float*)dy, (const float*)x, gamma, beta, mean, rstd, (float*)dx, (const float*)accum, (const float*)accum2, (float*)dx2,
-        split_c, accumulate2, dgamma, dbeta, colsum, colsum_ld, n2 / nx, nx, set_images, set_stride, H, W, C, G, silu, dy_compact,
-        ldx ? ldx : C, 1);
-    SISS_LAUNCH_RET();
+    return gn_bwd_f32(gn_bwd_call(dy, x, gamma, beta, mean, rstd, dx, accum, accum2, dx2, split_c, accumulate2, dgamma, dbeta, colsum,
+                                  colsum_ld, partial, n2, nx, set_images, set_stride, H, W, C, G, silu, dy_compact, ldx, stream), 1);
 }
 
 }  // extern "C"

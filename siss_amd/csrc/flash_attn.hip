@@ -700,10 +700,12 @@ __global__ __launch_bounds__(256) void flash_dkdv_reduce_kernel(const float* __r
 
 inline int fa_dpad(int D) { return D <= 64 ? 64 : (D <= 128 ? 128 : (D <= 192 ? 192 : 0)); }
 
-struct FwdArgs { const void *q, *k, *v; void* o; long ldq, ldk, ldv, ldo; float* lse2; };
-int fa_launch_fwd(const FwdArgs& a, int nbh, const FAShape& sh, float scale, bool pre, void* stream) {
-    const dim3 grid(sh.Sqp / kTQ, nbh);
-    const float sl2 = pre ? 1.f : scale * 1.4426950408889634f;
+inline int up64(int v) { return (v + 63) / 64 * 64; }
+// hoff / valid_k: see FAShape (merged layout: a.D, every key; head-split padded layout: 0 with a.H = 1 and padded a.D / a.Sq / a.Sk)
+int fa_launch_fwd(const FAFwdArgs& a, int hoff, int valid_k, void* stream) {
+    const FAShape sh{a.H, hoff, a.D, a.Sq, a.Sk, up64(a.Sq), up64(a.Sk), valid_k};
+    const dim3 grid(sh.Sqp / kTQ, a.B * a.H);
+    const float sl2 = a.pre ? 1.f : a.scale * 1.4426950408889634f;
     hipStream_t st = (hipStream_t)stream;
 #define FA_FWD(DP, DL)                                                                                                   \
     do {                                                                                                                  \
@@ -721,36 +723,19 @@ int fa_launch_fwd(const FwdArgs& a, int nbh, const FAShape& sh, float scale, boo
     return hipGetLastError() == hipSuccess ? SISS_OK : SISS_ERR_LAUNCH;
 }
 
-struct BwdArgs { const void *q, *k, *v, *o, *d_o; void *dq, *dk, *dv; long ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv;
-                 const float* lse2; float* delta; };
-// Few key tiles (cross attention: 77 keys = 2 tiles) leave the dK / dV grid at a fraction of the chip -- 128 blocks of 64 query
-// tiles each at B = 4.  Then the queries are cut into chunks (grid z), every block leaves its partial tiles in the library
-// workspace (siss_gemm_nt_set_workspace; launches on one stream at a time share it) and a small kernel sums them: deterministic,
-// no atomics.  Chunks: as many as bring the grid to ~1024 blocks, at least 4 query tiles each, within the workspace.
-void fa_qsplit(const FAShape& sh, int nbh, int DW, int& nch, int& qchunk, float*& ws) {
-    long bytes = 0;
-    ws = (float*)siss_workspace(&bytes);
-    const long base = (long)(sh.Skp / kTQ) * nbh;
-    const int qtiles = sh.Sqp / kTQ;
-    if (!ws || base >= 512 || qtiles < 8 || sh.Sk != sh.valid_k || sh.D % 4) return;
-    long n = (1024 + base - 1) / base;
-    if (n > qtiles / 4) n = qtiles / 4;
-    const long per_chunk = (long)nbh * sh.Skp * 2 * DW * (long)sizeof(float);
-    if (n * per_chunk > bytes - 4096) n = (bytes - 4096) / per_chunk;
-    if (n < 2) return;
-    const int tiles_per = (int)((qtiles + n - 1) / n);
-    nch = (qtiles + tiles_per - 1) / tiles_per;
-    qchunk = tiles_per * kTQ;
-}
 
 // pre: q holds scale * log2(e) * Q.  Scores then are base-2 logits as they come (sl2 = 1; only the augmented kernels have a
 // multiply to drop, hence their PRE forms), dQ is still the gradient with respect to the UNSCALED query -- scale * dS K as before --
 // and dK = scale * dS^T Q = ln(2) * dS^T q.
-int fa_launch_bwd(const BwdArgs& a, int nbh, int Bf, const FAShape& sh, float scale, bool pre, void* stream) {
-    const float sl2 = pre ? 1.f : scale * 1.4426950408889634f;
-    const float kscale = pre ? 0.6931471805599453f : scale;
+int fa_launch_bwd(const FABwdArgs& a, int hoff, int valid_k, void* stream) {
+    const FAShape sh{a.H, hoff, a.D, a.Sq, a.Sk, up64(a.Sq), up64(a.Sk), valid_k};
+    const int nbh = a.nB * a.H, Bf = a.Bf, pre = a.pre;
+    const float scale = a.scale, sl2 = pre ? 1.f : scale * 1.4426950408889634f, kscale = pre ? 0.6931471805599453f : scale;
     hipStream_t st = (hipStream_t)stream;
-    float* ws = nullptr;
+    // Few key tiles (cross attention: 77 keys = 2 tiles) leave the dK / dV grid at a fraction of the chip -- 128 blocks of 64 query tiles each
+    // at B = 4: the queries are cut into chunks on grid z (siss_fa_qchunks).  This family's reduce kernel wants every key valid, D % 4 == 0.
+    const bool qsplit_ok = sh.Sk == sh.valid_k && sh.D % 4 == 0;
+    const long chunk_floats = (long)nbh * sh.Skp * 2;         // (x DW columns: a chunk's dK and dV partials)
     // dQ first: it forms delta = rowsum(dO o O) for its 64 queries (when O is given) and leaves it for the dK / dV kernel
 #define FA_BWD(DP, AUG, DL, PRE)                                                                                                   \
     do {                                                                                                                     \
@@ -763,7 +748,7 @@ int fa_launch_bwd(const BwdArgs& a, int nbh, int Bf, const FAShape& sh, float sc
             (const bf16_t*)a.d_o, a.lddo, a.lse2, a.delta, (bf16_t*)a.dq, a.lddq, Bf, sh, scale, sl2);                      \
         constexpr int DW = (DL ? DL : FA<DP>::DT) * 16;                                                                     \
         int nch = 1, qchunk = sh.Sqp;                                                                                        \
-        fa_qsplit(sh, nbh, DW, nch, qchunk, ws);                                                                             \
+        float* const ws = qsplit_ok ? siss_fa_qchunks((long)(sh.Skp / kTQ) * nbh, sh.Sqp / kTQ, chunk_floats * DW * 4, nch, qchunk) : nullptr; \
         flash_bwd_dkdv_kernel<DP, AUG, DL, PRE><<<dim3(sh.Skp / kTQ, nbh, nch), kThreadsFA, smem_kv, st>>>(                     \
             (const bf16_t*)a.q, a.ldq, (const bf16_t*)a.k, a.ldk, (const bf16_t*)a.v, a.ldv, (const bf16_t*)a.d_o, a.lddo,  \
             a.lse2, a.delta, (bf16_t*)a.dk, a.lddk, (bf16_t*)a.dv, a.lddv, Bf, sh, kscale, sl2, qchunk, nch > 1 ? ws : nullptr); \
@@ -791,9 +776,22 @@ bool fa_shape_ok(int Sqp, int Skp, int Dp, int valid_k) {
     return Sqp > 0 && Skp > 0 && Sqp % kTQ == 0 && Skp % kTQ == 0 && (Dp == 64 || Dp == 128 || Dp == 192) && valid_k > 0 &&
            valid_k <= Skp;
 }
-inline int up64(int v) { return (v + 63) / 64 * 64; }
 
 }  // namespace
+
+float* siss_fa_qchunks(long kblocks, int qtiles, long chunk_bytes, int& nch, int& qchunk) {
+    long bytes = 0;
+    float* const ws = (float*)siss_workspace(&bytes);
+    if (!ws || kblocks >= 512 || qtiles < 8) return nullptr;
+    long n = (1024 + kblocks - 1) / kblocks;
+    if (n > qtiles / 4) n = qtiles / 4;
+    if (n * chunk_bytes > bytes - 4096) n = (bytes - 4096) / chunk_bytes;
+    if (n < 2) return nullptr;
+    const int tiles_per = (int)((qtiles + n - 1) / n);
+    nch = (qtiles + tiles_per - 1) / tiles_per;
+    qchunk = tiles_per * 64;
+    return ws;
+}
 
 extern "C" {
 
@@ -805,8 +803,10 @@ int siss_flash_attn_fwd(const void* q, const void* k, const void* v, void* o, fl
     SISS_CHECK_ARG(q && k && v && o && lse2 && BH > 0 && fa_shape_ok(Sq_pad, Sk_pad, D_pad, valid_k));
     SISS_CHECK_ARG(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) % 16 == 0);
     siss_count_dispatch(SISS_K_FLASH_FWD);
-    const FAShape sh{1, 0, D_pad, Sq_pad, Sk_pad, Sq_pad, Sk_pad, valid_k};
-    return fa_launch_fwd(FwdArgs{q, k, v, o, D_pad, D_pad, D_pad, D_pad, lse2}, BH, sh, scale, false, stream);
+    FAFwdArgs a = {};                                          // (batch, head) entries of one padded head each
+    a.q = q; a.k = k; a.v = v; a.o = o; a.ldq = a.ldk = a.ldv = a.ldo = D_pad; a.lse2 = lse2;
+    a.B = BH; a.H = 1; a.D = D_pad; a.Sq = Sq_pad; a.Sk = Sk_pad; a.scale = scale;
+    return fa_launch_fwd(a, 0, valid_k, stream);
 }
 
 // The same on the projections' own layout: q / o rows [B * Sq][ld >= H * D], k / v rows [B * Sk][ld], head h at columns
@@ -822,12 +822,12 @@ int siss_flash_attn_fwd_merged(const void* q, long ldq, const void* k, long ldk,
                    ldv >= (long)H * D && ldo >= (long)H * D);
     SISS_CHECK_ARG(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) % 16 == 0);
     siss_count_dispatch(SISS_K_FLASH_FWD);
-    {   // narrow heads on whole 128-row blocks: the 32x32x16 form (flash_attn32.hip)
-        const FA32FwdArgs a32{q, k, v, o, ldq, ldk, ldv, ldo, lse2, B, H, D, Sq, Sk, scale, q_prescaled != 0};
-        if (siss_fa32_fwd_takes(a32)) return siss_fa32_fwd(a32, stream);
-    }
-    const FAShape sh{H, D, D, Sq, Sk, up64(Sq), up64(Sk), Sk};
-    return fa_launch_fwd(FwdArgs{q, k, v, o, ldq, ldk, ldv, ldo, lse2}, B * H, sh, scale, q_prescaled != 0, stream);
+    FAFwdArgs a = {};
+    a.q = q; a.k = k; a.v = v; a.o = o; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.lse2 = lse2;
+    a.B = B; a.H = H; a.D = D; a.Sq = Sq; a.Sk = Sk; a.scale = scale; a.pre = q_prescaled != 0;
+    // narrow heads on whole 128-row blocks: the 32x32x16 form (flash_attn32.hip)
+    if (siss_fa32_fwd_takes(a)) return siss_fa32_fwd(a, stream);
+    return fa_launch_fwd(a, D, Sk, stream);
 }
 
 // dQ, dK, dV for nBH cotangent (batch, head) entries against BH forward entries (entry z uses forward entry z % BH: the
@@ -841,10 +841,11 @@ int siss_flash_attn_bwd(const void* q, const void* k, const void* v, const void*
     SISS_CHECK_ARG(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)d_o | (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) % 16 == 0);
     SISS_CHECK_ARG(((uintptr_t)lse2 | (uintptr_t)delta) % 16 == 0);
     siss_count_dispatch(SISS_K_FLASH_BWD);
-    const FAShape sh{1, 0, D_pad, Sq_pad, Sk_pad, Sq_pad, Sk_pad, valid_k};
-    const long d = D_pad;
-    return fa_launch_bwd(BwdArgs{q, k, v, nullptr, d_o, dq, dk, dv, d, d, d, d, d, d, d, d, lse2, const_cast<float*>(delta)},
-                         nBH, BH, sh, scale, false, stream);
+    FABwdArgs a = {};                                          // (batch, head) entries of one padded head each; no o: delta is given
+    a.q = q; a.k = k; a.v = v; a.d_o = d_o; a.dq = dq; a.dk = dk; a.dv = dv; a.lse2 = lse2; a.delta = const_cast<float*>(delta);
+    a.ldq = a.ldk = a.ldv = a.ldo = a.lddo = a.lddq = a.lddk = a.lddv = D_pad;
+    a.nB = nBH; a.Bf = BH; a.H = 1; a.D = D_pad; a.Sq = Sq_pad; a.Sk = Sk_pad; a.scale = scale;
+    return fa_launch_bwd(a, 0, valid_k, stream);
 }
 
 // The same on the projections' own layout (see siss_flash_attn_fwd_merged): nB cotangent batch entries against B forward ones
@@ -863,13 +864,13 @@ int siss_flash_attn_bwd_merged(const void* q, long ldq, const void* k, long ldk,
     SISS_CHECK_ARG(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)d_o | (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) % 16 == 0);
     SISS_CHECK_ARG(((uintptr_t)lse2 | (uintptr_t)delta) % 16 == 0);
     siss_count_dispatch(SISS_K_FLASH_BWD);
-    {   // narrow heads on whole 128-row blocks (SD's 4096-key self-attention sites): the 32x32x16 form (flash_attn32.hip)
-        const FA32Args a32{q, k, v, o, d_o, dq, dk, dv, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv, lse2, delta, nB, B, H, D, Sq, Sk, scale, q_prescaled != 0};
-        if (siss_fa32_bwd_takes(a32)) return siss_fa32_bwd(a32, stream);
-    }
-    const FAShape sh{H, D, D, Sq, Sk, up64(Sq), up64(Sk), Sk};
-    return fa_launch_bwd(BwdArgs{q, k, v, o, d_o, dq, dk, dv, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv, lse2, delta},
-                         nB * H, B, sh, scale, q_prescaled != 0, stream);
+    FABwdArgs a = {};
+    a.q = q; a.k = k; a.v = v; a.o = o; a.d_o = d_o; a.dq = dq; a.dk = dk; a.dv = dv; a.lse2 = lse2; a.delta = delta;
+    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.lddo = lddo; a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
+    a.nB = nB; a.Bf = B; a.H = H; a.D = D; a.Sq = Sq; a.Sk = Sk; a.scale = scale; a.pre = q_prescaled != 0;
+    // narrow heads on whole 128-row blocks (SD's 4096-key self-attention sites): the 32x32x16 form (flash_attn32.hip)
+    if (siss_fa32_bwd_takes(a)) return siss_fa32_bwd(a, stream);
+    return fa_launch_bwd(a, D, Sk, stream);
 }
 
 }  // extern "C"

@@ -730,10 +730,10 @@ bool shape_ok(int D, int Sq, int Sk) { return (D == 40 || D == 80 || D == 160) &
 // Shapes the 32x32 forms take: SD v1.5's head dims (40 / 80 / 160: five / ten / twenty 16-B chunks + the augmented one), whole
 // 128-query blocks, any number of keys (rows past the last key are neither moved nor counted), 16-B aligned rows.  Everything
 // else stays on flash_attn.hip's kernels.
-bool siss_fa32_bwd_takes(const FA32Args& a) { return shape_ok(a.D, a.Sq, a.Sk) && a.nB % a.Bf == 0; }
-bool siss_fa32_fwd_takes(const FA32FwdArgs& a) { return shape_ok(a.D, a.Sq, a.Sk); }
+bool siss_fa32_bwd_takes(const FABwdArgs& a) { return shape_ok(a.D, a.Sq, a.Sk) && a.nB % a.Bf == 0; }
+bool siss_fa32_fwd_takes(const FAFwdArgs& a) { return shape_ok(a.D, a.Sq, a.Sk); }
 
-int siss_fa32_bwd(const FA32Args& a, void* stream) {
+int siss_fa32_bwd(const FABwdArgs& a, void* stream) {
     if (!siss_fa32_bwd_takes(a)) return SISS_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     P32 p;
@@ -745,28 +745,10 @@ int siss_fa32_bwd(const FA32Args& a, void* stream) {
     p.scale = a.scale;
     p.kscale = a.pre ? 0.6931471805599453f : a.scale;
     p.c = a.pre ? 1.f : a.scale * 1.4426950408889634f;
-    // Few key blocks (cross-attention: one) leave the dK / dV grid at a fraction of the chip: the queries are cut into chunks of at
-    // least four 64-row tiles, as many as bring the grid to ~1024 blocks and fit the library workspace (partials + a reduce kernel).
+    // Few key blocks (cross-attention: one) leave the dK / dV grid at a fraction of the chip: query chunks (siss_fa_qchunks)
     const int nkb = (a.Sk + 127) / 128, DW = ((a.D + 15) / 16) * 16;
-    p.nch = 1; p.qchunk = a.Sq; p.part = nullptr;
-    {
-        long bytes = 0;
-        float* ws = (float*)siss_workspace(&bytes);
-        const long base = (long)nkb * p.nBH;
-        const int qtiles = a.Sq / 64;
-        if (ws && base < 512 && qtiles >= 8) {
-            long n = (1024 + base - 1) / base;
-            if (n > qtiles / 4) n = qtiles / 4;
-            const long per_chunk = (long)p.nBH * nkb * 128 * 2 * DW * (long)sizeof(float);
-            if (n * per_chunk > bytes - 4096) n = (bytes - 4096) / per_chunk;
-            if (n >= 2) {
-                const int tiles_per = (int)((qtiles + n - 1) / n);
-                p.nch = (qtiles + tiles_per - 1) / tiles_per;
-                p.qchunk = tiles_per * 64;
-                p.part = ws;
-            }
-        }
-    }
+    p.nch = 1; p.qchunk = a.Sq;
+    p.part = siss_fa_qchunks((long)nkb * p.nBH, a.Sq / 64, (long)p.nBH * nkb * 128 * 2 * DW * (long)sizeof(float), p.nch, p.qchunk);
     const unsigned gq = (unsigned)((long)(a.Sq / 128) * p.nBH), gk = (unsigned)((long)nkb * p.nch * p.nBH);
     const bool kt2 = a.D == 40 && !p.part && a.Sk % 256 == 0 && g_kt2;    // 256 keys per block (two 32-key tiles per wave)
 #define FA32_GO(NCH, PRE)                                                                                                  \
@@ -797,7 +779,7 @@ int siss_fa32_bwd(const FA32Args& a, void* stream) {
     return hipGetLastError() == hipSuccess ? SISS_OK : SISS_ERR_LAUNCH;
 }
 
-int siss_fa32_fwd(const FA32FwdArgs& a, void* stream) {
+int siss_fa32_fwd(const FAFwdArgs& a, void* stream) {
     if (!siss_fa32_fwd_takes(a)) return SISS_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     PF p;

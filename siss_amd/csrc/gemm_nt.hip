@@ -325,7 +325,7 @@ void* siss_workspace(long* bytes) {
     return g_slab_dev[dev];
 }
 
-static long g_dispatch[SISS_K_COUNT];
+static long g_dispatch[SISS_K_COUNT];      // one per SissKernelId (common.h): that enum is THE list of ids -- siss_dispatch_count's comment stops at 9
 void siss_count_dispatch(int k) { if (k >= 0 && k < SISS_K_COUNT) __atomic_fetch_add(&g_dispatch[k], 1L, __ATOMIC_RELAXED); }
 
 extern "C" {
@@ -385,9 +385,10 @@ namespace {
 // gemm_nt_dispatch AND by the host-side siss_conv3x3_*_takes queries, so the two cannot drift apart.  The kernel addresses its
 // tensors by 32-bit byte offsets (tensors of 4 GiB and more stay on the generic kernels); ldr / lda2 / ldcx = 0: operand absent.
 constexpr long kC3pMinTiles = 256;
-bool c3p_eligible(int M, int N, int Kp, int rows_per_image, int Wp, long lda, long ldc, long ldr, long lda2, int K2, long ldcx, int Nx) {
-    const long lim = 1L << 32;
-    if (M <= 0 || N <= 0 || Kp <= 0 || Kp % BK || N % BN || rows_per_image < 256 || (Wp != 0 && Wp < 8)) return false;
+bool c3p_eligible(const NTParams& p, long ldr, long lda2, long ldcx) {
+    const long lim = 1L << 32, lda = p.lda, ldc = p.ldc;
+    const int M = p.M, N = p.N, Kp = p.Kp, K2 = p.K2, Nx = p.Nx;
+    if (M <= 0 || N <= 0 || Kp <= 0 || Kp % BK || N % BN || p.rows_per_image < 256 || (p.Wp != 0 && p.Wp < 8)) return false;
     if ((long)cdiv(M, 128) * cdiv(N, BN) < kC3pMinTiles) return false;
     if (!((long)M * ldc * 2 < lim && (long)(M + 2) * lda * 2 < lim && (long)N * Kp * 2 < lim)) return false;
     if (ldr && !((long)M * ldr * 2 < lim)) return false;
@@ -403,79 +404,77 @@ bool is_conv3x3_pattern(const int* shifts, const int* coffs) {
     return true;
 }
 
-int gemm_nt_dispatch(const void* A, long lda, const void* W, void* C, long ldc, const float* bias,
-                     const float* rowbias, long ldrb, const void* R, long ldr, int M, int N, int Kp, int npanels,
-                     const int* shifts, const int* coffs, int rows_per_image, int Hp, int Wp, float alpha,
-                     int batch, long strideA, long strideW, long strideC, const float* rowsub, int mul_r, void* stream,
-                     float* qstats = nullptr, int* qstats_written = nullptr, int d2s = 0, const void* A2 = nullptr, long lda2 = 0,
-                     const void* W2 = nullptr, int K2 = 0, const float* bias2 = nullptr, const void* Wx = nullptr, void* Cx = nullptr,
-                     long ldcx = 0, int Nx = 0, int alpha_cols = 0, const int* phase_p0 = nullptr, const void* gg_h = nullptr,
-                     long gg_rows_x = 0, void* gf_y = nullptr) {
-    SISS_CHECK_ARG(A && W && C && shifts && coffs);
-    SISS_CHECK_ARG(alpha_cols == 0 || (alpha_cols > 0 && alpha_cols % 4 == 0 && npanels == 1 && !mul_r));   // (one-panel products: the generic kernel)
-    if (qstats_written) *qstats_written = 0;
+// One NT product as an entry point describes it: the kernel's parameter block (the dispatch fills in what it derives) plus what only the
+// host needs.  THE place of the defaults: all absent (null / 0) but alpha = 1, one panel (shift = coff = 0), rows_per_image = 1, batch = 1.
+struct NTCall {
+    static constexpr int kNoShift = 0;
+    NTParams p = {};
+    int batch = 1;
+    const int *shifts = &kNoShift, *coffs = &kNoShift;       // HOST arrays of p.npanels ints
+    const int* phase_p0 = nullptr;                           // HOST array of 5 panel offsets: the four d2s planes as one launch
+    float* qstats = nullptr; int* qstats_written = nullptr;  // asked for: p.qstats is set only where the persistent kernel forms them
+    void* stream;
+    NTCall(const void* A, long lda, const void* W, void* C, long ldc, int M, int N, int Kp, void* stream_) : stream(stream_) {
+        p.A = (const bf16_t*)A; p.lda = lda; p.W = (const bf16_t*)W; p.C = (bf16_t*)C; p.ldc = ldc;
+        p.M = M; p.N = N; p.Kp = Kp; p.npanels = 1; p.rows_per_image = 1; p.alpha = 1.f;
+    }
+    void panels(int npanels, const int* shifts_, const int* coffs_, int rows_per_image, int Hp, int Wp) {
+        p.npanels = npanels; shifts = shifts_; coffs = coffs_; p.rows_per_image = rows_per_image; p.Hp = Hp; p.Wp = Wp;
+    }
+    void residual(const void* R, long ldr) { p.R = (const bf16_t*)R; p.ldr = ldr; }
+};
+
+int gemm_nt_dispatch(const NTCall& c) {
+    NTParams p = c.p;
+    const int M = p.M, N = p.N, Kp = p.Kp, npanels = p.npanels, Hp = p.Hp, Wp = p.Wp, batch = c.batch;
+    SISS_CHECK_ARG(p.A && p.W && p.C && c.shifts && c.coffs);
+    SISS_CHECK_ARG(p.alpha_cols == 0 || (p.alpha_cols > 0 && p.alpha_cols % 4 == 0 && npanels == 1 && !p.mul_r));   // (one-panel products: the generic kernel)
+    if (c.qstats_written) *c.qstats_written = 0;
     SISS_CHECK_ARG(M > 0 && N > 0 && Kp > 0 && Kp % BK == 0 && npanels >= 1 && npanels <= kMaxPanels);
-    SISS_CHECK_ARG(lda % 8 == 0 && ldc % 8 == 0 && (!R || ldr % 8 == 0) && batch >= 1);
-    SISS_CHECK_ARG(((uintptr_t)A | (uintptr_t)W | (uintptr_t)C | (uintptr_t)R) % 16 == 0);
-    SISS_CHECK_ARG(strideA % 8 == 0 && strideW % 8 == 0 && strideC % 8 == 0);
-    SISS_CHECK_ARG(rows_per_image > 0 && (Hp == 0 || (long)Hp * Wp == rows_per_image));
-    NTParams p;
-    p.A = (const bf16_t*)A; p.W = (const bf16_t*)W; p.C = (bf16_t*)C;
-    p.bias = bias; p.rowbias = rowbias; p.R = (const bf16_t*)R;
-    p.lda = lda; p.ldc = ldc; p.ldr = ldr; p.ldrb = ldrb;
-    p.strideA = strideA; p.strideW = strideW; p.strideC = strideC;
-    p.M = M; p.N = N; p.Kp = Kp; p.npanels = npanels;
-    p.rows_per_image = rows_per_image; p.Hp = Hp; p.Wp = Wp; p.alpha = alpha; p.alpha_cols = alpha_cols;
-    p.inv_wp = Wp > 0 ? 1.0f / (float)Wp : 0.f;
-    p.ksplit = 1; p.slab = nullptr; p.qstats = nullptr; p.d2s = d2s;
-    p.gg_h = (const bf16_t*)gg_h; p.gg_rows_x = gg_rows_x;
-    p.gf_y = (bf16_t*)gf_y;
-    SISS_CHECK_ARG(!gf_y || (npanels == 1 && Hp == 0 && !d2s && !R && !rowbias && !rowsub && batch == 1 && !gg_h && N % 128 == 0 &&
-                             ldc == N && (uintptr_t)gf_y % 16 == 0 && alpha == 1.f && alpha_cols == 0));
-    SISS_CHECK_ARG(!gg_h || (gg_rows_x > 0 && npanels == 1 && Hp == 0 && !d2s && !R && !bias && !rowbias && !rowsub && batch == 1 &&
-                             N % 8 == 0 && ldc >= 2L * N && (uintptr_t)gg_h % 16 == 0 && alpha == 1.f));
-    p.A2 = (const bf16_t*)A2; p.W2 = (const bf16_t*)W2; p.bias2 = A2 ? bias2 : nullptr; p.lda2 = lda2; p.K2 = A2 ? K2 : 0;
-    p.Wx = (const bf16_t*)Wx; p.Cx = (bf16_t*)Cx; p.ldcx = ldcx; p.Nx = Cx ? Nx : 0;
-    SISS_CHECK_ARG(!Cx || (Wx && Nx > 0 && Nx % BN == 0 && ldcx % 8 == 0 && ldcx >= Nx && npanels == 9 && !qstats && !A2 &&
-                           ((uintptr_t)Wx | (uintptr_t)Cx) % 16 == 0));
-    SISS_CHECK_ARG(!A2 || (W2 && K2 > 0 && K2 % BK == 0 && lda2 % 8 == 0 && lda2 >= K2 && !R && npanels == 9 &&
-                           ((uintptr_t)A2 | (uintptr_t)W2) % 16 == 0 && (!bias2 || (uintptr_t)bias2 % 16 == 0)));
+    SISS_CHECK_ARG(p.lda % 8 == 0 && p.ldc % 8 == 0 && (!p.R || p.ldr % 8 == 0) && batch >= 1);
+    SISS_CHECK_ARG(((uintptr_t)p.A | (uintptr_t)p.W | (uintptr_t)p.C | (uintptr_t)p.R) % 16 == 0);
+    SISS_CHECK_ARG(p.strideA % 8 == 0 && p.strideW % 8 == 0 && p.strideC % 8 == 0);
+    SISS_CHECK_ARG(p.rows_per_image > 0 && (Hp == 0 || (long)Hp * Wp == p.rows_per_image));
+    p.inv_wp = Wp > 0 ? 1.0f / (float)Wp : 0.f; p.ksplit = 1;
+    SISS_CHECK_ARG(!p.gf_y || (npanels == 1 && Hp == 0 && !p.d2s && !p.R && !p.rowbias && !p.rowsub && batch == 1 && !p.gg_h && N % 128 == 0 &&
+                               p.ldc == N && (uintptr_t)p.gf_y % 16 == 0 && p.alpha == 1.f && p.alpha_cols == 0));
+    SISS_CHECK_ARG(!p.gg_h || (p.gg_rows_x > 0 && npanels == 1 && Hp == 0 && !p.d2s && !p.R && !p.bias && !p.rowbias && !p.rowsub && batch == 1 &&
+                               N % 8 == 0 && p.ldc >= 2L * N && (uintptr_t)p.gg_h % 16 == 0 && p.alpha == 1.f));
+    SISS_CHECK_ARG(!p.Cx || (p.Wx && p.Nx > 0 && p.Nx % BN == 0 && p.ldcx % 8 == 0 && p.ldcx >= p.Nx && npanels == 9 && !c.qstats && !p.A2 &&
+                             ((uintptr_t)p.Wx | (uintptr_t)p.Cx) % 16 == 0));
+    SISS_CHECK_ARG(!p.A2 || (p.W2 && p.K2 > 0 && p.K2 % BK == 0 && p.lda2 % 8 == 0 && p.lda2 >= p.K2 && !p.R && npanels == 9 &&
+                             ((uintptr_t)p.A2 | (uintptr_t)p.W2) % 16 == 0 && (!p.bias2 || (uintptr_t)p.bias2 % 16 == 0)));
 #ifdef SISS_PROBE
     { const char* e = getenv("SISS_NT_ABLATE"); p.ablate = e ? atoi(e) : 0; }
     { const char* e = getenv("SISS_NT_DEBUG_PTR"); p.dbg = e ? (long long*)strtoull(e, nullptr, 0) : nullptr; }
 #endif
-    SISS_CHECK_ARG(d2s == 0 || (d2s >= 1 && d2s <= 4 && Hp > 2 && Wp > 2 && batch == 1 && !rowsub && !mul_r));
-    p.nphase = 0;
-    for (int i = 0; i < 5; ++i) p.ph_p0[i] = 0;
-    if (phase_p0) {                                            // the four planes' products as ONE launch (siss_gemm_nt_d2s_phases)
-        SISS_CHECK_ARG(d2s && phase_p0[0] == 0 && phase_p0[4] == npanels && !qstats && !A2 && !Cx);
-        for (int i = 0; i < 4; ++i) SISS_CHECK_ARG(phase_p0[i + 1] > phase_p0[i]);
+    SISS_CHECK_ARG(p.d2s == 0 || (p.d2s >= 1 && p.d2s <= 4 && Hp > 2 && Wp > 2 && batch == 1 && !p.rowsub && !p.mul_r));
+    if (c.phase_p0) {                                          // the four planes' products as ONE launch (siss_gemm_nt_d2s_phases)
+        SISS_CHECK_ARG(p.d2s && c.phase_p0[0] == 0 && c.phase_p0[4] == npanels && !c.qstats && !p.A2 && !p.Cx);
+        for (int i = 0; i < 4; ++i) SISS_CHECK_ARG(c.phase_p0[i + 1] > c.phase_p0[i]);
         p.nphase = 4;
-        for (int i = 0; i < 5; ++i) p.ph_p0[i] = phase_p0[i];
+        for (int i = 0; i < 5; ++i) p.ph_p0[i] = c.phase_p0[i];
     }
-    p.rowsub = rowsub; p.mul_r = mul_r;
-    SISS_CHECK_ARG(!mul_r || (R && Hp == 0));              // the multiplicative epilogue has no halo form
-    const int dev_ = siss_current_device();
-    float* const g_slab = dev_ >= 0 ? g_slab_dev[dev_] : nullptr;
-    const long g_slab_bytes = dev_ >= 0 ? g_slab_bytes_dev[dev_] : 0;
-    SISS_CHECK_ARG((!rowbias && Hp == 0) || rows_per_image >= 64);   // <= 3 images per 128/256-row tile
-    SISS_CHECK_ARG(N % 8 == 0 && (!rowbias || ldrb % 4 == 0) && (!bias || (uintptr_t)bias % 16 == 0));
-    for (int i = 0; i < kMaxPanels; ++i) { p.shift[i] = i < npanels ? shifts[i] : 0; p.coff[i] = i < npanels ? coffs[i] : 0; }
-    for (int i = 0; i < npanels; ++i) SISS_CHECK_ARG(p.coff[i] % 8 == 0);
+    SISS_CHECK_ARG(!p.mul_r || (p.R && Hp == 0));          // the multiplicative epilogue has no halo form
+    long g_slab_bytes = 0;
+    float* const g_slab = (float*)siss_workspace(&g_slab_bytes);     // (null, 0 without one)
+    SISS_CHECK_ARG((!p.rowbias && Hp == 0) || p.rows_per_image >= 64);   // <= 3 images per 128/256-row tile
+    SISS_CHECK_ARG(N % 8 == 0 && (!p.rowbias || p.ldrb % 4 == 0) && (!p.bias || (uintptr_t)p.bias % 16 == 0));
+    for (int i = 0; i < npanels; ++i) { p.shift[i] = c.shifts[i]; p.coff[i] = c.coffs[i]; SISS_CHECK_ARG(p.coff[i] % 8 == 0); }
     // 3x3 filters on grids of at least kC3pMinTiles 128-row tiles: the persistent kernel (gemm_nt_c3p.hip; A tile shared by the three
     // kx taps, DMA / store waves beside the MFMA waves).  Measured sweep of the threshold (round 1, 2048 .. 32): 256 gives the
     // shortest step.  It addresses its tensors by 32-bit byte offsets: tensors of 4 GiB and more stay on the kernels below.
     {
-        const bool conv3 = npanels == 9 && batch == 1 && !rowsub && !mul_r && !d2s && is_conv3x3_pattern(p.shift, p.coff);
-        if (conv3 && c3p_eligible(M, N, Kp, rows_per_image, Wp, lda, ldc, R ? ldr : 0, A2 ? lda2 : 0, K2, Cx ? ldcx : 0, Nx)) {
-            if (qstats && Hp > 0 && ((uintptr_t)qstats % 16) == 0) {
-                p.qstats = qstats;                          // only the persistent kernel forms them; the caller is told
-                if (qstats_written) *qstats_written = 1;
+        const bool conv3 = npanels == 9 && batch == 1 && !p.rowsub && !p.mul_r && !p.d2s && is_conv3x3_pattern(p.shift, p.coff);
+        if (conv3 && c3p_eligible(p, p.R ? p.ldr : 0, p.A2 ? p.lda2 : 0, p.Cx ? p.ldcx : 0)) {
+            if (c.qstats && Hp > 0 && ((uintptr_t)c.qstats % 16) == 0) {
+                p.qstats = c.qstats;                        // only the persistent kernel forms them; the caller is told
+                if (c.qstats_written) *c.qstats_written = 1;
             }
-            return siss_launch_gemm_nt_c3p(&p, stream);
+            return siss_launch_gemm_nt_c3p(&p, c.stream);
         }
     }
-    SISS_CHECK_ARG(!A2 && !Cx);                                // only the persistent kernel folds a shortcut in (callers ask siss_conv3x3_*_takes first)
+    SISS_CHECK_ARG(!p.A2 && !p.Cx);                              // only the persistent kernel folds a shortcut in (callers ask siss_conv3x3_*_takes first)
     // Large grids: single-buffered blocks at 4 per CU (latency hidden by the other three) measured 10-15 %
     // faster than double-buffered blocks at 2 per CU; small grids (< 4 blocks per CU) keep the double buffer.
     const long tiles128 = (long)cdiv(M, 128) * cdiv(N, BN) * batch * (p.nphase ? p.nphase : 1);
@@ -484,8 +483,8 @@ int gemm_nt_dispatch(const void* A, long lda, const void* W, void* C, long ldc, 
     // 111.5 / 111.8 ms, B = 4 46.0 / 46.9 / 45.8 / 46.2 / 46.3 ms, CelebA-HQ unchanged -- e.g. 8192 x 1280 x K 10240: 640 tiles)
     if (tiles128 > 512) {
         // widths that are multiples of 160 but not of 128 (320, 960): 128 x 160 tiles -- no dead columns, two thirds of the A re-reads
-        if (N % 160 == 0 && N % BN != 0 && !p.gg_h && !p.gf_y && g_wide_tiles) return launch_nt<128, 4, 1, 160>(p, batch, (hipStream_t)stream);
-        return launch_nt<128, 4, 1>(p, batch, (hipStream_t)stream);
+        if (N % 160 == 0 && N % BN != 0 && !p.gg_h && !p.gf_y && g_wide_tiles) return launch_nt<128, 4, 1, 160>(p, batch, (hipStream_t)c.stream);
+        return launch_nt<128, 4, 1>(p, batch, (hipStream_t)c.stream);
     }
     // at most one block per CU anyway: a 4-deep ring (128 KiB) keeps three K-steps of DMA in flight, so a step
     // costs its MFMA time instead of an L2 round trip (the 8x8 .. 32x32 layers are bound by the serial K loop)
@@ -505,11 +504,11 @@ int gemm_nt_dispatch(const void* A, long lda, const void* W, void* C, long ldc, 
         if (batch == 1 && !p.nphase && tiles128 > 128 && steps >= 24 && g_slab &&
             (long)tiles128 * 2 * 128 * BN * (long)sizeof(float) <= g_slab_bytes) {
             p.ksplit = 2; p.slab = g_slab;
-            return launch_nt<128, 4, 2>(p, batch, (hipStream_t)stream);
+            return launch_nt<128, 4, 2>(p, batch, (hipStream_t)c.stream);
         }
-        return launch_nt<128, 4, 4>(p, batch, (hipStream_t)stream);
+        return launch_nt<128, 4, 4>(p, batch, (hipStream_t)c.stream);
     }
-    return launch_nt<128, 4, 2>(p, batch, (hipStream_t)stream);
+    return launch_nt<128, 4, 2>(p, batch, (hipStream_t)c.stream);
 }
 }  // namespace
 
@@ -521,17 +520,19 @@ int siss_gemm_nt(const void* A, long lda, const void* W, void* C, long ldc, cons
                  const float* rowbias, long ldrb, const void* R, long ldr, int M, int N, int Kp, int npanels,
                  const int* shifts, const int* coffs, int rows_per_image, int Hp, int Wp, float alpha,
                  int batch, long strideA, long strideW, long strideC, void* stream) {
-    return gemm_nt_dispatch(A, lda, W, C, ldc, bias, rowbias, ldrb, R, ldr, M, N, Kp, npanels, shifts, coffs,
-                            rows_per_image, Hp, Wp, alpha, batch, strideA, strideW, strideC, nullptr, 0, stream);
+    NTCall c(A, lda, W, C, ldc, M, N, Kp, stream); c.panels(npanels, shifts, coffs, rows_per_image, Hp, Wp);
+    c.p.bias = bias; c.p.rowbias = rowbias; c.p.ldrb = ldrb; c.residual(R, ldr); c.p.alpha = alpha;
+    c.batch = batch; c.p.strideA = strideA; c.p.strideW = strideW; c.p.strideC = strideC;
+    return gemm_nt_dispatch(c);
 }
 
 // siss_gemm_nt (one panel) whose alpha scales only the FIRST alpha_cols output columns (alpha_cols % 4 == 0; the others take 1): the
 // query part of a fused q / k / v projection, pre-scaled by softmax_scale * log2(e) for siss_flash_attn_*_merged(..., q_prescaled = 1).
 int siss_gemm_nt_alpha_cols(const void* A, long lda, const void* W, void* C, long ldc, const float* bias, const void* R, long ldr,
                             int M, int N, int Kp, float alpha, int alpha_cols, void* stream) {
-    const int zero = 0;
-    return gemm_nt_dispatch(A, lda, W, C, ldc, bias, nullptr, N, R, ldr, M, N, Kp, 1, &zero, &zero, 1, 0, 0, alpha, 1, 0, 0, 0,
-                            nullptr, 0, stream, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, alpha_cols);
+    NTCall c(A, lda, W, C, ldc, M, N, Kp, stream);
+    c.p.bias = bias; c.residual(R, ldr); c.p.alpha = alpha; c.p.alpha_cols = alpha_cols;
+    return gemm_nt_dispatch(c);
 }
 
 // siss_gemm_nt that may also hand the GroupNorm statistics of its OUTPUT to the consumer.  `qstats` (f32, siss_conv_qstats_words
@@ -544,8 +545,9 @@ int siss_gemm_nt_qstats(const void* A, long lda, const void* W, void* C, long ld
                         const int* shifts, const int* coffs, int rows_per_image, int Hp, int Wp, float alpha,
                         float* qstats, int* written, void* stream) {
     SISS_CHECK_ARG(qstats && written);
-    return gemm_nt_dispatch(A, lda, W, C, ldc, bias, rowbias, ldrb, R, ldr, M, N, Kp, npanels, shifts, coffs,
-                            rows_per_image, Hp, Wp, alpha, 1, 0, 0, 0, nullptr, 0, stream, qstats, written);
+    NTCall c(A, lda, W, C, ldc, M, N, Kp, stream); c.panels(npanels, shifts, coffs, rows_per_image, Hp, Wp);
+    c.p.bias = bias; c.p.rowbias = rowbias; c.p.ldrb = ldrb; c.residual(R, ldr); c.p.alpha = alpha; c.qstats = qstats; c.qstats_written = written;
+    return gemm_nt_dispatch(c);
 }
 
 // A ResnetBlock2D's tail in ONE product: C = conv3x3(A; W) + conv1x1(A2; W2) + bias + bias2 (+ rowbias) -- the 1x1 shortcut convolution
@@ -560,15 +562,19 @@ int siss_gemm_nt_qstats(const void* A, long lda, const void* W, void* C, long ld
 // has) and, in every launch with a residual, R at halo rows (loaded, then replaced by zero with a select).  Their content never
 // reaches C.  A is read at rows [min shift, M - 1 + max shift] of the panels' column windows and nowhere else.
 int siss_conv3x3_sc_takes(int M, int N, int Kp, int K2, int rows_per_image, int Wp, long lda, long ldc, long lda2) {
-    return lda2 > 0 && c3p_eligible(M, N, Kp, rows_per_image, Wp, lda, ldc, 0, lda2, K2, 0, 0) ? 1 : 0;
+    NTParams p = {};
+    p.M = M; p.N = N; p.Kp = Kp; p.K2 = K2; p.rows_per_image = rows_per_image; p.Wp = Wp; p.lda = lda; p.ldc = ldc;
+    return lda2 > 0 && c3p_eligible(p, 0, lda2, 0) ? 1 : 0;
 }
 int siss_conv3x3_sc(const void* A, long lda, const void* W, void* C, long ldc, const float* bias, const float* rowbias, long ldrb,
                     const void* A2, long lda2, const void* W2, int K2, const float* bias2, int M, int N, int Kp, const int* shifts,
                     const int* coffs, int rows_per_image, int Hp, int Wp, float* qstats, int* written, void* stream) {
     SISS_CHECK_ARG(A2 && W2 && shifts && coffs && is_conv3x3_pattern(shifts, coffs));     // (a 3x3 filter's nine panels: layout.conv3x3_panels)
     SISS_CHECK_ARG(siss_conv3x3_sc_takes(M, N, Kp, K2, rows_per_image, Wp, lda, ldc, lda2));
-    return gemm_nt_dispatch(A, lda, W, C, ldc, bias, rowbias, ldrb, nullptr, 0, M, N, Kp, 9, shifts, coffs, rows_per_image, Hp, Wp,
-                            1.0f, 1, 0, 0, 0, nullptr, 0, stream, qstats, written, 0, A2, lda2, W2, K2, bias2);
+    NTCall c(A, lda, W, C, ldc, M, N, Kp, stream); c.panels(9, shifts, coffs, rows_per_image, Hp, Wp);
+    c.p.bias = bias; c.p.rowbias = rowbias; c.p.ldrb = ldrb; c.qstats = qstats; c.qstats_written = written;
+    c.p.A2 = (const bf16_t*)A2; c.p.lda2 = lda2; c.p.W2 = (const bf16_t*)W2; c.p.K2 = K2; c.p.bias2 = bias2;
+    return gemm_nt_dispatch(c);
 }
 
 // The backward of that block tail in ONE product: conv2's dgrad  C = sum_taps A(shifted) . W  (nine panels, W = the transposed tap copies)
@@ -578,15 +584,19 @@ int siss_conv3x3_sc(const void* A, long lda, const void* W, void* C, long ldc, c
 // siss_conv3x3_dgrad_sc_takes: whether a product of this shape lands on that kernel (else: two siss_gemm_nt calls).
 // (ldr: the row stride of R, 0 without one -- R is addressed by 32-bit offsets too)
 int siss_conv3x3_dgrad_sc_takes(int M, int N, int Kp, int Nx, int rows_per_image, int Wp, long lda, long ldc, long ldcx, long ldr) {
-    return ldcx > 0 && c3p_eligible(M, N, Kp, rows_per_image, Wp, lda, ldc, ldr, 0, 0, ldcx, Nx) ? 1 : 0;
+    NTParams p = {};
+    p.M = M; p.N = N; p.Kp = Kp; p.Nx = Nx; p.rows_per_image = rows_per_image; p.Wp = Wp; p.lda = lda; p.ldc = ldc;
+    return ldcx > 0 && c3p_eligible(p, ldr, 0, ldcx) ? 1 : 0;
 }
 int siss_conv3x3_dgrad_sc(const void* A, long lda, const void* W, void* C, long ldc, const void* R, long ldr, const void* Wx, void* Cx,
                           long ldcx, int Nx, int M, int N, int Kp, const int* shifts, const int* coffs, int rows_per_image, int Hp,
                           int Wp, void* stream) {
     SISS_CHECK_ARG(Wx && Cx && shifts && coffs && is_conv3x3_pattern(shifts, coffs));
     SISS_CHECK_ARG(siss_conv3x3_dgrad_sc_takes(M, N, Kp, Nx, rows_per_image, Wp, lda, ldc, ldcx, R ? ldr : 0));
-    return gemm_nt_dispatch(A, lda, W, C, ldc, nullptr, nullptr, N, R, ldr, M, N, Kp, 9, shifts, coffs, rows_per_image, Hp, Wp,
-                            1.0f, 1, 0, 0, 0, nullptr, 0, stream, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, Wx, Cx, ldcx, Nx);
+    NTCall c(A, lda, W, C, ldc, M, N, Kp, stream); c.panels(9, shifts, coffs, rows_per_image, Hp, Wp);
+    c.residual(R, ldr);
+    c.p.Wx = (const bf16_t*)Wx; c.p.Cx = (bf16_t*)Cx; c.p.ldcx = ldcx; c.p.Nx = Nx;
+    return gemm_nt_dispatch(c);
 }
 
 // siss_gemm_nt whose rows are the pixels of ONE space-to-depth plane (plane = 2 py + px) of a stride-2 convolution's input: the
@@ -598,8 +608,9 @@ int siss_gemm_nt_d2s(const void* A, long lda, const void* W, void* C, long ldc, 
                      int Kp, int npanels, const int* shifts, const int* coffs, int rows_per_image, int Hp, int Wp,
                      int plane, void* stream) {
     SISS_CHECK_ARG(plane >= 0 && plane < 4);
-    return gemm_nt_dispatch(A, lda, W, C, ldc, nullptr, nullptr, N, R, ldr, M, N, Kp, npanels, shifts, coffs,
-                            rows_per_image, Hp, Wp, 1.0f, 1, 0, 0, 0, nullptr, 0, stream, nullptr, nullptr, 1 + plane);
+    NTCall c(A, lda, W, C, ldc, M, N, Kp, stream); c.panels(npanels, shifts, coffs, rows_per_image, Hp, Wp);
+    c.residual(R, ldr); c.p.d2s = 1 + plane;
+    return gemm_nt_dispatch(c);
 }
 // The same with a bias (f32 [N], added before the one rounding): one PHASE of a sub-pixel upsample convolution -- the rows are the
 // LOW-resolution pixels, plane = 2 py + px is the phase, the panels its 2x2 taps (siss_upsample_phase_weights), and the epilogue
@@ -608,8 +619,9 @@ int siss_gemm_nt_d2s_bias(const void* A, long lda, const void* W, void* C, long 
                           int npanels, const int* shifts, const int* coffs, int rows_per_image, int Hp, int Wp, int plane,
                           void* stream) {
     SISS_CHECK_ARG(plane >= 0 && plane < 4);
-    return gemm_nt_dispatch(A, lda, W, C, ldc, bias, nullptr, N, nullptr, 0, M, N, Kp, npanels, shifts, coffs,
-                            rows_per_image, Hp, Wp, 1.0f, 1, 0, 0, 0, nullptr, 0, stream, nullptr, nullptr, 1 + plane);
+    NTCall c(A, lda, W, C, ldc, M, N, Kp, stream); c.panels(npanels, shifts, coffs, rows_per_image, Hp, Wp);
+    c.p.bias = bias; c.p.d2s = 1 + plane;
+    return gemm_nt_dispatch(c);
 }
 
 // The FOUR planes of siss_gemm_nt_d2s / siss_gemm_nt_d2s_bias as one launch: plane z runs panels [phase_p0[z], phase_p0[z + 1]) of
@@ -623,9 +635,9 @@ int siss_gemm_nt_d2s_phases(const void* A, long lda, const void* W, void* C, lon
                             int M, int N, int Kp, const int* phase_p0, const int* shifts, const int* coffs, int rows_per_image,
                             int Hp, int Wp, void* stream) {
     SISS_CHECK_ARG(phase_p0 && phase_p0[4] >= 4 && phase_p0[4] <= kMaxPanels);
-    return gemm_nt_dispatch(A, lda, W, C, ldc, bias, nullptr, N, R, ldr, M, N, Kp, phase_p0[4], shifts, coffs,
-                            rows_per_image, Hp, Wp, 1.0f, 1, 0, 0, 0, nullptr, 0, stream, nullptr, nullptr, 1, nullptr, 0, nullptr, 0,
-                            nullptr, nullptr, nullptr, 0, 0, 0, phase_p0);
+    NTCall c(A, lda, W, C, ldc, M, N, Kp, stream); c.panels(phase_p0[4], shifts, coffs, rows_per_image, Hp, Wp);
+    c.p.bias = bias; c.residual(R, ldr); c.p.d2s = 1; c.phase_p0 = phase_p0;
+    return gemm_nt_dispatch(c);
 }
 
 // The dgrad of GEGLU's output projection with the GEGLU backward in its epilogue (diffusers FeedForward: out = a * gelu(g), [a | g] =
@@ -636,10 +648,9 @@ int siss_gemm_nt_d2s_phases(const void* A, long lda, const void* W, void* C, lon
 int siss_gemm_nt_geglu_bwd(const void* A, long lda, const void* W, void* dh, const void* h, long rows_x, int M, int N, int Kp,
                            void* stream) {
     SISS_CHECK_ARG(h && rows_x > 0);
-    static const int zero = 0;
-    return gemm_nt_dispatch(A, lda, W, dh, 2L * N, nullptr, nullptr, N, nullptr, 0, M, N, Kp, 1, &zero, &zero, 1, 0, 0, 1.0f, 1, 0, 0, 0,
-                            nullptr, 0, stream, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, 0, nullptr,
-                            h, rows_x);
+    NTCall c(A, lda, W, dh, 2L * N, M, N, Kp, stream);
+    c.p.gg_h = (const bf16_t*)h; c.p.gg_rows_x = rows_x;
+    return gemm_nt_dispatch(c);
 }
 
 // GEGLU's input projection with the GEGLU forward in its epilogue: h[r][0 : 2F] = A[r] . W^T + bias (W: [2F][Kp], rows 0 .. F-1 the
@@ -649,10 +660,9 @@ int siss_gemm_nt_geglu_bwd(const void* A, long lda, const void* W, void* dh, con
 int siss_gemm_nt_geglu_fwd(const void* A, long lda, const void* W, const float* bias, void* h, void* y, int M, int F, int Kp,
                            void* stream) {
     SISS_CHECK_ARG(y && F > 0 && F % 64 == 0);
-    static const int zero = 0;
-    return gemm_nt_dispatch(A, lda, W, h, 2L * F, bias, nullptr, 0, nullptr, 0, M, 2 * F, Kp, 1, &zero, &zero, 1, 0, 0, 1.0f, 1, 0, 0, 0,
-                            nullptr, 0, stream, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, 0, nullptr,
-                            nullptr, 0, y);
+    NTCall c(A, lda, W, h, 2L * F, M, 2 * F, Kp, stream);
+    c.p.bias = bias; c.p.gf_y = (bf16_t*)y;
+    return gemm_nt_dispatch(c);
 }
 
 // floats in the `qstats` buffer of a product with M rows and N output channels
@@ -668,9 +678,10 @@ int siss_gemm_nt_mulsub(const void* A, long lda, const void* W, void* C, long ld
                         const float* rowsub, int M, int N, int Kp, float alpha, int batch, long strideA, long strideW,
                         long strideC, void* stream) {
     SISS_CHECK_ARG(R && rowsub);
-    static const int zero = 0;
-    return gemm_nt_dispatch(A, lda, W, C, ldc, nullptr, nullptr, N, R, ldr, M, N, Kp, 1, &zero, &zero, 1, 0, 0, alpha,
-                            batch, strideA, strideW, strideC, rowsub, 1, stream);
+    NTCall c(A, lda, W, C, ldc, M, N, Kp, stream);
+    c.residual(R, ldr); c.p.rowsub = rowsub; c.p.mul_r = 1; c.p.alpha = alpha;
+    c.batch = batch; c.p.strideA = strideA; c.p.strideW = strideW; c.p.strideC = strideC;
+    return gemm_nt_dispatch(c);
 }
 
 }  // extern "C"

@@ -17,6 +17,7 @@
 // Split-K over row ranges; partial tiles are accumulated with f32 global atomics (no-return
 // global_atomic_add_f32; 16 consecutive floats per lane group).
 #include "common.h"
+#include "tn_job.h"
 #include <algorithm>
 #include <mutex>
 #include <type_traits>
@@ -637,31 +638,24 @@ int launch_tn(const TNParams& p, hipStream_t st) {
 
 }  // namespace
 
-// argument list of siss_gemm_tn as a struct (include/siss_hip.h declares the same layout)
-struct siss_tn_job {
-    const void* Y; long ldy; const void* X; long ldx; float* dW; long set_stride;
-    int N, C, npanels, nsets, rows_per_set, row_begin, row_end, nsplits;
-    long x_set_rows;
-    const void* zero_page; float* dbias; float* dbias2;
-    int shifts[9]; int coffs[9];
-    long bias_set_stride;                 // floats between the sets of dbias / dbias2; 0 = set_stride (siss_gemm_tn_bs's extra argument)
-};
+static_assert(sizeof(((siss_tn_job*)nullptr)->shifts) == sizeof(((TNParams*)nullptr)->shift), "a job holds the kernel's panel count inline");
 
-static int tn_setup(const void* Y, long ldy, const void* X, long ldx, float* dW, long set_stride, int N, int C,
-                    int npanels, const int* shifts, const int* coffs, int nsets, int rows_per_set,
-                    long x_set_rows, int row_begin, int row_end, int nsplits, const void* zero_page,
-                    float* dbias, float* dbias2, bool grouped, TNParams& p, bool& fused3_out) {
-    SISS_CHECK_ARG(Y && X && dW && shifts && coffs && zero_page);
+// One job -> the kernel's parameter block: checks, then variant (fused 3-tap / one-tap) and split count by the rules above siss_gemm_tn
+static int tn_setup(const siss_tn_job& j, bool grouped, TNParams& p, bool& fused3_out) {
+    const int N = j.N, C = j.C, npanels = j.npanels, nsets = j.nsets;
+    int nsplits = j.nsplits;
+    SISS_CHECK_ARG(j.Y && j.X && j.dW && j.zero_page);
     SISS_CHECK_ARG(N > 0 && C > 0 && npanels >= 1 && npanels <= kMaxPanels && nsets >= 1);
-    SISS_CHECK_ARG(ldy % 8 == 0 && ldx % 8 == 0 && C % 8 == 0);   // N may be ragged (masked at the store)
-    SISS_CHECK_ARG(((uintptr_t)Y | (uintptr_t)X | (uintptr_t)zero_page) % 16 == 0 && (uintptr_t)dW % 4 == 0);
-    SISS_CHECK_ARG(row_begin >= 0 && row_end > row_begin && row_end <= rows_per_set);
-    p.Y = (const bf16_t*)Y; p.X = (const bf16_t*)X; p.dW = dW; p.zero_page = (const bf16_t*)zero_page;
-    p.dbias = dbias; p.dbias2 = dbias ? dbias2 : nullptr;
-    p.ldy = ldy; p.ldx = ldx; p.set_stride = set_stride; p.bias_stride = set_stride; p.x_set_rows = x_set_rows;
+    SISS_CHECK_ARG(j.ldy % 8 == 0 && j.ldx % 8 == 0 && C % 8 == 0);   // N may be ragged (masked at the store)
+    SISS_CHECK_ARG(((uintptr_t)j.Y | (uintptr_t)j.X | (uintptr_t)j.zero_page) % 16 == 0 && (uintptr_t)j.dW % 4 == 0);
+    SISS_CHECK_ARG(j.row_begin >= 0 && j.row_end > j.row_begin && j.row_end <= j.rows_per_set);
+    p.Y = (const bf16_t*)j.Y; p.X = (const bf16_t*)j.X; p.dW = j.dW; p.zero_page = (const bf16_t*)j.zero_page;
+    p.dbias = j.dbias; p.dbias2 = j.dbias ? j.dbias2 : nullptr;
+    p.ldy = j.ldy; p.ldx = j.ldx; p.set_stride = j.set_stride; p.x_set_rows = j.x_set_rows;
+    p.bias_stride = j.bias_set_stride ? j.bias_set_stride : j.set_stride;
     p.N = N; p.C = C; p.npanels = npanels; p.nsets = nsets;
-    p.rows_per_set = rows_per_set; p.row_begin = row_begin; p.row_end = row_end;
-    for (int i = 0; i < kMaxPanels; ++i) { p.shift[i] = i < npanels ? shifts[i] : 0; p.coff[i] = i < npanels ? coffs[i] : 0; }
+    p.rows_per_set = j.rows_per_set; p.row_begin = j.row_begin; p.row_end = j.row_end;
+    for (int i = 0; i < kMaxPanels; ++i) { p.shift[i] = i < npanels ? j.shifts[i] : 0; p.coff[i] = i < npanels ? j.coffs[i] : 0; }
     for (int i = 0; i < npanels; ++i) SISS_CHECK_ARG(p.coff[i] % 8 == 0);
     // 3x3 filter rows: panels come in triples whose shifts are consecutive rows with equal channel offsets
     bool triples = npanels % 3 == 0;
@@ -669,7 +663,7 @@ static int tn_setup(const void* Y, long ldy, const void* X, long ldx, float* dW,
         triples = p.shift[3 * g + 1] == p.shift[3 * g] + 1 && p.shift[3 * g + 2] == p.shift[3 * g] + 2 &&
                   p.coff[3 * g + 1] == p.coff[3 * g] && p.coff[3 * g + 2] == p.coff[3 * g];
     bool fused3 = triples;
-    const int rows = row_end - row_begin;
+    const int rows = j.row_end - j.row_begin;
     const bool overwrite = nsplits == -1;                  // one split per tile, dW = product (no read, no zero fill needed)
     if (overwrite) nsplits = 1;
     // -2 (round 6): automatic like 0, and a product that lands on ONE split OVERWRITES its tiles instead of read-add-writing them
@@ -771,6 +765,10 @@ static int launch_tn_group(const TNParams* ps, int n, hipStream_t st, int max_bl
 
 extern "C" {
 
+int siss_gemm_tn_bs(const void* Y, long ldy, const void* X, long ldx, float* dW, long set_stride, int N, int C, int npanels,
+                    const int* shifts, const int* coffs, int nsets, int rows_per_set, long x_set_rows, int row_begin, int row_end,
+                    int nsplits, const void* zero_page, float* dbias, float* dbias2, long bias_set_stride, void* stream);   // (below)
+
 // dW must be zeroed (or hold the running sum for gradient accumulation) before the call.
 // dbias / dbias2 (optional): dbias[set*set_stride + n] += sum over the set's rows of Y[r][n].
 // Rows [row_begin, row_end) of every set are reduced; shifts/coffs are HOST arrays.
@@ -788,13 +786,8 @@ int siss_gemm_tn(const void* Y, long ldy, const void* X, long ldx, float* dW, lo
                  int npanels, const int* shifts, const int* coffs, int nsets, int rows_per_set,
                  long x_set_rows, int row_begin, int row_end, int nsplits, const void* zero_page,
                  float* dbias, float* dbias2, void* stream) {
-    TNParams p;
-    bool fused3 = false;
-    const int rc = tn_setup(Y, ldy, X, ldx, dW, set_stride, N, C, npanels, shifts, coffs, nsets, rows_per_set, x_set_rows,
-                            row_begin, row_end, nsplits, zero_page, dbias, dbias2, false, p, fused3);
-    if (rc != SISS_OK) return rc;
-    if (fused3) return launch_tn<3>(p, (hipStream_t)stream);
-    return launch_tn<1>(p, (hipStream_t)stream);
+    return siss_gemm_tn_bs(Y, ldy, X, ldx, dW, set_stride, N, C, npanels, shifts, coffs, nsets, rows_per_set, x_set_rows, row_begin,
+                           row_end, nsplits, zero_page, dbias, dbias2, set_stride, stream);
 }
 
 // siss_gemm_tn whose bias gradients have a set stride of their own: dbias[set * bias_set_stride + n] (dW keeps set_stride).  For a
@@ -804,12 +797,17 @@ int siss_gemm_tn_bs(const void* Y, long ldy, const void* X, long ldx, float* dW,
                     int npanels, const int* shifts, const int* coffs, int nsets, int rows_per_set,
                     long x_set_rows, int row_begin, int row_end, int nsplits, const void* zero_page,
                     float* dbias, float* dbias2, long bias_set_stride, void* stream) {
+    SISS_CHECK_ARG(shifts && coffs && npanels >= 1 && npanels <= kMaxPanels);     // (the job holds the panels inline; tn_setup checks the rest)
+    siss_tn_job j = {};
+    j.Y = Y; j.ldy = ldy; j.X = X; j.ldx = ldx; j.dW = dW; j.set_stride = set_stride; j.N = N; j.C = C; j.npanels = npanels;
+    j.nsets = nsets; j.rows_per_set = rows_per_set; j.x_set_rows = x_set_rows; j.row_begin = row_begin; j.row_end = row_end;
+    j.nsplits = nsplits; j.zero_page = zero_page; j.dbias = dbias; j.dbias2 = dbias2;
+    for (int i = 0; i < npanels; ++i) { j.shifts[i] = shifts[i]; j.coffs[i] = coffs[i]; }
     TNParams p;
     bool fused3 = false;
-    const int rc = tn_setup(Y, ldy, X, ldx, dW, set_stride, N, C, npanels, shifts, coffs, nsets, rows_per_set, x_set_rows,
-                            row_begin, row_end, nsplits, zero_page, dbias, dbias2, false, p, fused3);
+    const int rc = tn_setup(j, false, p, fused3);
     if (rc != SISS_OK) return rc;
-    p.bias_stride = bias_set_stride;
+    p.bias_stride = bias_set_stride;                           // (as given: 0 is not "set_stride" here)
     if (fused3) return launch_tn<3>(p, (hipStream_t)stream);
     return launch_tn<1>(p, (hipStream_t)stream);
 }
@@ -844,8 +842,7 @@ int siss_gemm_tn_set_pair_cost(int permille) {
 // records (nsplits is ignored).  Returns 1 (bad argument) when the shapes are not (3-tap, one-panel): launch them separately then.
 int siss_gemm_tn_pair(const void* job3, const void* job1, int max_blocks, void* stream) {
     SISS_CHECK_ARG(job3 && job1 && max_blocks >= 0);
-    const siss_tn_job& a = *(const siss_tn_job*)job3;
-    const siss_tn_job& b = *(const siss_tn_job*)job1;
+    siss_tn_job a = *(const siss_tn_job*)job3, b = *(const siss_tn_job*)job1;     // (copies: they get the split counts found below)
     SISS_CHECK_ARG(a.npanels % 3 == 0 && b.npanels == 1);
     int maxb = max_blocks;
     if (maxb == 0) {
@@ -877,15 +874,12 @@ int siss_gemm_tn_pair(const void* job3, const void* job1, int max_blocks, void* 
     SISS_CHECK_ARG(s3 >= 1 && s1 >= 1);
     TNPair g;
     bool f3 = false, f1 = false;
-    int rc = tn_setup(a.Y, a.ldy, a.X, a.ldx, a.dW, a.set_stride, a.N, a.C, a.npanels, a.shifts, a.coffs, a.nsets, a.rows_per_set,
-                      a.x_set_rows, a.row_begin, a.row_end, s3, a.zero_page, a.dbias, a.dbias2, false, g.j3, f3);
+    a.nsplits = s3; b.nsplits = s1;
+    int rc = tn_setup(a, false, g.j3, f3);
     if (rc != SISS_OK) return rc;
-    rc = tn_setup(b.Y, b.ldy, b.X, b.ldx, b.dW, b.set_stride, b.N, b.C, b.npanels, b.shifts, b.coffs, b.nsets, b.rows_per_set,
-                  b.x_set_rows, b.row_begin, b.row_end, s1, b.zero_page, b.dbias, b.dbias2, false, g.j1, f1);
+    rc = tn_setup(b, false, g.j1, f1);
     if (rc != SISS_OK) return rc;
     SISS_CHECK_ARG(f3 && !f1);
-    if (a.bias_set_stride) g.j3.bias_stride = a.bias_set_stride;
-    if (b.bias_set_stride) g.j1.bias_stride = b.bias_set_stride;
     g.nv3 = (int)(base3 * s3);
     g.nv1 = (int)(base1 * s1);
     g.n3 = (g.nv3 + 7) & ~7;
@@ -904,7 +898,21 @@ int siss_gemm_tn_pair(const void* job3, const void* job1, int max_blocks, void* 
 // arguments: nothing is copied to the device, hipGraph-safe).  jobs: HOST array of siss_tn_job (the argument list of
 // siss_gemm_tn as a struct, shifts / coffs inline).  Meant for the low-resolution weight gradients: each of them alone leaves
 // most CUs idle and pays a launch's fixed latency.  All operands must stay valid until the launch has run.
-static int tn_grouped(const void* jobs, int njobs, int max_blocks, void* stream);
+static int tn_grouped(const void* jobs, int njobs, int max_blocks, void* stream) {
+    SISS_CHECK_ARG(jobs && njobs > 0 && njobs <= 256);
+    TNParams p3[256], p1[256];
+    int n3 = 0, n1 = 0;
+    for (int i = 0; i < njobs; ++i) {
+        TNParams p;
+        bool fused3 = false;
+        const int rc = tn_setup(((const siss_tn_job*)jobs)[i], true, p, fused3);
+        if (rc != SISS_OK) return rc;
+        if (fused3) p3[n3++] = p; else p1[n1++] = p;
+    }
+    if (n3) { const int rc = launch_tn_group<3>(p3, n3, (hipStream_t)stream, max_blocks); if (rc != SISS_OK) return rc; }
+    if (n1) { const int rc = launch_tn_group<1>(p1, n1, (hipStream_t)stream, 2 * max_blocks); if (rc != SISS_OK) return rc; }
+    return SISS_OK;
+}
 int siss_gemm_tn_grouped(const void* jobs, int njobs, void* stream) { return tn_grouped(jobs, njobs, 0, stream); }
 // The same with the launches' grids capped at max_blocks workgroups (a multiple of 8, >= 8; the 3-tap launches hold one CU per
 // workgroup, the one-tap launches half a CU): each workgroup walks several blocks.  For running the weight gradients on a side stream
@@ -913,26 +921,5 @@ int siss_gemm_tn_grouped_capped(const void* jobs, int njobs, int max_blocks, voi
     SISS_CHECK_ARG(max_blocks >= 8 && max_blocks % 8 == 0);
     return tn_grouped(jobs, njobs, max_blocks, stream);
 }
-static int tn_grouped(const void* jobs, int njobs, int max_blocks, void* stream) {
-    SISS_CHECK_ARG(jobs && njobs > 0 && njobs <= 256);
-    const siss_tn_job* js = (const siss_tn_job*)jobs;
-    TNParams p3[256], p1[256];
-    int n3 = 0, n1 = 0;
-    for (int i = 0; i < njobs; ++i) {
-        const siss_tn_job& j = js[i];
-        TNParams p;
-        bool fused3 = false;
-        const int rc = tn_setup(j.Y, j.ldy, j.X, j.ldx, j.dW, j.set_stride, j.N, j.C, j.npanels, j.shifts, j.coffs, j.nsets,
-                                j.rows_per_set, j.x_set_rows, j.row_begin, j.row_end, j.nsplits, j.zero_page, j.dbias, j.dbias2,
-                                true, p, fused3);
-        if (rc != SISS_OK) return rc;
-        if (j.bias_set_stride) p.bias_stride = j.bias_set_stride;
-        if (fused3) p3[n3++] = p; else p1[n1++] = p;
-    }
-    if (n3) { const int rc = launch_tn_group<3>(p3, n3, (hipStream_t)stream, max_blocks); if (rc != SISS_OK) return rc; }
-    if (n1) { const int rc = launch_tn_group<1>(p1, n1, (hipStream_t)stream, 2 * max_blocks); if (rc != SISS_OK) return rc; }
-    return SISS_OK;
-}
-
 
 }  // extern "C"

@@ -15,6 +15,7 @@
 // the dual-cotangent backward of the SISS step.
 // Output / cotangent rows may be "compact" ([N][H*W][C], no halo) for the attention block.
 #include "nt_common.h"
+#include "gn_host.h"
 
 namespace {
 
@@ -901,13 +902,6 @@ int g_use_slab = 1;
 
 }  // namespace
 
-int siss_gn_slab_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, int N, int H,
-                     int W, int C, int G, float eps, int silu, int out_compact, int ldx, void* stream);
-int siss_gn_slab_bwd(const void* dy, const void* x, const float* gamma, const float* beta, const float* mean,
-                     const float* rstd, void* dx, const void* accum, const void* accum2, void* dx2, int split_c,
-                     int accumulate2, float* dgamma, float* dbeta, float* colsum, long colsum_ld, int n2, int nx,
-                     int set_images, long set_stride, int H, int W, int C, int G, int silu, int dy_compact, int ldx,
-                     void* stream);
 extern "C" {
 
 // 1 (default): the small sites (<= 32 x 32 pixels forward, <= 16 x 16 backward) run on the one-launch slab kernels
@@ -988,47 +982,48 @@ int siss_groupnorm_fwd(const void* x, const float* gamma, const float* beta, voi
     return siss_groupnorm_fwd_ld(x, gamma, beta, y, mean, rstd, partial, N, H, W, C, G, eps, silu, out_compact, 0, stream);
 }
 
-static int gn_bwd_launch(const void* dy, const void* x, const float* gamma, const float* beta,
-                          const float* mean, const float* rstd, void* dx, const void* accum, const void* accum2,
-                          void* dx2, int split_c, int accumulate2, float* dgamma,
-                          float* dbeta, float* colsum, long colsum_ld, float* partial, int n2, int nx, int set_images,
-                          long set_stride, int H, int W, int C, int G, int silu, int dy_compact, int ldx, int s2d, void* stream) {
+// What every backward entry point asks of a call (the two-pass launcher and siss_groupnorm_bwd_sc add their own)
+static int gn_bwd_check(const GNBwdCall& c, int s2d) {
+    SISS_CHECK_ARG(!s2d || (c.dx2 && c.H % 2 == 0 && c.W % 2 == 0));
+    SISS_CHECK_ARG(c.dy && c.x && c.gamma && c.beta && c.mean && c.rstd && c.dx && c.dgamma && c.dbeta && c.partial);
+    SISS_CHECK_ARG(c.n2 > 0 && c.nx > 0 && c.set_images > 0 && c.n2 % c.set_images == 0);
+    SISS_CHECK_ARG(c.n2 == c.nx || c.n2 == 2 * c.nx);     // cotangent sets per saved sample: 1 or 2
+    SISS_CHECK_ARG(((uintptr_t)c.dy | (uintptr_t)c.x | (uintptr_t)c.dx | (uintptr_t)c.accum | (uintptr_t)c.accum2 | (uintptr_t)c.dx2) % 16 == 0);
+    SISS_CHECK_ARG(!c.dx2 || (c.split_c > 0 && c.split_c < c.C && c.split_c % 8 == 0));
+    SISS_CHECK_ARG(c.ldx == 0 || (c.ldx >= c.C && c.ldx % 8 == 0));
+    SISS_CHECK_ARG((uintptr_t)c.partial % 16 == 0);
+    return SISS_OK;
+}
+static int gn_bwd_launch(const GNBwdCall& c, int s2d) {       // s2d: dx in space-to-depth layout (siss_groupnorm_bwd_ld_s2d)
+    const int n2 = c.n2, nx = c.nx;
     GNShape s;
-    SISS_CHECK_ARG(!s2d || (dx2 && H % 2 == 0 && W % 2 == 0));
-    SISS_CHECK_ARG(dy && x && gamma && beta && mean && rstd && dx && dgamma && dbeta && partial);
-    SISS_CHECK_ARG(n2 > 0 && nx > 0 && set_images > 0 && n2 % set_images == 0);
-    SISS_CHECK_ARG(n2 == nx || n2 == 2 * nx);     // cotangent sets per saved sample: 1 or 2
-    SISS_CHECK_ARG(make_shape(H, W, C, G, s, nx, kBlocksBwd));
-    SISS_CHECK_ARG(((uintptr_t)dy | (uintptr_t)x | (uintptr_t)dx | (uintptr_t)accum | (uintptr_t)accum2 | (uintptr_t)dx2) % 16 == 0);
-    SISS_CHECK_ARG(!dx2 || (split_c > 0 && split_c < C && split_c % 8 == 0));
-    SISS_CHECK_ARG(ldx == 0 || (ldx >= C && ldx % 8 == 0));
-    SISS_CHECK_ARG((uintptr_t)partial % 16 == 0);
-    if (ldx) s.ldx = ldx;
-    if (!s2d && g_use_slab && s.nslices == 1 && (n2 == nx || n2 == 2 * nx) && n2 / set_images <= 2) {
-        const int rc = siss_gn_slab_bwd(dy, x, gamma, beta, mean, rstd, dx, accum, accum2, dx2, split_c, accumulate2, dgamma, dbeta,
-                                        colsum, colsum_ld, n2, nx, set_images, set_stride, H, W, C, G, silu, dy_compact, ldx, stream);
+    if (const int rc = gn_bwd_check(c, s2d)) return rc;
+    SISS_CHECK_ARG(make_shape(c.H, c.W, c.C, c.G, s, nx, kBlocksBwd));
+    if (c.ldx) s.ldx = c.ldx;
+    if (!s2d && g_use_slab && s.nslices == 1 && (n2 == nx || n2 == 2 * nx) && n2 / c.set_images <= 2) {
+        const int rc = siss_gn_slab_bwd(c);
         if (rc >= 0) return rc;
     }
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = (hipStream_t)c.stream;
     // the statistics kernel (142 VGPRs: three blocks resident per CU) and the apply kernel (190: two) each get ONE resident round
     GNShape ss;
-    SISS_CHECK_ARG(make_shape(H, W, C, G, ss, nx, kBlocksBwdStats));
+    SISS_CHECK_ARG(make_shape(c.H, c.W, c.C, c.G, ss, nx, kBlocksBwdStats));
     ss.ldx = s.ldx;
     dim3 grid(s.nchunks, nx, s.nslices), grid_s(ss.nchunks, nx, ss.nslices);
-    const bf16_t* dyp = (const bf16_t*)dy; const bf16_t* xp = (const bf16_t*)x;
+    const bf16_t* dyp = (const bf16_t*)c.dy; const bf16_t* xp = (const bf16_t*)c.x;
 #define GN_BWD(SILU, SETS)                                                                                          \
-    gn_bwd_stats_kernel<SILU, SETS><<<grid_s, kThreads, 0, st>>>(dyp, xp, gamma, beta, mean, rstd, ss, nx, dy_compact, \
-                                                               set_images, set_stride, partial, dgamma, dbeta);    \
+    gn_bwd_stats_kernel<SILU, SETS><<<grid_s, kThreads, 0, st>>>(dyp, xp, c.gamma, c.beta, c.mean, c.rstd, ss, nx, c.dy_compact, \
+                                                               c.set_images, c.set_stride, c.partial, c.dgamma, c.dbeta);    \
     if (s2d)                                                                                                        \
-        gn_bwd_apply_kernel<SILU, SETS, true><<<grid, kThreads, 0, st>>>(dyp, xp, gamma, beta, mean, rstd, partial, s, nx,    \
-                                                               dy_compact, (const bf16_t*)accum, (const bf16_t*)accum2, (bf16_t*)dx, (bf16_t*)dx2, split_c,  \
-                                                               accumulate2, colsum, colsum_ld, ss.nchunks);                \
+        gn_bwd_apply_kernel<SILU, SETS, true><<<grid, kThreads, 0, st>>>(dyp, xp, c.gamma, c.beta, c.mean, c.rstd, c.partial, s, nx,    \
+                                                               c.dy_compact, (const bf16_t*)c.accum, (const bf16_t*)c.accum2, (bf16_t*)c.dx, (bf16_t*)c.dx2, c.split_c,  \
+                                                               c.accumulate2, c.colsum, c.colsum_ld, ss.nchunks);                \
     else                                                                                                            \
-        gn_bwd_apply_kernel<SILU, SETS, false><<<grid, kThreads, 0, st>>>(dyp, xp, gamma, beta, mean, rstd, partial, s, nx,    \
-                                                               dy_compact, (const bf16_t*)accum, (const bf16_t*)accum2, (bf16_t*)dx, (bf16_t*)dx2, split_c,  \
-                                                               accumulate2, colsum, colsum_ld, ss.nchunks)
-    if (n2 == nx) { if (silu) { GN_BWD(true, 1); } else { GN_BWD(false, 1); } }
-    else          { if (silu) { GN_BWD(true, 2); } else { GN_BWD(false, 2); } }
+        gn_bwd_apply_kernel<SILU, SETS, false><<<grid, kThreads, 0, st>>>(dyp, xp, c.gamma, c.beta, c.mean, c.rstd, c.partial, s, nx,    \
+                                                               c.dy_compact, (const bf16_t*)c.accum, (const bf16_t*)c.accum2, (bf16_t*)c.dx, (bf16_t*)c.dx2, c.split_c,  \
+                                                               c.accumulate2, c.colsum, c.colsum_ld, ss.nchunks)
+    if (n2 == nx) { if (c.silu) { GN_BWD(true, 1); } else { GN_BWD(false, 1); } }
+    else          { if (c.silu) { GN_BWD(true, 2); } else { GN_BWD(false, 2); } }
 #undef GN_BWD
     SISS_LAUNCH_RET();
 }
@@ -1044,8 +1039,8 @@ int siss_groupnorm_bwd_ld(const void* dy, const void* x, const float* gamma, con
                           void* dx2, int split_c, int accumulate2, float* dgamma,
                           float* dbeta, float* colsum, long colsum_ld, float* partial, int n2, int nx, int set_images,
                           long set_stride, int H, int W, int C, int G, int silu, int dy_compact, int ldx, void* stream) {
-    return gn_bwd_launch(dy, x, gamma, beta, mean, rstd, dx, accum, accum2, dx2, split_c, accumulate2, dgamma, dbeta, colsum, colsum_ld,
-                         partial, n2, nx, set_images, set_stride, H, W, C, G, silu, dy_compact, ldx, 0, stream);
+    return gn_bwd_launch(gn_bwd_call(dy, x, gamma, beta, mean, rstd, dx, accum, accum2, dx2, split_c, accumulate2, dgamma, dbeta, colsum,
+                                     colsum_ld, partial, n2, nx, set_images, set_stride, H, W, C, G, silu, dy_compact, ldx, stream), 0);
 }
 // The same for a split target (dx2 != null; H, W even) whose FIRST part -- channels [0, split_c), `dx` -- is written in
 // space-to-depth layout: dx is a padded (H / 2) x (W / 2) tensor of 4 split_c channels, pixel (y, x) at row (y / 2, x / 2), columns
@@ -1055,8 +1050,8 @@ int siss_groupnorm_bwd_ld_s2d(const void* dy, const void* x, const float* gamma,
                               void* dx2, int split_c, int accumulate2, float* dgamma,
                               float* dbeta, float* colsum, long colsum_ld, float* partial, int n2, int nx, int set_images,
                               long set_stride, int H, int W, int C, int G, int silu, int dy_compact, int ldx, void* stream) {
-    return gn_bwd_launch(dy, x, gamma, beta, mean, rstd, dx, accum, accum2, dx2, split_c, accumulate2, dgamma, dbeta, colsum, colsum_ld,
-                         partial, n2, nx, set_images, set_stride, H, W, C, G, silu, dy_compact, ldx, 1, stream);
+    return gn_bwd_launch(gn_bwd_call(dy, x, gamma, beta, mean, rstd, dx, accum, accum2, dx2, split_c, accumulate2, dgamma, dbeta, colsum,
+                                     colsum_ld, partial, n2, nx, set_images, set_stride, H, W, C, G, silu, dy_compact, ldx, stream), 1);
 }
 /* the same with ldx = C */
 int siss_groupnorm_bwd(const void* dy, const void* x, const float* gamma, const float* beta,
@@ -1084,15 +1079,14 @@ int siss_groupnorm_bwd_sc(const void* dy, const void* x, const float* gamma, con
                           int s2d, int ldx, void* stream) {
     GNShape ss;
     SISS_CHECK_ARG(!colsum);
-    SISS_CHECK_ARG(dy && x && gamma && beta && mean && rstd && dx && dout && wsc && dgamma && dbeta && partial && gconst);
-    SISS_CHECK_ARG(!s2d || (dx2 && H % 2 == 0 && W % 2 == 0));
-    SISS_CHECK_ARG(n2 > 0 && nx > 0 && set_images > 0 && n2 % set_images == 0 && (n2 == nx || n2 == 2 * nx));
+    GNBwdCall c = {};                                          // (the fields gn_bwd_check reads)
+    c.dy = dy; c.x = x; c.gamma = gamma; c.beta = beta; c.mean = mean; c.rstd = rstd; c.dx = dx; c.accum2 = accum2; c.dx2 = dx2;
+    c.split_c = split_c; c.dgamma = dgamma; c.dbeta = dbeta; c.partial = partial; c.n2 = n2; c.nx = nx; c.set_images = set_images;
+    c.H = H; c.W = W; c.C = C; c.ldx = ldx;
+    if (const int rc = gn_bwd_check(c, s2d)) return rc;
+    SISS_CHECK_ARG(dout && wsc && gconst && ((uintptr_t)dout | (uintptr_t)wsc | (uintptr_t)gconst) % 16 == 0);
     SISS_CHECK_ARG(K > 0 && K % BK == 0 && ldo >= K && ldo % 8 == 0);
     SISS_CHECK_ARG(make_shape(H, W, C, G, ss, nx, kBlocksBwdStats) && ss.nslices == 1);
-    SISS_CHECK_ARG(((uintptr_t)dy | (uintptr_t)x | (uintptr_t)dx | (uintptr_t)dout | (uintptr_t)wsc | (uintptr_t)accum2 | (uintptr_t)dx2 |
-                    (uintptr_t)partial | (uintptr_t)gconst) % 16 == 0);
-    SISS_CHECK_ARG(!dx2 || (split_c > 0 && split_c < C && split_c % 8 == 0));
-    SISS_CHECK_ARG(ldx == 0 || (ldx >= C && ldx % 8 == 0));
     const long rpi = (long)(H + 2) * (W + 2);
     SISS_CHECK_ARG(rpi >= 64 && nx * rpi < (1L << 31) - 256);          // <= 3 images per 128-row tile; rows of a set in an int
     if (ldx) ss.ldx = ldx;

@@ -7,6 +7,7 @@
 // (The two-phase persistent form for the LARGE sites -- per-sample barrier, fixed-point accumulators -- measured 2x slower
 // than the two-pass kernels and lives in tools/probes/groupnorm2p.hip; docs/experiments.md.)
 #include "common.h"
+#include "gn_host.h"
 #include <type_traits>
 
 namespace {
@@ -372,7 +373,6 @@ int slab_slice(int H, int W, int C, int G, int N, SlabShape& s) {
 
 }  // namespace
 
-// The slab kernels (small sites): SISS_OK / error, or -1 when the site is not covered.
 int siss_gn_slab_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, int N, int H,
                      int W, int C, int G, float eps, int silu, int out_compact, int ldx, void* stream) {
     SlabShape s;
@@ -392,25 +392,22 @@ int siss_gn_slab_fwd(const void* x, const float* gamma, const float* beta, void*
     return hipGetLastError() == hipSuccess ? SISS_OK : SISS_ERR_LAUNCH;
 }
 
-int siss_gn_slab_bwd(const void* dy, const void* x, const float* gamma, const float* beta, const float* mean,
-                     const float* rstd, void* dx, const void* accum, const void* accum2, void* dx2, int split_c,
-                     int accumulate2, float* dgamma, float* dbeta, float* colsum, long colsum_ld, int n2, int nx,
-                     int set_images, long set_stride, int H, int W, int C, int G, int silu, int dy_compact, int ldx,
-                     void* stream) {
+int siss_gn_slab_bwd(const GNBwdCall& c) {
+    const int n2 = c.n2, nx = c.nx, silu = c.silu;
     SlabShape s;
     // backward: only up to 16 x 16 pixels (measured per site, B = 16: 8x8 38.8 -> 24.0 us, 16x16 40.9 -> 26.9 us, but 32x32
     // 40.7 -> 45.7 us: three tensors of 1024 pixels per block leave one block per CU and a serial walk of 8 vectors per lane)
-    if (H * W > 256 || !slab_slice(H, W, C, G, nx, s)) return -1;
-    if (ldx) s.ldx = ldx;
+    if (c.H * c.W > 256 || !slab_slice(c.H, c.W, c.C, c.G, nx, s)) return -1;
+    if (c.ldx) s.ldx = c.ldx;
     BwdArgs a;
-    a.dy = (const bf16_t*)dy; a.x = (const bf16_t*)x; a.gamma = gamma; a.beta = beta; a.mean = mean; a.rstd = rstd;
-    a.accum = (const bf16_t*)accum; a.accum2 = (const bf16_t*)accum2; a.dx = (bf16_t*)dx; a.dx2 = (bf16_t*)dx2;
-    a.dgamma = dgamma; a.dbeta = dbeta; a.colsum = colsum; a.colsum_ld = colsum_ld; a.set_stride = set_stride;
-    a.split_c = split_c; a.accumulate2 = accumulate2; a.nx = nx; a.dy_compact = dy_compact; a.set_images = set_images;
-    const bool extra = accum || accum2 || (dx2 && accumulate2);
-    const dim3 grid(C / s.Cs, nx);
+    a.dy = (const bf16_t*)c.dy; a.x = (const bf16_t*)c.x; a.gamma = c.gamma; a.beta = c.beta; a.mean = c.mean; a.rstd = c.rstd;
+    a.accum = (const bf16_t*)c.accum; a.accum2 = (const bf16_t*)c.accum2; a.dx = (bf16_t*)c.dx; a.dx2 = (bf16_t*)c.dx2;
+    a.dgamma = c.dgamma; a.dbeta = c.dbeta; a.colsum = c.colsum; a.colsum_ld = c.colsum_ld; a.set_stride = c.set_stride;
+    a.split_c = c.split_c; a.accumulate2 = c.accumulate2; a.nx = nx; a.dy_compact = c.dy_compact; a.set_images = c.set_images;
+    const bool extra = c.accum || c.accum2 || (c.dx2 && c.accumulate2);
+    const dim3 grid(c.C / s.Cs, nx);
     siss_count_dispatch(SISS_K_GN_SLAB);
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = (hipStream_t)c.stream;
     static unsigned char att[8][kMaxDevices];
 #define GN_SLAB_BWD(SILU, SETS, EXTRA, SLOT)                                                                               \
     do {                                                                                                                   \
