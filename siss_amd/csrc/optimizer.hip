@@ -10,19 +10,9 @@
 // ||g||^2 = ||g_x||^2 - 2 s <g_x,g_a> + s^2 ||g_a||^2 is formed from the f64 sums, so the clip
 // coefficient needs no third pass.  All scalars (s, clip, step count) stay on the device:
 // no host sync, and the launches replay correctly from a hipGraph.
-#include "common.h"
+#include "opt_step.h"   // grid, StepScalars + scalars_kernel, the norm sums' order, the AdamW arithmetic (shared with saliency.hip)
 
 namespace {
-
-constexpr int kThreads = 256;
-constexpr int kMaxBlocks = 2048;
-
-struct StepScalars {   // lives in device memory; 16 floats
-    float norm_x, norm_a, dot, scale;      // 0..3  (scale = s in g = g_x - s*g_a)
-    float pre_clip_norm, clip_coef, step, pad0;  // 4..7
-    float bc1, bc2_sqrt, pad1, pad2;       // 8..11
-    float pad3[4];
-};
 
 // A list of stretches of a flat buffer (the TRAINABLE parameters of a subset update), in siss_zero_ranges' form: 16-byte granules, n
 // starts followed by the n + 1 prefix sums of the lengths.  at(i): the buffer granule of granule i of the compacted index space -- a
@@ -53,72 +43,17 @@ __global__ __launch_bounds__(kThreads) void norms_kernel(const float* __restrict
                                                          const float* __restrict__ ga, long n,
                                                          double* __restrict__ partials, const long* __restrict__ tab, int nr,
                                                          long buf_vec) {
-    __shared__ double sh[3 * kThreads / 64];
     double sxx = 0, saa = 0, sxa = 0;
     const long nvec = n / 4;
     RangeWalk walk(tab, nr, buf_vec);
     for (long k = (long)blockIdx.x * kThreads + threadIdx.x; k < nvec; k += (long)gridDim.x * kThreads) {
         long i = k;
         if constexpr (RANGES) { i = walk.at(k); if (i < 0) continue; }
-        f32x4_t x = reinterpret_cast<const f32x4_t*>(gx)[i];
-        f32x4_t a = reinterpret_cast<const f32x4_t*>(ga)[i];
-        float pxx = 0, paa = 0, pxa = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { pxx += x[j] * x[j]; paa += a[j] * a[j]; pxa += x[j] * a[j]; }
-        sxx += pxx; saa += paa; sxa += pxa;
+        norm_granule(reinterpret_cast<const f32x4_t*>(gx)[i], reinterpret_cast<const f32x4_t*>(ga)[i], sxx, saa, sxa);
     }
     if (!RANGES && blockIdx.x == 0)                     // (a compacted buffer is whole granules: no tail)
-        for (long i = nvec * 4 + threadIdx.x; i < n; i += kThreads) {
-            sxx += (double)gx[i] * gx[i]; saa += (double)ga[i] * ga[i]; sxa += (double)gx[i] * ga[i];
-        }
-    sxx = wave_sum_d(sxx); saa = wave_sum_d(saa); sxa = wave_sum_d(sxa);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { sh[3 * w] = sxx; sh[3 * w + 1] = saa; sh[3 * w + 2] = sxa; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double a = 0, b = 0, c = 0;
-        for (int i = 0; i < kThreads / 64; ++i) { a += sh[3 * i]; b += sh[3 * i + 1]; c += sh[3 * i + 2]; }
-        partials[3 * blockIdx.x] = a; partials[3 * blockIdx.x + 1] = b; partials[3 * blockIdx.x + 2] = c;
-    }
-}
-
-// mode 0: norm fixing  s = scaling_norm / ||g_a||        (delete_celeb.py:746)
-// mode 1: erasediff    s = -max(eta - <gx,ga>/||ga||^2, 0) (:740-742)
-// mode 2: like 0 but s = 0 when it would be inf          (delete_tshirt.py:688-690)
-__global__ void scalars_kernel(const double* __restrict__ partials, int nblk, int mode, float knob,
-                               float max_norm, float beta1, float beta2, StepScalars* __restrict__ sc) {
-    // one block folds the per-block partial sums in parallel (a single thread walking 2048 x 3 dependent L2 reads
-    // cost 240 us: more than the streaming pass that produced them); fixed lane -> index map: deterministic
-    __shared__ double shs[3 * kThreads / 64];
-    double xx = 0, aa = 0, xa = 0;
-    for (int i = threadIdx.x; i < nblk; i += kThreads) { xx += partials[3 * i]; aa += partials[3 * i + 1]; xa += partials[3 * i + 2]; }
-    xx = wave_sum_d(xx); aa = wave_sum_d(aa); xa = wave_sum_d(xa);
-    if ((threadIdx.x & 63) == 0) { const int w = threadIdx.x >> 6; shs[3 * w] = xx; shs[3 * w + 1] = aa; shs[3 * w + 2] = xa; }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    xx = aa = xa = 0;
-    for (int i = 0; i < kThreads / 64; ++i) { xx += shs[3 * i]; aa += shs[3 * i + 1]; xa += shs[3 * i + 2]; }
-    const double nx = sqrt(xx), na = sqrt(aa);
-    double s;
-    if (mode == 1) {
-        s = (double)knob - xa / aa;
-        s = -(s > 0 ? s : 0);
-    } else {
-        s = (double)knob / na;
-        if (mode == 2 && isinf(s)) s = 0;
-    }
-    double g2 = xx - 2 * s * xa + s * s * aa;
-    if (g2 < 0) g2 = 0;
-    const double gn = sqrt(g2);
-    double coef = (double)max_norm / (gn + 1e-6);   // torch.nn.utils.clip_grad_norm_
-    if (coef > 1) coef = 1;
-    const float step = sc->step + 1.f;
-    sc->norm_x = (float)nx; sc->norm_a = (float)na; sc->dot = (float)xa; sc->scale = (float)s;
-    sc->pre_clip_norm = (float)gn; sc->clip_coef = (float)coef; sc->step = step;
-    // in double, ONE rounding: 1.f - powf(beta, step) cancels at small step counts (beta2 = 0.999, step 2: an f32 pow's ~3e-8
-    // absolute error over 0.002 is 3.5e-6 of the update, where torch's own f32 AdamW is at 2e-7 of it; docs/history.md)
-    sc->bc1 = (float)(1.0 - pow((double)beta1, (double)step));
-    sc->bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
+        for (long i = nvec * 4 + threadIdx.x; i < n; i += kThreads) norm_tail(gx[i], ga[i], sxx, saa, sxa);
+    norm_block_fold(sxx, saa, sxa, partials);
 }
 
 // pass 2: g = clip * (g_x - s g_a); torch.optim.AdamW single-tensor update order.
@@ -129,42 +64,16 @@ __global__ __launch_bounds__(kThreads) void recombine_adamw_kernel(
     float* __restrict__ m, float* __restrict__ v, bf16_t* __restrict__ shadow,
     float* __restrict__ g_out, long n, float lr, float beta1, float beta2, float eps, float wd,
     const StepScalars* __restrict__ sc, const long* __restrict__ tab, int nr, long buf_vec) {
-    const float s = sc->scale, clip = sc->clip_coef, bc1 = sc->bc1, bc2s = sc->bc2_sqrt;
-    const float step_size = lr / bc1;
-    const float decay = 1.f - lr * wd;
+    const AdamWStep upd(sc, lr, beta1, beta2, eps, wd);
     const long nvec = n / 4;
-    auto upd = [&](float x, float a, float& pp, float& mm, float& vv) -> float {
-        const float g = __fmul_rn(__fsub_rn(x, __fmul_rn(s, a)), clip);
-        pp = __fmul_rn(pp, decay);
-        mm = __fadd_rn(mm, __fmul_rn(__fsub_rn(g, mm), 1.f - beta1));           // lerp
-        vv = __fadd_rn(__fmul_rn(vv, beta2), __fmul_rn(__fmul_rn(g, g), 1.f - beta2));
-        const float den = __fadd_rn(sqrtf(vv) / bc2s, eps);
-        pp = __fsub_rn(pp, __fmul_rn(step_size, mm / den));
-        return g;
-    };
     RangeWalk walk(tab, nr, buf_vec);
     for (long k = (long)blockIdx.x * kThreads + threadIdx.x; k < nvec; k += (long)gridDim.x * kThreads) {
         long i = k;
         if constexpr (RANGES) { i = walk.at(k); if (i < 0) continue; }
-        f32x4_t x = reinterpret_cast<const f32x4_t*>(gx)[i], a = reinterpret_cast<const f32x4_t*>(ga)[i];
-        f32x4_t pp = reinterpret_cast<f32x4_t*>(p)[i], mm = reinterpret_cast<f32x4_t*>(m)[i],
-                vv = reinterpret_cast<f32x4_t*>(v)[i], gg;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { float P = pp[j], M = mm[j], V = vv[j]; gg[j] = upd(x[j], a[j], P, M, V); pp[j] = P; mm[j] = M; vv[j] = V; }
-        reinterpret_cast<f32x4_t*>(p)[i] = pp;
-        reinterpret_cast<f32x4_t*>(m)[i] = mm;
-        reinterpret_cast<f32x4_t*>(v)[i] = vv;
-        if (g_out) reinterpret_cast<f32x4_t*>(g_out)[i] = gg;
-        if (shadow) reinterpret_cast<u32x2_t*>(shadow)[i] = u32x2_t{pack_bf2(pp[0], pp[1]), pack_bf2(pp[2], pp[3])};
+        update_granule(upd, gx, ga, p, m, v, shadow, g_out, i);
     }
     if (!RANGES && blockIdx.x == 0)
-        for (long i = nvec * 4 + threadIdx.x; i < n; i += kThreads) {
-            float P = p[i], M = m[i], V = v[i];
-            const float g = upd(gx[i], ga[i], P, M, V);
-            p[i] = P; m[i] = M; v[i] = V;
-            if (g_out) g_out[i] = g;
-            if (shadow) shadow[i] = f2bf(P);
-        }
+        for (long i = nvec * 4 + threadIdx.x; i < n; i += kThreads) update_element(upd, gx, ga, p, m, v, shadow, g_out, i);
 }
 
 __global__ __launch_bounds__(kThreads) void cast_bf16_kernel(const float* __restrict__ src,
@@ -282,13 +191,6 @@ __global__ __launch_bounds__(256) void conv_weight_dgrad_multi_bf16_kernel(const
             if (c < j.ci && o < j.co) dst[(long)c * j.co + o] = tile[r][oo];
         }
     }
-}
-
-inline int grid_for(long n) {
-    long b = (n / 4 + kThreads - 1) / kThreads;
-    if (b < 1) b = 1;
-    if (b > kMaxBlocks) b = kMaxBlocks;
-    return (int)b;
 }
 
 // ---- sub-pixel form of Upsample2D (nearest 2x -> conv3x3; round 4).  Output pixel (2Y + py, 2X + px) reads the LOW-resolution rows

@@ -26,16 +26,40 @@ class FlatAdamW:
         self.scalars = torch.zeros(lib.query("siss_opt_scalars_words"), dtype=torch.float32, device=dev)
         self.last_grad = None
 
-    def launch(self, grads, *, scaling_norm=None, eta=None, inf_guard=False, want_grad=False, ranges=None):
+    def launch(self, grads, *, scaling_norm=None, eta=None, inf_guard=False, want_grad=False, ranges=None, mask=None):
         """Enqueue both passes (no host sync).  grads: [2, P] f32 = (g_x, g_a).  ranges: (device table, stretches, granules) of a
         trainable subset (siss_amd.trainable.Subset.table) -- norms, scaling factor, clip and update over the listed stretches
-        only, every other byte of p / m / v / shadow untouched; the caller keeps the table alive (a captured step holds its address)."""
+        only, every other byte of p / m / v / shadow untouched; the caller keeps the table alive (a captured step holds its address).
+        mask: the packed words of a siss_amd.saliency.SaliencyMask over this buffer (int32, one bit per float) -- the same passes on
+        the elements whose bit is set (csrc/saliency.hip); the caller keeps the words alive likewise."""
         n = self.p.numel()
         assert grads.dtype == torch.float32 and grads.shape == (2, n) and grads.is_contiguous()
         if eta is not None:
             mode, knob = MODE_ERASEDIFF, float(eta)
         else:
             mode, knob = (MODE_NORM_FIX_INF_GUARD if inf_guard else MODE_NORM_FIX), float(scaling_norm)
+        if mask is not None:
+            if ranges is not None:
+                raise ValueError("FlatAdamW.launch(ranges=..., mask=...): a subset update and a masked update do not combine")
+            if mask is not getattr(self, "_mask_checked", None):      # once per mask, not per step
+                for name in ("siss_grad_norms_scale_masked", "siss_recombine_clip_adamw_masked"):
+                    if not lib.has(name):
+                        raise RuntimeError(f"this libsiss_hip.so has no {name}: a saliency mask needs the masked kernels of "
+                                           "csrc/saliency.hip (there is no fall-back to the full update)")
+                if not (mask.dtype == torch.int32 and mask.device == self.p.device and mask.dim() == 1 and mask.is_contiguous()
+                        and mask.numel() == (n + 31) // 32 and mask.data_ptr() % 16 == 0):
+                    raise ValueError(f"FlatAdamW.launch(mask=...): {(n + 31) // 32} contiguous int32 words on {self.p.device}, 16-byte "
+                                     f"aligned, are needed (one bit per float of the buffer); got {tuple(mask.shape)} {mask.dtype} on "
+                                     f"{mask.device} at offset {mask.data_ptr() % 16} of a 16-byte line")
+                self._mask_checked = mask
+            if want_grad and (self.last_grad is None):
+                self.last_grad = torch.zeros_like(self.p)    # (written where a bit is set only: zero elsewhere)
+            lib.call("siss_grad_norms_scale_masked", grads[0], grads[1], n, mask, mode, knob, self.max_grad_norm,
+                     self.betas[0], self.betas[1], self.partials, self.scalars)
+            lib.call("siss_recombine_clip_adamw_masked", grads[0], grads[1], self.p, self.m, self.v, self.shadow,
+                     self.last_grad if want_grad else None, n, mask, self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
+                     self.scalars)
+            return
         if ranges is not None:
             if want_grad and (self.last_grad is None):
                 self.last_grad = torch.zeros_like(self.p)    # (written on the stretches only: zero elsewhere)
@@ -58,7 +82,7 @@ class FlatAdamW:
                  self.last_grad if want_grad else None, n, self.lr, self.betas[0], self.betas[1],
                  self.eps, self.wd, self.scalars)
 
-    def launch_sharded(self, gx_shard, ga_shard, lo, hi, group, *, scaling_norm=None, eta=None, inf_guard=False, ranges=None):
+    def launch_sharded(self, gx_shard, ga_shard, lo, hi, group, *, scaling_norm=None, eta=None, inf_guard=False, ranges=None, mask=None):
         """The same update on THIS rank's parameter shard [lo, hi) (sharded data-parallel exchange):
         gx_shard / ga_shard are the rank-summed gradients of the shard.  The three norm sums are all-reduced (24 bytes),
         so every rank forms the same scaling factor and clip coefficient as the replicated update; p / m / v / shadow are
@@ -68,6 +92,9 @@ class FlatAdamW:
         if ranges is not None:
             raise NotImplementedError("FlatAdamW.launch_sharded with a trainable subset: the sharded exchange splits the WHOLE buffer "
                                       "over the ranks; a subset update takes the all-reduce exchange (launch(ranges=...))")
+        if mask is not None:
+            raise NotImplementedError("FlatAdamW.launch_sharded with a saliency mask: there is no masked sharded update; a masked "
+                                      "update takes the all-reduce exchange (launch(mask=...))")
         n = hi - lo
         assert gx_shard.numel() == n and ga_shard.numel() == n and gx_shard.dtype == torch.float32
         if eta is not None:

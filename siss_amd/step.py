@@ -41,7 +41,7 @@ class SISSStepper:
     def __init__(self, engine: UNetEngine, alphas_cumprod, *, lr, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=1e-2, scaling_norm=None, eta=None, lambd=0.5, train_batch_size,
                  grad_accum=1, max_grad_norm=1.0, loss_fn=SISS, inf_guard=False, process_group=None,
-                 mixed_precision="bf16", superfactor=1.0, superfactor_decay=None, trainable=None, lora=None):
+                 mixed_precision="bf16", superfactor=1.0, superfactor_decay=None, trainable=None, lora=None, saliency=None):
         """trainable: None (every parameter: the reference's protocol), an iterable of parameter names, or "requires_grad" (the flags
         of the parameters of the UNet2DModel / UNet2DConditionModel that owns the engine).  With a subset the norms, the scaling
         factor, the clip and the AdamW update run over the trainable tensors only; the rest keep every byte.  The selection (the
@@ -52,9 +52,21 @@ class SISSStepper:
         lora: None, or a siss_amd.lora.LoRAState over this engine (opt-in, not the reference's protocol): the base weights stay frozen
         and the optimizer runs on the adapters' flat buffer -- after the backward pass the weight gradients of the targets are
         projected to (dA, dB) of both sets, the norms / scaling factor / clip / AdamW run in adapter space, and one merge pass rewrites
-        the targets' stretches of the master and its shadow.  Only the targets' weight-gradient products run; no full-size m / v."""
+        the targets' stretches of the master and its shadow.  Only the targets' weight-gradient products run; no full-size m / v.
+
+        saliency: None, or a siss_amd.saliency.SaliencyMask over this engine (opt-in, not the reference's protocol): one bit per float
+        of the flat buffer -- the norms, the scaling factor, the clip and the AdamW update run over the elements whose bit is set
+        (csrc/saliency.hip), every other byte of the parameters, their moments and their shadow keeps its value.  The backward pass
+        and the gradient exchange are the full update's (every weight-gradient product runs, the whole buffer is summed); exclusive
+        with trainable= and lora=.  The mask's words live as long as the stepper: a captured step holds their address."""
         self.e = engine
         self.lora = lora
+        self.saliency = None
+        if saliency is not None:
+            for other, name in ((trainable, "trainable"), (lora, "lora")):
+                if other is not None:
+                    raise ValueError(f"SISSStepper(saliency=..., {name}=...): the saliency mask selects single weights of every tensor; "
+                                     f"saliency and {name} do not combine")
         if lora is not None:
             if trainable is not None:
                 raise ValueError("SISSStepper(lora=..., trainable=...): a LoRA run trains the adapters of its targets and nothing else")
@@ -104,6 +116,7 @@ class SISSStepper:
         engine.set_trainable(self.subset)
         # (the table is built once and lives as long as the stepper: a captured step holds its address)
         self._ranges = None if self.subset is None or lora is not None else self.subset.table(dev)
+        self._mask = None
         self._micro = 0
         self.last = None
         self._pending = []
@@ -134,6 +147,28 @@ class SISSStepper:
                 print("[siss_amd] trainable subset: the sharded exchange splits the whole buffer over the ranks; using the all-reduce")
                 self.exchange = "allreduce"
         self.set_overlap(overlap)
+        if saliency is not None:
+            self.set_saliency(saliency)
+
+    def set_saliency(self, mask):
+        """Restrict the update to the set bits of `mask` (siss_amd.saliency.SaliencyMask over this engine) from the next step on -- what
+        SISSStepper(saliency=mask) does; a task calls it once its mask is computed (forget_gradient needs the stepper).  Before a step
+        is captured: a captured step holds the address of the words it was captured with."""
+        if self.lora is not None or self.subset is not None:
+            raise ValueError("SISSStepper.set_saliency on a stepper with " + ("lora" if self.lora is not None else "trainable") +
+                             ": saliency does not combine with lora / trainable")
+        from .saliency import fingerprint, require_kernels
+        require_kernels()
+        fp = fingerprint(self.e)
+        if (mask.total, mask.tensors, mask.params) != (fp["total"], fp["tensors"], fp["real_params"]):
+            raise ValueError("SISSStepper(saliency=...): the mask was built over another engine's parameter layout")
+        if mask.bits.device != self.e.ps.flat.device:
+            raise ValueError("SISSStepper(saliency=...): the mask's words are on another device than the engine")
+        self.saliency, self._mask = mask, mask.bits
+        if self.dp_on and self.exchange == "sharded":
+            # (the overlapped / serial all-reduce of the whole buffer is the full update's and stays as it is)
+            print("[siss_amd] saliency mask: there is no masked sharded update; using the all-reduce")
+            self.set_overlap(self.overlap, "allreduce")
 
     def _subset(self, trainable):
         """SISSStepper(trainable=...) as a siss_amd.trainable.Subset of the engine's flat buffer (None: the full update)."""
@@ -175,6 +210,8 @@ class SISSStepper:
         if self.subset is not None and self.dp_on and (self.overlap or self.exchange == "sharded"):
             raise NotImplementedError("a trainable subset exchanges its gradients in one grouped all-reduce after the backward "
                                       "pass: set_overlap(False, 'allreduce')")
+        if self.saliency is not None and self.dp_on and self.exchange == "sharded":
+            raise NotImplementedError("a saliency-masked step has no sharded update: set_overlap(on, 'allreduce')")
         self.e.on_early_grads_final = self._early_allreduce if self.overlap else None
 
     def _gather_optimizer_state(self):
@@ -200,13 +237,14 @@ class SISSStepper:
         depends on the node.  Times `iters` steps each way (max over ranks) and keeps the faster setting."""
         if not self.dp_on or self.e.ps.split >= self.e.ps.total or self.subset is not None:
             return self.overlap                      # (a subset has one exchange mode: nothing to choose)
+        masked = self.saliency is not None           # (a masked step: overlapped or serial all-reduce, no sharded update)
         import time
         dist = torch.distributed
         results = {}
         # the three settings a node can tell apart: one all-reduce after the backward, the same exchange overlapped with it,
         # and the sharded update (reduce-scatter -> shard-local AdamW -> all-gather of the parameters)
         candidates = {"overlap": (True, "allreduce"), "serial": (False, "allreduce")}
-        if can_shard(self.e.ps.total, self.world):
+        if can_shard(self.e.ps.total, self.world) and not masked:
             candidates["serial_sharded"] = (False, "sharded")
         # the timed steps are real optimizer steps: put parameters, AdamW moments, the step counter and the stepper's own
         # state (NegGrad's decaying superfactor, the last step's statistics) back afterwards -- the run that follows starts
@@ -466,7 +504,7 @@ class SISSStepper:
             all_gather_params(self.e.ps.flat, lo, hi, self.pg)
             self.e.refresh_weights(cast_shadow=True)
             return
-        self.opt.launch(g, ranges=self._ranges, **okw)
+        self.opt.launch(g, ranges=self._ranges, mask=self._mask, **okw)
         self.e.refresh_weights(lazy=True)               # (the dgrad weight copies: beside the next forward pass)
 
     def _lora_update(self):
@@ -520,6 +558,8 @@ class SISSStepper:
         if self.subset is not None:
             return self.subset.params, self.subset.tensors
         specs = self.e.ps.specs
+        if self.saliency is not None:
+            return self.saliency.count, len(specs)
         return sum(int(sp.numel) for sp in specs.values()), len(specs)
 
 

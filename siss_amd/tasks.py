@@ -275,6 +275,82 @@ class _DeleteBase(Task):
         if lcfg is not None:
             from .lora import select_targets
             select_targets(self.unet_param_specs(), lcfg.patterns)
+        # deletion.saliency: a malformed mapping, an unknown field, a fraction outside (0, 1), batches < 1 and the key together with
+        # deletion.trainable / deletion.lora are settled here too
+        self.saliency_config()
+
+    # -- deletion.saliency: null | {fraction, batches, seed, path} (OPT-IN; siss_amd/saliency.py) --------------------------------------
+    def saliency_config(self):
+        """The parsed deletion.saliency (siss_amd.saliency.SaliencyConfig), or None (absent / null: the full update, today's run)."""
+        from .saliency import parse_saliency
+        d = self.cfg.get("deletion") or {}
+        return parse_saliency(d.get("saliency"), trainable=d.get("trainable"), lora=d.get("lora"))
+
+    def saliency_batches(self, ds_del, B):
+        """A SEPARATE iterator over the forget dataset for the mask's gradient (the loop's own forget iterator is not advanced): the
+        rows of the forget store / latent cache the loop opened, or the dataset itself."""
+        src = getattr(self, "forget_cache", None) or self.forget_store
+        if src is not None:
+            return index_batches(self.deletion_sampler(ds_del, B), B, src)
+        return batches(ds_del, self.deletion_sampler(ds_del, B), B)
+
+    def saliency_mask(self, stepper, ds_del, B, cond, device, rank, world, pg):
+        """The SaliencyMask of the run (None without the key), built once, at the pretrained weights, before step 1: loaded from
+        `path` when both files are there, else computed on `batches` forget micro-batches (the task's own prepare_batch, sample_noise
+        and conditioning `cond`, timesteps uniform in [timestep_low, T)) from a generator of its own seeded with `seed` -- the loop's
+        samplers and generator are not advanced.  More than one rank: rank 0 alone builds it, its words are broadcast and every rank
+        checks the count.  Rank 0 writes the two mask files into output_dir."""
+        sc = self.saliency_config()
+        if sc is None:
+            return None
+        from .saliency import SaliencyMask, count_bits, forget_gradient
+        eng = stepper.e
+
+        def build():
+            if sc.path is not None and SaliencyMask.present(sc.path):
+                mask = SaliencyMask.load(sc.path, eng)
+                print(f"[siss_amd] deletion.saliency: mask loaded from {sc.path} ({mask.count} of {mask.params} parameters)")
+                return mask
+            if sc.path is not None:
+                print(f"[siss_amd] deletion.saliency.path {sc.path!r} holds no mask files: computing the mask")
+            gen = torch.Generator(device=device).manual_seed(sc.seed)
+            g = forget_gradient(stepper, self.saliency_batches(ds_del, B), sc.batches, prepare=self.prepare_batch,
+                                sample_noise=self.sample_noise, conditioning=cond, timestep_low=self.timestep_low, generator=gen)
+            mask = SaliencyMask.from_gradient(eng, g, sc.fraction, batches=sc.batches, seed=sc.seed)
+            print(f"[siss_amd] deletion.saliency: |g| >= {mask.threshold:.6g} keeps {mask.count} of {mask.params} parameters "
+                  f"(k = {mask.k}, {sc.batches} forget micro-batches)")
+            return mask
+
+        if world == 1:
+            mask = build()
+        else:
+            # rank 0 builds the mask; the others learn FIRST whether it did (a refusal -- a zero threshold, a non-finite gradient, a
+            # file of another layout -- is raised on every rank: nobody waits in a broadcast for words that never come), then receive
+            # the words and check the number of set bits
+            import torch.distributed as dist
+            mask, err = None, None
+            if rank == 0:
+                try:
+                    mask = build()
+                except Exception as e:
+                    err = e
+            word = [None if rank != 0 else (f"{type(err).__name__}: {err}" if err is not None else
+                                            dict(mask.config(), set_bits=count_bits(mask.bits)))]
+            dist.broadcast_object_list(word, src=0, group=pg)
+            if isinstance(word[0], str):
+                raise err if err is not None else RuntimeError(f"deletion.saliency: rank 0 could not build the mask ({word[0]})")
+            c = word[0]
+            if rank != 0:
+                bits = torch.zeros((eng.ps.total + 31) // 32, dtype=torch.int32, device=device)
+                mask = SaliencyMask(eng, bits, c["count"], k=c["k"], threshold=c["threshold"], fraction=c["fraction"],
+                                    batches=c["batches"], seed=c["seed"])
+            dist.broadcast(mask.bits, src=0, group=pg)
+            mine = count_bits(mask.bits)
+            if mine != c["set_bits"]:
+                raise RuntimeError(f"deletion.saliency: rank {rank} holds {mine} set bits after the broadcast, rank 0 holds {c['set_bits']}")
+        if rank == 0:
+            mask.save(str(self.cfg.output_dir))
+        return mask
 
     # -- deletion.lora: null | {rank, alpha, targets, seed} (OPT-IN; siss_amd/lora.py) ------------------------------------------------
     def lora_config(self):
@@ -586,6 +662,9 @@ class _DeleteBase(Task):
         n_steps = int(cfg.training_steps) * max(1, len(d.get("img_name") or [1]))
         cond = self.conditioning(B, device)
         os.makedirs(cfg.output_dir, exist_ok=True)
+        saliency = self.saliency_mask(stepper, ds_del, B, cond, device, rank, world, pg)
+        if saliency is not None:
+            stepper.set_saliency(saliency)
 
         def record(handle, meta):
             st = handle.get()
@@ -593,6 +672,8 @@ class _DeleteBase(Task):
             st["trainable_params"], st["trainable_tensors"] = stepper.trainable_counts()
             if lora is not None:
                 st["lora_rank"], st["lora_alpha"], st["lora_params"], st["lora_tensors"] = lora.rank, lora.alpha, lora.params, lora.tensors
+            if saliency is not None:
+                st.update(saliency.log_fields())
             return st
 
         def say(st, meta):
@@ -1365,6 +1446,9 @@ class TrainUnconditional(Task):
         if (cfg.get("deletion") or {}).get("lora") is not None:
             raise NotImplementedError("deletion.lora: LoRA adapters belong to the unlearning tasks (delete_celeb / delete_tshirt / "
                                       "delete_sd); the pre-training task updates every parameter")
+        if (cfg.get("deletion") or {}).get("saliency") is not None:
+            raise NotImplementedError("deletion.saliency: the saliency mask belongs to the unlearning tasks (delete_celeb / delete_tshirt "
+                                      "/ delete_sd); the pre-training task has no forget set and updates every parameter")
 
     def dataset(self, shape):
         cfg = self.cfg
