@@ -456,7 +456,14 @@ class _DeleteBase(Task):
             if den.shape[-1] != 3:
                 raise ValueError(f"metrics.denoising_injections.sscd: the SSCD network takes 3-channel images, got {den.shape[-1]}")
             den = (den.clamp(0, 1) * 255).to(torch.uint8).contiguous()                       # grid()'s rule: truncation
-            self.injection.record(self.injection.score_u8(den), step, t_inj)                 # only the n scores leave the device
+            if self.replication is None:
+                scores = self.injection.score_u8(den)
+            else:                                            # score_u8's own launches, keeping the rows they normalise for the search
+                sc = self.injection
+                emb, scores = sc.model.embed_u8(den, sc.mean, sc.std, ref=sc.reference(den.device))
+            self.injection.record(scores, step, t_inj)                                       # only the n scores leave the device
+            if self.replication is not None:
+                self.replication.record(f"t{t_inj}", emb, step)
         den = den.cpu().numpy()
 
         def grid(a):
@@ -498,9 +505,43 @@ class _DeleteBase(Task):
         """Refuse, before the first step, a metrics block that cannot run (a host-side check: no GPU needed)."""
         self.check_membership()
         self.injection = self.check_injection_score()
+        self.replication = self.check_sscd_nn()
 
     membership_supported = True
     injection = None            # the injection check's scorer / settings (check_injection_score), None when not configured
+    replication = None          # metrics.sscd_nn: its settings (check_sscd_nn) until the index is there (open_replication), then the tracker
+
+    def sscd_nn_sources(self):
+        """What metrics.sscd_nn takes from the task: (the SSCD metric it needs, that metric's scorer or None, the default gallery
+        directory, the forget images)."""
+        cfg = self.cfg
+        inj = (cfg.get("metrics") or {}).get("denoising_injections")
+        inj = inj if isinstance(inj, dict) else {}
+        ds = cfg.get("dataset_all")
+        return ("metrics.denoising_injections.sscd", self.injection, ds.get("data_path") if isinstance(ds, dict) else None,
+                [inj.get("img_path")])
+
+    def check_sscd_nn(self):
+        """metrics.sscd_nn: {index_path, data_path, k, threshold, batch_size} (OPT-IN, absent from the repo's configs): at each
+        evaluation the images the SSCD metric embeds are also searched in an index of the whole gallery -- data_path (default: the
+        dataset's image directory) plus the forget image(s), flagged -- and {global_step, tag, nn_mean, nn_max, nn_p95, above,
+        nn_is_forget, nn_other_max, top} is appended to replication_rank0.jsonl (sscd_search.ReplicationScore).  Refused here, before
+        the first step: the key without its SSCD metric, a missing data_path, k outside 1 .. 32, a threshold that is no finite number,
+        an index_path that holds another model's index.  Returns the settings, or None."""
+        nn = (self.cfg.get("metrics") or {}).get("sscd_nn")
+        if nn is None:
+            return None
+        from .sscd_search import parse_config
+        need, scorer, default_dir, forget = self.sscd_nn_sources()
+        settings = parse_config(nn, need, scorer, default_dir, forget, os.path.join(str(self.cfg.output_dir), "replication_rank0.jsonl"))
+        self._note_eval_every("metrics.sscd_nn", "the search runs")
+        return settings
+
+    def open_replication(self, device):
+        """Rank 0, once, before step 0: the index of metrics.sscd_nn loaded from index_path, or built and saved there."""
+        if isinstance(self.replication, dict):
+            from .sscd_search import open_index
+            self.replication = open_index(self.replication, device)
 
     def check_injection_score(self):
         """metrics.denoising_injections.sscd: {model_path, data_transforms} (null / absent: nothing): the SSCD similarity of the
@@ -665,6 +706,8 @@ class _DeleteBase(Task):
         saliency = self.saliency_mask(stepper, ds_del, B, cond, device, rank, world, pg)
         if saliency is not None:
             stepper.set_saliency(saliency)
+        if rank == 0 and self.replication is not None:
+            self.open_replication(device)
 
         def record(handle, meta):
             st = handle.get()
@@ -1086,6 +1129,15 @@ class DeleteSD(_DeleteBase):
         self.kmeans = self.check_fraction_deletion()
         self.sscd = self.check_sscd()
         self.clip_iqa = self.check_clip_iqa()
+        self.replication = self.check_sscd_nn(ready=True)
+
+    def check_sscd_nn(self, ready=False):
+        """(the base's check_metrics asks before metrics.sscd is settled: answered once it is)"""
+        return super().check_sscd_nn() if ready else None
+
+    def sscd_nn_sources(self):
+        df = self.cfg.get("data_files") or {}
+        return "metrics.sscd", self.sscd, df.get("img_dir"), [df.get("mem_img_path")]
 
     def _need_vae(self, what, does):
         ckpt = str(self.cfg.get("pretrained_model_name_or_path") or "")
@@ -1357,13 +1409,19 @@ class DeleteSD(_DeleteBase):
                                                       ("metrics.clip_iqa", self.clip_iqa)) if scorer is not None]
         if active and sampler.vae is None:
             raise FileNotFoundError(f"{active[0][0]}: the validation pipeline has no VAE decoder")
+        keep = None
+        if self.replication is not None:             # metrics.sscd's pass keeps its rows: they serve sscd_<i> and the search
+            from .sscd_search import KeepEmbeddings
+            keep = KeepEmbeddings(self.sscd)
+            active = [(what, keep if scorer is self.sscd else scorer) for what, scorer in active]
+            self.replication.extra = fields
         for _, scorer in active:
             scorer.extra = fields                               # pipeline.sampler: every record says which sampler made the images
         out_type = "decoded" if active else "np" if sampler.vae is not None else "latent"
         with sampler.holding_graphs():
             for i, p in enumerate(vp):
                 e = self._prompt_embedding(p, device)
-                imgs, text_n, uncond_n, results = [], [], [], [[] for _ in active]
+                imgs, text_n, uncond_n, results, rows = [], [], [], [[] for _ in active], []
                 for _ in range(nb):
                     im, st = sampler(e, negative_prompt_embeds=self._negative_embeds, num_inference_steps=steps,
                                      guidance_scale=7.5, num_images_per_prompt=bs, generator=g, output_type=out_type)
@@ -1371,6 +1429,8 @@ class DeleteSD(_DeleteBase):
                         out, im = score_chain([scorer for _, scorer in active], im)     # uint8 [n, H, W, 3], still on the device
                         for got, one in zip(results, out):
                             got.append(one)
+                        if keep is not None:
+                            rows.append(keep.emb)
                         imgs.extend(list(im.cpu().numpy()))
                     elif out_type == "np":
                         imgs.extend(list(im))
@@ -1379,6 +1439,8 @@ class DeleteSD(_DeleteBase):
                 for (_, scorer), got in zip(active, results):
                     if got:
                         scorer.record(i, torch.cat(got).cpu(), step)
+                if rows:
+                    self.replication.record(i, torch.cat(rows), step)
                 if imgs:
                     _grid(imgs, int(np.sqrt(len(imgs)))).save(os.path.join(cfg.output_dir, f"validation_p{i}_step{step}.png"))
                 rec = {"step": step, "prompt": i, "prompt_text": None if p is None else str(p),
@@ -1412,8 +1474,14 @@ class DeleteSD(_DeleteBase):
                                           num_inference_steps=steps, guidance_scale=7.5, num_images_per_prompt=inj["num_images"],
                                           generator=g, output_type="decoded" if self.sscd is not None else "np")
         if self.sscd is not None:
-            scores, im = self.sscd.score_decoded(im)            # bytes and embeddings in one pass
+            scorer = self.sscd
+            if self.replication is not None:
+                from .sscd_search import KeepEmbeddings
+                scorer = KeepEmbeddings(self.sscd)
+            scores, im = scorer.score_decoded(im)               # bytes and embeddings in one pass
             self.sscd.record(f"inj_{inj['prompt']}", scores.cpu(), step)
+            if self.replication is not None:
+                self.replication.record(f"inj_{inj['prompt']}", scorer.emb, step)
             im = im.cpu().numpy()
         name = f"injected_mem_s{inj['strength']:g}_step{step}.png"
         _grid(list(im), int(np.sqrt(len(im)))).save(os.path.join(cfg.output_dir, name))
