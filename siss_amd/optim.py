@@ -26,18 +26,35 @@ class FlatAdamW:
         self.scalars = torch.zeros(lib.query("siss_opt_scalars_words"), dtype=torch.float32, device=dev)
         self.last_grad = None
 
-    def launch(self, grads, *, scaling_norm=None, eta=None, inf_guard=False, want_grad=False, ranges=None, mask=None):
+    def launch(self, grads, *, scaling_norm=None, eta=None, inf_guard=False, want_grad=False, ranges=None, mask=None, ewc=None):
         """Enqueue both passes (no host sync).  grads: [2, P] f32 = (g_x, g_a).  ranges: (device table, stretches, granules) of a
         trainable subset (siss_amd.trainable.Subset.table) -- norms, scaling factor, clip and update over the listed stretches
         only, every other byte of p / m / v / shadow untouched; the caller keeps the table alive (a captured step holds its address).
         mask: the packed words of a siss_amd.saliency.SaliencyMask over this buffer (int32, one bit per float) -- the same passes on
-        the elements whose bit is set (csrc/saliency.hip); the caller keeps the words alive likewise."""
+        the elements whose bit is set (csrc/saliency.hip); the caller keeps the words alive likewise.
+        ewc: a siss_amd.ewc.FisherAnchor over this buffer -- pass 1 folds strength * F * (p - pstar) into the keep-side set first
+        (csrc/ewc.hip) and grads[0] IS OVERWRITTEN with g_x + that term; pass 2 is the plain one.  Not with ranges / mask; the caller
+        keeps the anchor alive likewise."""
         n = self.p.numel()
         assert grads.dtype == torch.float32 and grads.shape == (2, n) and grads.is_contiguous()
         if eta is not None:
             mode, knob = MODE_ERASEDIFF, float(eta)
         else:
             mode, knob = (MODE_NORM_FIX_INF_GUARD if inf_guard else MODE_NORM_FIX), float(scaling_norm)
+        if ewc is not None:
+            for other, name in ((ranges, "ranges"), (mask, "mask")):
+                if other is not None:
+                    raise ValueError(f"FlatAdamW.launch({name}=..., ewc=...): the Fisher anchor is folded into the whole-buffer pass 1 "
+                                     f"only; a {'subset' if name == 'ranges' else 'masked'} update and an anchor do not combine")
+            self._ewc_check(ewc)
+            lib.call("siss_grad_norms_scale_ewc", grads[0], grads[1], self.p, ewc.pstar, ewc.fisher, n, ewc.strength, mode, knob,
+                     self.max_grad_norm, self.betas[0], self.betas[1], self.partials, self.ewc_partials, self.scalars)
+            if want_grad and (self.last_grad is None):
+                self.last_grad = torch.empty_like(self.p)
+            lib.call("siss_recombine_clip_adamw", grads[0], grads[1], self.p, self.m, self.v, self.shadow,
+                     self.last_grad if want_grad else None, n, self.lr, self.betas[0], self.betas[1],
+                     self.eps, self.wd, self.scalars)
+            return
         if mask is not None:
             if ranges is not None:
                 raise ValueError("FlatAdamW.launch(ranges=..., mask=...): a subset update and a masked update do not combine")
@@ -82,7 +99,27 @@ class FlatAdamW:
                  self.last_grad if want_grad else None, n, self.lr, self.betas[0], self.betas[1],
                  self.eps, self.wd, self.scalars)
 
-    def launch_sharded(self, gx_shard, ga_shard, lo, hi, group, *, scaling_norm=None, eta=None, inf_guard=False, ranges=None, mask=None):
+    def _ewc_check(self, ewc):
+        """Once per anchor, not per step: the kernels are there, F and pstar cover this buffer on its device, and the slab of the
+        penalty sums exists (before a step is captured: SISSStepper.set_ewc calls this)."""
+        if ewc is getattr(self, "_ewc_checked", None):
+            return
+        n = self.p.numel()
+        for name in ("siss_grad_norms_scale_ewc", "siss_ewc_partials_words"):
+            if not lib.has(name):
+                raise RuntimeError(f"this libsiss_hip.so has no {name}: a Fisher anchor needs the kernels of csrc/ewc.hip (there is no "
+                                   "fall-back to the plain update)")
+        for name, t in (("fisher", ewc.fisher), ("pstar", ewc.pstar)):
+            if not (t.dtype == torch.float32 and t.device == self.p.device and t.dim() == 1 and t.is_contiguous() and t.numel() == n
+                    and t.data_ptr() % 16 == 0):
+                raise ValueError(f"FlatAdamW.launch(ewc=...): {name} must be {n} contiguous f32 values on {self.p.device}, 16-byte "
+                                 f"aligned; got {tuple(t.shape)} {t.dtype} on {t.device}")
+        if getattr(self, "ewc_partials", None) is None:
+            self.ewc_partials = torch.zeros(lib.query("siss_ewc_partials_words"), dtype=torch.float64, device=self.p.device)
+        self._ewc_checked = ewc
+
+    def launch_sharded(self, gx_shard, ga_shard, lo, hi, group, *, scaling_norm=None, eta=None, inf_guard=False, ranges=None, mask=None,
+                       ewc=None):
         """The same update on THIS rank's parameter shard [lo, hi) (sharded data-parallel exchange):
         gx_shard / ga_shard are the rank-summed gradients of the shard.  The three norm sums are all-reduced (24 bytes),
         so every rank forms the same scaling factor and clip coefficient as the replicated update; p / m / v / shadow are
@@ -95,6 +132,9 @@ class FlatAdamW:
         if mask is not None:
             raise NotImplementedError("FlatAdamW.launch_sharded with a saliency mask: there is no masked sharded update; a masked "
                                       "update takes the all-reduce exchange (launch(mask=...))")
+        if ewc is not None:
+            raise NotImplementedError("FlatAdamW.launch_sharded with a Fisher anchor: there is no sharded fold; an anchored update "
+                                      "takes the all-reduce exchange (launch(ewc=...))")
         n = hi - lo
         assert gx_shard.numel() == n and ga_shard.numel() == n and gx_shard.dtype == torch.float32
         if eta is not None:

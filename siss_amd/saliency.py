@@ -239,6 +239,62 @@ class SaliencyMask:
         return dict(saliency_params=self.count, saliency_fraction=self.count / self.params, saliency_threshold=self.threshold)
 
 
+class quiet_backward:
+    """`with quiet_backward(stepper, what):` -- backward passes at the stepper's current weights that are no part of a step (the
+    saliency mask's forget gradient, the Fisher estimate of siss_amd/ewc.py): refused in the middle of an accumulation or with
+    collectives in flight; the data-parallel overlap hook (SISSStepper._early_allreduce) is off inside -- it would start an all-reduce
+    of the gradient tails from inside every backward pass, and the gradient is this rank's own; on exit the hook is back, the gradient
+    buffers are zero and no collective is pending."""
+
+    def __init__(self, stepper, what):
+        self.stepper, self.what = stepper, what
+
+    def __enter__(self):
+        st = self.stepper
+        if st._micro != 0:
+            raise RuntimeError(f"{self.what} in the middle of an accumulation: the gradient buffers hold a step's micro-batches")
+        if st._pending:
+            raise RuntimeError(f"{self.what} with gradient collectives of a step still in flight")
+        self.hook, st.e.on_early_grads_final = st.e.on_early_grads_final, None
+        return self
+
+    def __exit__(self, *exc):
+        e = self.stepper.e
+        e.wgrad_overwrite = False
+        e.on_early_grads_final = self.hook
+        e.ps.grads.zero_()
+        if exc[0] is None:
+            assert not self.stepper._pending, f"{self.what} started a gradient collective"
+        return False
+
+
+def backward_batch(stepper, batch, scale_batches, *, first, prepare=None, sample_noise=None, conditioning=None, timestep_low=0,
+                   generator=None):
+    """One micro-batch of the eps-MSE at the stepper's current weights into gradient set 0: the forward and the nsets = 1 backward
+    that loss_fn = simple_neg_del drives, scale 1 / (B * scale_batches).  first: the buffers are zeroed and one-split weight gradients
+    overwrite their tiles; else the micro-batch accumulates (a plain full fill, no sparse key).  Inside quiet_backward."""
+    import torch
+    from .loss import mixture_fwd, mse_bwd_seed
+    e = stepper.e
+    dev = e.device
+    T = int(stepper.ac.numel())
+    e.wgrad_overwrite = first and stepper.wgrad_overwrite
+    if first:
+        e.zero_grad()
+    a0 = batch.to(dev, non_blocking=True)              # (a tensor, or the IndexBatch of an image store / latent cache)
+    if prepare is not None:
+        a0 = prepare(a0, generator)
+    a0 = a0.to(device=dev, dtype=stepper.io_dtype).contiguous()
+    B = a0.shape[0]
+    noise = (sample_noise(a0.shape, dev, generator) if sample_noise is not None
+             else torch.randn(a0.shape, device=dev, generator=generator)).to(stepper.io_dtype).contiguous()
+    t = torch.randint(int(timestep_low), T, (B,), device=dev, generator=generator)
+    m = mixture_fwd(a0, a0, noise, t, torch.zeros(B, device=dev), stepper.ac, stepper.gamma_tab, stepper.sigma_tab, 0.5)
+    pred = e.forward(m.x_mix, t, **dict(conditioning or {}))
+    cot, _, _ = mse_bwd_seed(pred, noise, 1.0 / (B * scale_batches))
+    e.backward(cot, nsets=1)
+
+
 def forget_gradient(stepper, batches_iter, n_batches, *, prepare=None, sample_noise=None, conditioning=None, timestep_low=0,
                     generator=None):
     """The gradient of the forget eps-MSE loss at the stepper's current weights, averaged over n_batches micro-batches drawn from
@@ -248,44 +304,12 @@ def forget_gradient(stepper, batches_iter, n_batches, *, prepare=None, sample_no
     none); timesteps uniform in [timestep_low, T).  No optimizer launch and no gradient exchange (the overlap hook of a data-parallel
     stepper is off for the duration): on return the gradient buffers are zero and the parameters,
     m, v, the step counters and the sparse-fill records are what they were."""
-    import torch
-    from .loss import mixture_fwd, mse_bwd_seed
-    e = stepper.e
-    dev = e.device
-    T = int(stepper.ac.numel())
-    cond = dict(conditioning or {})
     if n_batches < 1:
         raise ValueError(f"forget_gradient: n_batches={n_batches!r}")
-    if stepper._micro != 0:
-        raise RuntimeError("forget_gradient in the middle of an accumulation: the gradient buffers hold a step's micro-batches")
-    if stepper._pending:
-        raise RuntimeError("forget_gradient with gradient collectives of a step still in flight")
-    # no exchange: the data-parallel overlap hook (SISSStepper._early_allreduce) would start an all-reduce of the gradient tails from
-    # inside every one of these backward passes -- the gradient is this rank's own
-    hook, e.on_early_grads_final = e.on_early_grads_final, None
-    try:
+    with quiet_backward(stepper, "forget_gradient"):
         for k in range(n_batches):
-            # first micro-batch: one-split weight gradients overwrite their tiles; the others accumulate (a plain full fill, no sparse key)
-            e.wgrad_overwrite = k == 0 and stepper.wgrad_overwrite
-            if k == 0:
-                e.zero_grad()
-            a0 = next(batches_iter)
-            a0 = a0.to(dev, non_blocking=True)              # (a tensor, or the IndexBatch of an image store / latent cache)
-            if prepare is not None:
-                a0 = prepare(a0, generator)
-            a0 = a0.to(device=dev, dtype=stepper.io_dtype).contiguous()
-            B = a0.shape[0]
-            noise = (sample_noise(a0.shape, dev, generator) if sample_noise is not None
-                     else torch.randn(a0.shape, device=dev, generator=generator)).to(stepper.io_dtype).contiguous()
-            t = torch.randint(int(timestep_low), T, (B,), device=dev, generator=generator)
-            m = mixture_fwd(a0, a0, noise, t, torch.zeros(B, device=dev), stepper.ac, stepper.gamma_tab, stepper.sigma_tab, 0.5)
-            pred = e.forward(m.x_mix, t, **cond)
-            cot, _, _ = mse_bwd_seed(pred, noise, 1.0 / (B * n_batches))
-            e.backward(cot, nsets=1)
-        g = e.ps.grads[0].clone()
-    finally:
-        e.wgrad_overwrite = False
-        e.on_early_grads_final = hook
-        e.ps.grads.zero_()
-    assert not stepper._pending, "forget_gradient started a gradient collective"
+            # first micro-batch: one-split weight gradients overwrite their tiles; the others accumulate
+            backward_batch(stepper, next(batches_iter), n_batches, first=k == 0, prepare=prepare, sample_noise=sample_noise,
+                           conditioning=conditioning, timestep_low=timestep_low, generator=generator)
+        g = stepper.e.ps.grads[0].clone()
     return g

@@ -41,7 +41,8 @@ class SISSStepper:
     def __init__(self, engine: UNetEngine, alphas_cumprod, *, lr, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=1e-2, scaling_norm=None, eta=None, lambd=0.5, train_batch_size,
                  grad_accum=1, max_grad_norm=1.0, loss_fn=SISS, inf_guard=False, process_group=None,
-                 mixed_precision="bf16", superfactor=1.0, superfactor_decay=None, trainable=None, lora=None, saliency=None):
+                 mixed_precision="bf16", superfactor=1.0, superfactor_decay=None, trainable=None, lora=None, saliency=None,
+                 ewc=None):
         """trainable: None (every parameter: the reference's protocol), an iterable of parameter names, or "requires_grad" (the flags
         of the parameters of the UNet2DModel / UNet2DConditionModel that owns the engine).  With a subset the norms, the scaling
         factor, the clip and the AdamW update run over the trainable tensors only; the rest keep every byte.  The selection (the
@@ -58,7 +59,12 @@ class SISSStepper:
         of the flat buffer -- the norms, the scaling factor, the clip and the AdamW update run over the elements whose bit is set
         (csrc/saliency.hip), every other byte of the parameters, their moments and their shadow keeps its value.  The backward pass
         and the gradient exchange are the full update's (every weight-gradient product runs, the whole buffer is summed); exclusive
-        with trainable= and lora=.  The mask's words live as long as the stepper: a captured step holds their address."""
+        with trainable= and lora=.  The mask's words live as long as the stepper: a captured step holds their address.
+
+        ewc: None, or a siss_amd.ewc.FisherAnchor over this engine (opt-in, not the reference's protocol): once per optimizer step,
+        after the accumulation and the data-parallel exchange, strength * F * (theta - theta*) is added to the keep-side gradient set
+        inside pass 1 of the update (csrc/ewc.hip), so that the norms, the scaling factor, the clip and AdamW see it; exclusive with
+        trainable=, lora= and saliency=.  F and theta* live as long as the stepper: a captured step holds their addresses."""
         self.e = engine
         self.lora = lora
         self.saliency = None
@@ -67,6 +73,12 @@ class SISSStepper:
                 if other is not None:
                     raise ValueError(f"SISSStepper(saliency=..., {name}=...): the saliency mask selects single weights of every tensor; "
                                      f"saliency and {name} do not combine")
+        self.ewc = None
+        if ewc is not None:
+            for other, name in ((trainable, "trainable"), (lora, "lora"), (saliency, "saliency")):
+                if other is not None:
+                    raise ValueError(f"SISSStepper(ewc=..., {name}=...): the Fisher anchor is folded into the whole-buffer update; "
+                                     f"ewc and {name} do not combine")
         if lora is not None:
             if trainable is not None:
                 raise ValueError("SISSStepper(lora=..., trainable=...): a LoRA run trains the adapters of its targets and nothing else")
@@ -149,11 +161,38 @@ class SISSStepper:
         self.set_overlap(overlap)
         if saliency is not None:
             self.set_saliency(saliency)
+        if ewc is not None:
+            self.set_ewc(ewc)
+
+    def set_ewc(self, anchor):
+        """Fold the penalty gradient of `anchor` (siss_amd.ewc.FisherAnchor over this engine) into the keep-side set from the next step
+        on -- what SISSStepper(ewc=anchor) does; a task calls it once its Fisher is computed (FisherAnchor.from_batches needs the
+        stepper).  Before a step is captured: a captured step holds the addresses of F and theta*."""
+        if self.lora is not None or self.subset is not None or self.saliency is not None:
+            raise ValueError("SISSStepper.set_ewc on a stepper with " +
+                             ("lora" if self.lora is not None else "trainable" if self.subset is not None else "saliency") +
+                             ": ewc does not combine with lora / trainable / saliency")
+        from .ewc import require_kernels
+        from .saliency import fingerprint
+        require_kernels()
+        fp = fingerprint(self.e)
+        if (anchor.total, anchor.tensors, anchor.params) != (fp["total"], fp["tensors"], fp["real_params"]):
+            raise ValueError("SISSStepper(ewc=...): the anchor was built over another engine's parameter layout")
+        if anchor.fisher.device != self.e.ps.flat.device:
+            raise ValueError("SISSStepper(ewc=...): the anchor's tensors are on another device than the engine")
+        self.opt._ewc_check(anchor)                    # (the slab of the penalty sums: allocated now, not inside a captured step)
+        self.ewc = anchor
+        if self.dp_on and self.exchange == "sharded":
+            # (the overlapped / serial all-reduce of the whole buffer is the full update's and stays as it is)
+            print("[siss_amd] Fisher anchor: there is no sharded fold; using the all-reduce")
+            self.set_overlap(self.overlap, "allreduce")
 
     def set_saliency(self, mask):
         """Restrict the update to the set bits of `mask` (siss_amd.saliency.SaliencyMask over this engine) from the next step on -- what
         SISSStepper(saliency=mask) does; a task calls it once its mask is computed (forget_gradient needs the stepper).  Before a step
         is captured: a captured step holds the address of the words it was captured with."""
+        if self.ewc is not None:
+            raise ValueError("SISSStepper.set_saliency on a stepper with ewc: saliency does not combine with a Fisher anchor")
         if self.lora is not None or self.subset is not None:
             raise ValueError("SISSStepper.set_saliency on a stepper with " + ("lora" if self.lora is not None else "trainable") +
                              ": saliency does not combine with lora / trainable")
@@ -212,6 +251,8 @@ class SISSStepper:
                                       "pass: set_overlap(False, 'allreduce')")
         if self.saliency is not None and self.dp_on and self.exchange == "sharded":
             raise NotImplementedError("a saliency-masked step has no sharded update: set_overlap(on, 'allreduce')")
+        if self.ewc is not None and self.dp_on and self.exchange == "sharded":
+            raise NotImplementedError("a step with a Fisher anchor has no sharded update: set_overlap(on, 'allreduce')")
         self.e.on_early_grads_final = self._early_allreduce if self.overlap else None
 
     def _gather_optimizer_state(self):
@@ -237,7 +278,7 @@ class SISSStepper:
         depends on the node.  Times `iters` steps each way (max over ranks) and keeps the faster setting."""
         if not self.dp_on or self.e.ps.split >= self.e.ps.total or self.subset is not None:
             return self.overlap                      # (a subset has one exchange mode: nothing to choose)
-        masked = self.saliency is not None           # (a masked step: overlapped or serial all-reduce, no sharded update)
+        masked = self.saliency is not None or self.ewc is not None   # (masked / anchored: overlapped or serial all-reduce, no sharded update)
         import time
         dist = torch.distributed
         results = {}
@@ -504,7 +545,10 @@ class SISSStepper:
             all_gather_params(self.e.ps.flat, lo, hi, self.pg)
             self.e.refresh_weights(cast_shadow=True)
             return
-        self.opt.launch(g, ranges=self._ranges, mask=self._mask, **okw)
+        if self.ewc is not None:
+            self.opt.launch(g, ewc=self.ewc, **okw)     # (g[0] becomes g_x + strength * F * (theta - theta*): zeroed before the next step)
+        else:
+            self.opt.launch(g, ranges=self._ranges, mask=self._mask, **okw)
         self.e.refresh_weights(lazy=True)               # (the dgrad weight copies: beside the next forward pass)
 
     def _lora_update(self):
@@ -548,8 +592,11 @@ class SISSStepper:
             done.record()
         else:
             host, done = dev.clone(), None
+        stats_from, ewc = self.opt.stats_from, self.ewc
+        if ewc is not None:                      # (slots 12 / 13 of the same block: no further copy)
+            stats_from = lambda s: dict(self.opt.stats_from(s), **ewc.stats_from(s))
         return _PendingStats(host, done, keys, sizes, last.get("subscore"), last.get("superfactor") if "superfactor" in last else None,
-                             self.opt.stats_from)
+                             stats_from)
 
     def trainable_counts(self):
         """(trainable_params, trainable_tensors) of every log line: the parameters the optimizer updates."""

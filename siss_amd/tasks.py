@@ -278,6 +278,86 @@ class _DeleteBase(Task):
         # deletion.saliency: a malformed mapping, an unknown field, a fraction outside (0, 1), batches < 1 and the key together with
         # deletion.trainable / deletion.lora are settled here too
         self.saliency_config()
+        # deletion.ewc: a malformed mapping, an unknown field, a missing or non-positive strength, batches / batch_size < 1 and the key
+        # together with deletion.trainable / deletion.lora / deletion.saliency are settled here too
+        self.ewc_config()
+
+    # -- deletion.ewc: null | {strength, batches, batch_size, seed, normalize, path} (OPT-IN; siss_amd/ewc.py) -------------------------
+    def ewc_config(self):
+        """The parsed deletion.ewc (siss_amd.ewc.EWCConfig), or None (absent / null: no anchor, today's run)."""
+        from .ewc import parse_ewc
+        d = self.cfg.get("deletion") or {}
+        return parse_ewc(d.get("ewc"), trainable=d.get("trainable"), lora=d.get("lora"), saliency=d.get("saliency"))
+
+    def ewc_batches(self, ds_all, bs, device):
+        """A SEPARATE iterator (with close()) over the keep dataset for the Fisher estimate (the loop's own keep iterator is not
+        advanced): the rows of the keep store / latent cache the loop opened, or the dataset itself through a prefetcher of its own."""
+        src = getattr(self, "keep_cache", None) or self.keep_store
+        if src is not None:
+            return index_batches(InfiniteSampler(ds_all, rank=0, num_replicas=1), bs, src)
+        return _DeleteBase.keep_batches(self, ds_all, bs, 0, 1, device)
+
+    def ewc_anchor(self, stepper, ds_all, B, cond, device, rank, world, pg):
+        """The FisherAnchor of the run (None without the key), built once, at the pretrained weights, before step 1: F loaded from
+        `path` when both files are there, else the empirical Fisher of the keep eps-MSE on `batches` keep micro-batches of
+        `batch_size` (null: train_batch_size) from a keep iterator of its own (keep_batches: with an image store or a latent cache on,
+        the index batches go to prepare_batch unchanged), the task's prepare_batch, sample_noise and conditioning, timesteps uniform in
+        [timestep_low, T), and a generator of its own seeded with `seed` -- the loop's iterators and generator are not advanced.  More
+        than one rank: rank 0 alone builds F, the ranks agree on success, then F is broadcast.  Rank 0 writes the two files into
+        output_dir."""
+        ec = self.ewc_config()
+        if ec is None:
+            return None
+        from .ewc import FisherAnchor
+        eng = stepper.e
+        bs = int(ec.batch_size or B)
+
+        def build():
+            if ec.path is not None and FisherAnchor.present(ec.path):
+                anchor = FisherAnchor.load(ec.path, eng, ec.strength)
+                print(f"[siss_amd] deletion.ewc: Fisher loaded from {ec.path} (strength {ec.strength:g})")
+                return anchor
+            if ec.path is not None:
+                print(f"[siss_amd] deletion.ewc.path {ec.path!r} holds no Fisher files: computing the Fisher")
+            gen = torch.Generator(device=device).manual_seed(ec.seed)
+            it = self.ewc_batches(ds_all, bs, device)
+            try:
+                cond_b = cond if bs == B else self.conditioning(bs, device)
+                anchor = FisherAnchor.from_batches(stepper, it, ec.batches, strength=ec.strength, prepare=self.prepare_batch,
+                                                   sample_noise=self.sample_noise, conditioning=cond_b,
+                                                   timestep_low=self.timestep_low, generator=gen, normalize=ec.normalize,
+                                                   batch_size=bs, seed=ec.seed)
+            finally:
+                it.close()
+            print(f"[siss_amd] deletion.ewc: empirical Fisher of {ec.batches} keep micro-batches of {bs} (mean {anchor.mean:.6g}, max "
+                  f"{anchor.max:.6g}, {anchor.zeros} zeros before normalisation), strength {ec.strength:g}")
+            return anchor
+
+        if world == 1:
+            anchor = build()
+        else:
+            # rank 0 builds F; the others learn FIRST whether it did (a refusal -- a non-finite or all-zero F, a file of another layout
+            # -- is raised on every rank: nobody waits in a broadcast for values that never come), then receive F
+            import torch.distributed as dist
+            anchor, err = None, None
+            if rank == 0:
+                try:
+                    anchor = build()
+                except Exception as e:
+                    err = e
+            word = [None if rank != 0 else (f"{type(err).__name__}: {err}" if err is not None else anchor.config())]
+            dist.broadcast_object_list(word, src=0, group=pg)
+            if isinstance(word[0], str):
+                raise err if err is not None else RuntimeError(f"deletion.ewc: rank 0 could not build the Fisher ({word[0]})")
+            c = word[0]
+            if rank != 0:
+                anchor = FisherAnchor(eng, torch.zeros_like(eng.ps.flat), eng.ps.flat.detach().clone(), ec.strength,
+                                      batches=c["batches"], batch_size=c["batch_size"], seed=c["seed"], normalize=c["normalize"],
+                                      mean=c["mean"], max=c["max"], zeros=c["zeros"], source=c["source"])
+            dist.broadcast(anchor.fisher, src=0, group=pg)
+        if rank == 0:
+            anchor.save(str(self.cfg.output_dir))
+        return anchor
 
     # -- deletion.saliency: null | {fraction, batches, seed, path} (OPT-IN; siss_amd/saliency.py) --------------------------------------
     def saliency_config(self):
@@ -706,6 +786,9 @@ class _DeleteBase(Task):
         saliency = self.saliency_mask(stepper, ds_del, B, cond, device, rank, world, pg)
         if saliency is not None:
             stepper.set_saliency(saliency)
+        ewc = self.ewc_anchor(stepper, ds_all, B, cond, device, rank, world, pg)
+        if ewc is not None:
+            stepper.set_ewc(ewc)
         if rank == 0 and self.replication is not None:
             self.open_replication(device)
 
@@ -717,6 +800,8 @@ class _DeleteBase(Task):
                 st["lora_rank"], st["lora_alpha"], st["lora_params"], st["lora_tensors"] = lora.rank, lora.alpha, lora.params, lora.tensors
             if saliency is not None:
                 st.update(saliency.log_fields())
+            if ewc is not None:
+                st.update(ewc.log_fields())            # (ewc_penalty / ewc_grad_norm: the step's own block, SISSStepper.stats_async)
             return st
 
         def say(st, meta):
@@ -1517,6 +1602,9 @@ class TrainUnconditional(Task):
         if (cfg.get("deletion") or {}).get("saliency") is not None:
             raise NotImplementedError("deletion.saliency: the saliency mask belongs to the unlearning tasks (delete_celeb / delete_tshirt "
                                       "/ delete_sd); the pre-training task has no forget set and updates every parameter")
+        if (cfg.get("deletion") or {}).get("ewc") is not None:
+            raise NotImplementedError("deletion.ewc: the Fisher anchor belongs to the unlearning tasks (delete_celeb / delete_tshirt / "
+                                      "delete_sd); the pre-training task has no pretrained weights to stay near")
 
     def dataset(self, shape):
         cfg = self.cfg
