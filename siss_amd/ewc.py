@@ -13,10 +13,8 @@ gradient of the batch-mean loss (batch_size 1 gives the per-sample Fisher).  It 
 The files: `fisher.safetensors` (key `fisher`, the flat buffer's layout) beside `fisher.json` (strength, batches, batch_size, seed,
 normalize, mean / max before the normalisation, the zero count, whether it was computed or loaded, and the fingerprint of the buffer).
 """
-import json
-import os
-
-from .saliency import fingerprint
+from .variants import (backward_batch, exclusive, files_present, fingerprint, load_tensor, need_bool, need_fields, need_int,
+                       need_opt_str, quiet_backward, real_mask, save_tensor)
 
 KEY = "deletion.ewc"
 FISHER_FILE, CONFIG_FILE = "fisher.safetensors", "fisher.json"
@@ -35,10 +33,6 @@ class EWCConfig:
         return {k: getattr(self, k) for k in FIELDS}
 
 
-def _is_int(x):
-    return isinstance(x, int) and not isinstance(x, bool)
-
-
 def check_strength(strength, key=KEY + ".strength"):
     import math
     if isinstance(strength, bool) or not isinstance(strength, (int, float)) or not math.isfinite(strength) or not strength > 0:
@@ -53,33 +47,18 @@ def parse_ewc(value, trainable=None, lora=None, saliency=None):
     a path that is no string, and the key together with deletion.trainable, deletion.lora or deletion.saliency (those keys' values)."""
     if value is None:
         return None
-    if not hasattr(value, "keys"):
-        raise ValueError(f"{KEY}={value!r}: a mapping {{{', '.join(FIELDS)}}} is needed (e.g. +{KEY}={{strength:10,batches:8}})")
-    for other, name in ((trainable, "deletion.trainable"), (lora, "deletion.lora"), (saliency, "deletion.saliency")):
-        if other is not None:
-            raise ValueError(f"{KEY} together with {name}: the anchor is folded into the whole-buffer update, {name} runs passes of "
-                             "its own -- leave one of the two keys out")
-    value = dict(value)
-    unknown = sorted(set(value) - set(FIELDS))
-    if unknown:
-        raise ValueError(f"{KEY}: unknown field(s) {unknown} ({', '.join(FIELDS)})")
+    value = need_fields(KEY, value, FIELDS, "{strength:10,batches:8}")
+    exclusive("config", {KEY: value, "deletion.saliency": saliency, "deletion.lora": lora, "deletion.trainable": trainable})
     v = dict(DEFAULTS, **{k: x for k, x in value.items() if x is not None})
     if v["strength"] is None:
         raise ValueError(f"{KEY}.strength is required: a number > 0")
-    strength = check_strength(v["strength"])
-    batches, batch_size, seed, normalize, path = v["batches"], v["batch_size"], v["seed"], v["normalize"], v["path"]
-    if not _is_int(batches) or batches < 1:
-        raise ValueError(f"{KEY}.batches={batches!r}: a positive number of keep micro-batches is needed")
-    if batch_size is not None and (not _is_int(batch_size) or batch_size < 1):
-        raise ValueError(f"{KEY}.batch_size={batch_size!r}: null (train_batch_size) or a positive micro-batch size is needed (1: the "
-                         "per-sample Fisher)")
-    if not _is_int(seed):
-        raise ValueError(f"{KEY}.seed={seed!r}: an integer is needed")
-    if not isinstance(normalize, bool):
-        raise ValueError(f"{KEY}.normalize={normalize!r}: true or false is needed")
-    if path is not None and not isinstance(path, str):
-        raise ValueError(f"{KEY}.path={path!r}: null or the directory that holds {FISHER_FILE} and {CONFIG_FILE}")
-    return EWCConfig(strength, batches, batch_size, seed, normalize, path)
+    batch_size = v["batch_size"]
+    if batch_size is not None:
+        need_int(KEY + ".batch_size", batch_size, True, "null (train_batch_size) or a positive micro-batch size (1: the per-sample Fisher)")
+    return EWCConfig(check_strength(v["strength"]),
+                     need_int(KEY + ".batches", v["batches"], True, "a positive number of keep micro-batches"), batch_size,
+                     need_int(KEY + ".seed", v["seed"]), need_bool(KEY + ".normalize", v["normalize"]),
+                     need_opt_str(KEY + ".path", v["path"], f"the directory that holds {FISHER_FILE} and {CONFIG_FILE}"))
 
 
 def require_kernels():
@@ -88,15 +67,6 @@ def require_kernels():
         if not lib.has(name):
             raise RuntimeError(f"this libsiss_hip.so has no {name}: a Fisher anchor needs the kernels of csrc/ewc.hip (there is no "
                                "fall-back to the plain update)")
-
-
-def real_mask(specs, total, device=None):
-    """[total] bool: True on the real parameters of a flat buffer, False on its alignment padding."""
-    import torch
-    real = torch.zeros(int(total), dtype=torch.bool, device=device)
-    for sp in specs.values():
-        real[sp.off:sp.off + sp.numel] = True
-    return real
 
 
 def normalize_fisher(F, real):
@@ -160,7 +130,6 @@ class FisherAnchor:
         step counters and sparse-fill records are what they were.  normalize: F is divided by its f64 mean over the real parameters."""
         import torch
         from . import lib
-        from .saliency import backward_batch, quiet_backward
         require_kernels()
         if n_batches < 1:
             raise ValueError(f"FisherAnchor.from_batches: n_batches={n_batches!r}")
@@ -186,29 +155,17 @@ class FisherAnchor:
 
     def save(self, directory):
         """fisher.safetensors + fisher.json under `directory` (safetensors and JSON only)."""
-        from safetensors.torch import save_file
-        os.makedirs(directory, exist_ok=True)
-        save_file({"fisher": self.fisher.cpu().contiguous()}, os.path.join(directory, FISHER_FILE))
-        with open(os.path.join(directory, CONFIG_FILE), "w") as f:
-            json.dump(self.config(), f, indent=1)
+        save_tensor(directory, FISHER_FILE, "fisher", self.fisher, CONFIG_FILE, self.config())
 
     @staticmethod
     def present(directory):
-        return bool(directory) and all(os.path.isfile(os.path.join(str(directory), f)) for f in (FISHER_FILE, CONFIG_FILE))
+        return files_present(directory, FISHER_FILE, CONFIG_FILE)
 
     @classmethod
     def load(cls, directory, engine, strength):
         """The F saved under `directory`, anchored at `engine`'s CURRENT weights with `strength`: refused when it was taken over another
         buffer (ps.total, the tensor count or the real parameter count differ)."""
-        from safetensors.torch import load_file
-        with open(os.path.join(directory, CONFIG_FILE)) as f:
-            c = json.load(f)
-        fp = fingerprint(engine)
-        for key in ("total", "tensors", "real_params"):
-            if int(c.get(key, -1)) != fp[key]:
-                raise ValueError(f"{os.path.join(directory, CONFIG_FILE)}: {key} = {c.get(key)!r}, this UNet has {fp[key]} -- the Fisher "
-                                 "was computed for another architecture or parameter layout")
-        F = load_file(os.path.join(directory, FISHER_FILE))["fisher"]
+        F, c = load_tensor(directory, FISHER_FILE, "fisher", CONFIG_FILE, engine, "Fisher")
         return cls(engine, F, engine.ps.flat.detach().clone(), strength, batches=c.get("batches"), batch_size=c.get("batch_size"),
                    seed=c.get("seed"), normalize=c.get("normalize"), mean=c.get("mean"), max=c.get("max"), zeros=c.get("zeros"),
                    source="loaded")

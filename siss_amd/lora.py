@@ -15,6 +15,7 @@ import math
 import os
 
 from .trainable import parse_patterns, select
+from .variants import exclusive, need_fields, need_int
 
 MAX_RANK = 64
 TILE = 64                       # rows / columns of a target one block owns (csrc/lora.hip kTile; checked against siss_lora_tile)
@@ -38,15 +39,8 @@ def parse_lora(value, trainable=None):
     field, and the key together with deletion.trainable (`trainable`: that key's value)."""
     if value is None:
         return None
-    if not hasattr(value, "keys"):
-        raise ValueError(f"{KEY}={value!r}: a mapping {{rank, alpha, targets, seed}} is needed (e.g. +{KEY}={{rank:4,targets:[attn]}})")
-    if trainable is not None:
-        raise ValueError(f"{KEY} together with deletion.trainable: a LoRA run trains the adapters of its targets and nothing else -- "
-                         "leave one of the two keys out")
-    value = dict(value)
-    unknown = sorted(set(value) - {"rank", "alpha", "targets", "seed"})
-    if unknown:
-        raise ValueError(f"{KEY}: unknown field(s) {unknown} (rank, alpha, targets, seed)")
+    value = need_fields(KEY, value, ("rank", "alpha", "targets", "seed"), "{rank:4,targets:[attn]}")
+    exclusive("config", {KEY: value, "deletion.trainable": trainable})
     rank = value.get("rank")
     if isinstance(rank, bool) or not isinstance(rank, int) or not 1 <= rank <= MAX_RANK:
         raise ValueError(f"{KEY}.rank={rank!r}: an integer in 1..{MAX_RANK} is needed")
@@ -58,8 +52,7 @@ def parse_lora(value, trainable=None):
     seed = value.get("seed", 0)
     if seed is None:
         seed = 0
-    if isinstance(seed, bool) or not isinstance(seed, int):
-        raise ValueError(f"{KEY}.seed={seed!r}: an integer is needed")
+    need_int(KEY + ".seed", seed)
     if "targets" not in value or value["targets"] is None:
         raise ValueError(f"{KEY}.targets is missing: a list of regular expressions over the parameter names (e.g. [attn])")
     patterns = parse_patterns(value["targets"], key=KEY + ".targets")
@@ -260,6 +253,10 @@ class LoRAState:
     def config(self):
         return dict(rank=self.rank, alpha=self.alpha, targets=list(self.names), seed=self.seed, base_checkpoint=self.base,
                     steps=int(self.steps), lora_params=self.params)
+
+    def log_fields(self):
+        """What every log line of a LoRA run carries."""
+        return dict(lora_rank=self.rank, lora_alpha=self.alpha, lora_params=self.params, lora_tensors=self.tensors)
 
     def save(self, directory):
         """pytorch_lora_weights.safetensors + lora_config.json under `directory` (safetensors and JSON only)."""

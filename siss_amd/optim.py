@@ -3,9 +3,17 @@ delete_celeb.py:714-773 (reference) in two streaming passes; see csrc/optimizer.
 import torch
 
 from . import lib
+from .variants import SHARD, exclusive
 
 MODE_NORM_FIX, MODE_ERASEDIFF, MODE_NORM_FIX_INF_GUARD = 0, 1, 2
 EMA_STEP, EMA_ONE_MINUS_DECAY, EMA_DECAY = 5, 6, 7        # slots of the single-set block (csrc/train_state.hip TrainScalars)
+
+
+def _mode_knob(scaling_norm, eta, inf_guard):
+    """(mode, knob) of pass 1: eta selects EraseDiff's recombination, else the norm fix with or without the inf guard."""
+    if eta is not None:
+        return MODE_ERASEDIFF, float(eta)
+    return (MODE_NORM_FIX_INF_GUARD if inf_guard else MODE_NORM_FIX), float(scaling_norm)
 
 
 class FlatAdamW:
@@ -37,27 +45,14 @@ class FlatAdamW:
         keeps the anchor alive likewise."""
         n = self.p.numel()
         assert grads.dtype == torch.float32 and grads.shape == (2, n) and grads.is_contiguous()
-        if eta is not None:
-            mode, knob = MODE_ERASEDIFF, float(eta)
-        else:
-            mode, knob = (MODE_NORM_FIX_INF_GUARD if inf_guard else MODE_NORM_FIX), float(scaling_norm)
+        mode, knob = _mode_knob(scaling_norm, eta, inf_guard)
+        exclusive("FlatAdamW.launch", {"ranges=": ranges, "mask=": mask, "ewc=": ewc})
+        # pass 1 takes (gx, ga, *head, mode .. partials, *tail, scalars), pass 2 (gx .. g_out, n, *sel, lr .. scalars)
+        one, two, head, tail, sel = "siss_grad_norms_scale", "siss_recombine_clip_adamw", None, (), ()
         if ewc is not None:
-            for other, name in ((ranges, "ranges"), (mask, "mask")):
-                if other is not None:
-                    raise ValueError(f"FlatAdamW.launch({name}=..., ewc=...): the Fisher anchor is folded into the whole-buffer pass 1 "
-                                     f"only; a {'subset' if name == 'ranges' else 'masked'} update and an anchor do not combine")
             self._ewc_check(ewc)
-            lib.call("siss_grad_norms_scale_ewc", grads[0], grads[1], self.p, ewc.pstar, ewc.fisher, n, ewc.strength, mode, knob,
-                     self.max_grad_norm, self.betas[0], self.betas[1], self.partials, self.ewc_partials, self.scalars)
-            if want_grad and (self.last_grad is None):
-                self.last_grad = torch.empty_like(self.p)
-            lib.call("siss_recombine_clip_adamw", grads[0], grads[1], self.p, self.m, self.v, self.shadow,
-                     self.last_grad if want_grad else None, n, self.lr, self.betas[0], self.betas[1],
-                     self.eps, self.wd, self.scalars)
-            return
-        if mask is not None:
-            if ranges is not None:
-                raise ValueError("FlatAdamW.launch(ranges=..., mask=...): a subset update and a masked update do not combine")
+            one, head, tail = "siss_grad_norms_scale_ewc", (self.p, ewc.pstar, ewc.fisher, n, ewc.strength), (self.ewc_partials,)
+        elif mask is not None:
             if mask is not getattr(self, "_mask_checked", None):      # once per mask, not per step
                 for name in ("siss_grad_norms_scale_masked", "siss_recombine_clip_adamw_masked"):
                     if not lib.has(name):
@@ -69,35 +64,21 @@ class FlatAdamW:
                                      f"aligned, are needed (one bit per float of the buffer); got {tuple(mask.shape)} {mask.dtype} on "
                                      f"{mask.device} at offset {mask.data_ptr() % 16} of a 16-byte line")
                 self._mask_checked = mask
-            if want_grad and (self.last_grad is None):
-                self.last_grad = torch.zeros_like(self.p)    # (written where a bit is set only: zero elsewhere)
-            lib.call("siss_grad_norms_scale_masked", grads[0], grads[1], n, mask, mode, knob, self.max_grad_norm,
-                     self.betas[0], self.betas[1], self.partials, self.scalars)
-            lib.call("siss_recombine_clip_adamw_masked", grads[0], grads[1], self.p, self.m, self.v, self.shadow,
-                     self.last_grad if want_grad else None, n, mask, self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
-                     self.scalars)
-            return
-        if ranges is not None:
-            if want_grad and (self.last_grad is None):
-                self.last_grad = torch.zeros_like(self.p)    # (written on the stretches only: zero elsewhere)
+            one, two, sel = "siss_grad_norms_scale_masked", "siss_recombine_clip_adamw_masked", (mask,)
+        elif ranges is not None:
             if not lib.has("siss_recombine_clip_adamw_ranges"):
                 raise RuntimeError("this libsiss_hip.so has no siss_recombine_clip_adamw_ranges: a trainable subset needs the "
                                    "subset kernels of csrc/optimizer.hip (there is no fall-back to the full update)")
             tab, nr, granules = ranges
             assert tab.dtype == torch.int64 and tab.device == self.p.device and tab.numel() == 2 * nr + 1 and n % 4 == 0
-            lib.call("siss_grad_norms_scale_ranges", grads[0], grads[1], n, tab, nr, granules, mode, knob, self.max_grad_norm,
-                     self.betas[0], self.betas[1], self.partials, self.scalars)
-            lib.call("siss_recombine_clip_adamw_ranges", grads[0], grads[1], self.p, self.m, self.v, self.shadow,
-                     self.last_grad if want_grad else None, n, tab, nr, granules, self.lr, self.betas[0], self.betas[1],
-                     self.eps, self.wd, self.scalars)
-            return
-        lib.call("siss_grad_norms_scale", grads[0], grads[1], n, mode, knob, self.max_grad_norm,
-                 self.betas[0], self.betas[1], self.partials, self.scalars)
+            one, two, sel = "siss_grad_norms_scale_ranges", "siss_recombine_clip_adamw_ranges", (tab, nr, granules)
         if want_grad and (self.last_grad is None):
-            self.last_grad = torch.empty_like(self.p)
-        lib.call("siss_recombine_clip_adamw", grads[0], grads[1], self.p, self.m, self.v, self.shadow,
-                 self.last_grad if want_grad else None, n, self.lr, self.betas[0], self.betas[1],
-                 self.eps, self.wd, self.scalars)
+            # (ranges / mask write their stretches / set bits only: zero elsewhere)
+            self.last_grad = torch.zeros_like(self.p) if sel else torch.empty_like(self.p)
+        lib.call(one, grads[0], grads[1], *(head or (n, *sel)), mode, knob, self.max_grad_norm, self.betas[0], self.betas[1],
+                 self.partials, *tail, self.scalars)
+        lib.call(two, grads[0], grads[1], self.p, self.m, self.v, self.shadow, self.last_grad if want_grad else None, n, *sel,
+                 self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.scalars)
 
     def _ewc_check(self, ewc):
         """Once per anchor, not per step: the kernels are there, F and pstar cover this buffer on its device, and the slab of the
@@ -126,21 +107,10 @@ class FlatAdamW:
         touched on [lo, hi) only -- the caller all-gathers the parameters afterwards."""
         import ctypes
         import torch.distributed as dist
-        if ranges is not None:
-            raise NotImplementedError("FlatAdamW.launch_sharded with a trainable subset: the sharded exchange splits the WHOLE buffer "
-                                      "over the ranks; a subset update takes the all-reduce exchange (launch(ranges=...))")
-        if mask is not None:
-            raise NotImplementedError("FlatAdamW.launch_sharded with a saliency mask: there is no masked sharded update; a masked "
-                                      "update takes the all-reduce exchange (launch(mask=...))")
-        if ewc is not None:
-            raise NotImplementedError("FlatAdamW.launch_sharded with a Fisher anchor: there is no sharded fold; an anchored update "
-                                      "takes the all-reduce exchange (launch(ewc=...))")
+        exclusive("FlatAdamW.launch_sharded", {"ranges=": ranges, "mask=": mask, "ewc=": ewc, SHARD: True}, NotImplementedError)
         n = hi - lo
         assert gx_shard.numel() == n and ga_shard.numel() == n and gx_shard.dtype == torch.float32
-        if eta is not None:
-            mode, knob = MODE_ERASEDIFF, float(eta)
-        else:
-            mode, knob = (MODE_NORM_FIX_INF_GUARD if inf_guard else MODE_NORM_FIX), float(scaling_norm)
+        mode, knob = _mode_knob(scaling_norm, eta, inf_guard)
         nblk = ctypes.c_int(0)
         lib.call("siss_grad_norm_partials", gx_shard, ga_shard, n, self.partials, ctypes.byref(nblk))
         sums = self.partials.view(-1, 3)[:nblk.value].sum(dim=0, keepdim=True)      # [1, 3] f64 on the device

@@ -9,9 +9,10 @@ k-th largest magnitude, found on the device by an integer radix select (siss_abs
 The mask files: `saliency_mask.safetensors` (the packed words, key `bits`) beside `saliency.json` (fraction, k, count, threshold,
 batches, seed and the fingerprint of the buffer the bits index: ps.total, the tensor count, real_params).
 """
-import json
-import os
 import struct
+
+from .variants import (backward_batch, exclusive, files_present, fingerprint, load_tensor, need_fields, need_int, need_opt_str,
+                       quiet_backward, real_mask, save_tensor)
 
 KEY = "deletion.saliency"
 MASK_FILE, CONFIG_FILE = "saliency_mask.safetensors", "saliency.json"
@@ -47,26 +48,13 @@ def parse_saliency(value, trainable=None, lora=None):
     together with deletion.trainable or deletion.lora (`trainable`, `lora`: those keys' values)."""
     if value is None:
         return None
-    if not hasattr(value, "keys"):
-        raise ValueError(f"{KEY}={value!r}: a mapping {{fraction, batches, seed, path}} is needed (e.g. +{KEY}={{fraction:0.5,batches:8}})")
-    for other, name in ((trainable, "deletion.trainable"), (lora, "deletion.lora")):
-        if other is not None:
-            raise ValueError(f"{KEY} together with {name}: the saliency mask selects single weights of every tensor, {name} selects "
-                             "its own -- leave one of the two keys out")
-    value = dict(value)
-    unknown = sorted(set(value) - set(FIELDS))
-    if unknown:
-        raise ValueError(f"{KEY}: unknown field(s) {unknown} ({', '.join(FIELDS)})")
-    v = dict(DEFAULTS, **{k: x for k, x in value.items() if x is not None or k == "path"})
-    fraction = check_fraction(v["fraction"])
-    batches, seed, path = v["batches"], v["seed"], v["path"]
-    if isinstance(batches, bool) or not isinstance(batches, int) or batches < 1:
-        raise ValueError(f"{KEY}.batches={batches!r}: a positive number of forget micro-batches is needed")
-    if isinstance(seed, bool) or not isinstance(seed, int):
-        raise ValueError(f"{KEY}.seed={seed!r}: an integer is needed")
-    if path is not None and not isinstance(path, str):
-        raise ValueError(f"{KEY}.path={path!r}: null or the directory that holds {MASK_FILE} and {CONFIG_FILE}")
-    return SaliencyConfig(fraction, batches, seed, path)
+    value = need_fields(KEY, value, FIELDS, "{fraction:0.5,batches:8}")
+    exclusive("config", {KEY: value, "deletion.lora": lora, "deletion.trainable": trainable})
+    v = dict(DEFAULTS, **{k: x for k, x in value.items() if x is not None})
+    return SaliencyConfig(check_fraction(v["fraction"]),
+                          need_int(KEY + ".batches", v["batches"], True, "a positive number of forget micro-batches"),
+                          need_int(KEY + ".seed", v["seed"]),
+                          need_opt_str(KEY + ".path", v["path"], f"the directory that holds {MASK_FILE} and {CONFIG_FILE}"))
 
 
 def bits_to_float(bits):
@@ -79,12 +67,6 @@ def require_kernels():
         if not lib.has(name):
             raise RuntimeError(f"this libsiss_hip.so has no {name}: a saliency mask needs the kernels of csrc/saliency.hip (there is no "
                                "fall-back to the full update)")
-
-
-def fingerprint(engine):
-    """What the bits of a mask index: the flat buffer's length, the tensor count and the number of real (non-padding) parameters."""
-    ps = engine.ps
-    return dict(total=int(ps.total), tensors=len(ps.specs), real_params=sum(int(sp.numel) for sp in ps.specs.values()))
 
 
 def select_magnitude(g, k):
@@ -193,9 +175,7 @@ class SaliencyMask:
         flags = torch.as_tensor(tensor).reshape(-1).to(engine.device) != 0
         if flags.numel() != ps.total:
             raise ValueError(f"SaliencyMask.from_bool: {flags.numel()} flags for a flat buffer of {ps.total} floats")
-        real = torch.zeros(ps.total, dtype=torch.bool, device=engine.device)
-        for sp in ps.specs.values():
-            real[sp.off:sp.off + sp.numel] = True
+        real = real_mask(ps.specs, ps.total, engine.device)
         return cls(engine, pack_bool(flags), int((flags & real).sum()))
 
     def to_bool(self):
@@ -208,91 +188,23 @@ class SaliencyMask:
 
     def save(self, directory):
         """saliency_mask.safetensors + saliency.json under `directory` (safetensors and JSON only)."""
-        from safetensors.torch import save_file
-        os.makedirs(directory, exist_ok=True)
-        save_file({"bits": self.bits.cpu().contiguous()}, os.path.join(directory, MASK_FILE))
-        with open(os.path.join(directory, CONFIG_FILE), "w") as f:
-            json.dump(self.config(), f, indent=1)
+        save_tensor(directory, MASK_FILE, "bits", self.bits, CONFIG_FILE, self.config())
 
     @staticmethod
     def present(directory):
-        return bool(directory) and all(os.path.isfile(os.path.join(str(directory), f)) for f in (MASK_FILE, CONFIG_FILE))
+        return files_present(directory, MASK_FILE, CONFIG_FILE)
 
     @classmethod
     def load(cls, directory, engine):
         """The mask saved under `directory`, for `engine`: refused when it was taken over another buffer (ps.total, the tensor count
         or the real parameter count differ)."""
-        from safetensors.torch import load_file
-        with open(os.path.join(directory, CONFIG_FILE)) as f:
-            c = json.load(f)
-        fp = fingerprint(engine)
-        for key in ("total", "tensors", "real_params"):
-            if int(c.get(key, -1)) != fp[key]:
-                raise ValueError(f"{os.path.join(directory, CONFIG_FILE)}: {key} = {c.get(key)!r}, this UNet has {fp[key]} -- the mask "
-                                 "was computed for another architecture or parameter layout")
-        bits = load_file(os.path.join(directory, MASK_FILE))["bits"]
+        bits, c = load_tensor(directory, MASK_FILE, "bits", CONFIG_FILE, engine, "mask")
         return cls(engine, bits, c["count"], k=c.get("k"), threshold=c.get("threshold"), fraction=c.get("fraction"),
                    batches=c.get("batches"), seed=c.get("seed"))
 
     def log_fields(self):
         """What every log line of a masked run carries."""
         return dict(saliency_params=self.count, saliency_fraction=self.count / self.params, saliency_threshold=self.threshold)
-
-
-class quiet_backward:
-    """`with quiet_backward(stepper, what):` -- backward passes at the stepper's current weights that are no part of a step (the
-    saliency mask's forget gradient, the Fisher estimate of siss_amd/ewc.py): refused in the middle of an accumulation or with
-    collectives in flight; the data-parallel overlap hook (SISSStepper._early_allreduce) is off inside -- it would start an all-reduce
-    of the gradient tails from inside every backward pass, and the gradient is this rank's own; on exit the hook is back, the gradient
-    buffers are zero and no collective is pending."""
-
-    def __init__(self, stepper, what):
-        self.stepper, self.what = stepper, what
-
-    def __enter__(self):
-        st = self.stepper
-        if st._micro != 0:
-            raise RuntimeError(f"{self.what} in the middle of an accumulation: the gradient buffers hold a step's micro-batches")
-        if st._pending:
-            raise RuntimeError(f"{self.what} with gradient collectives of a step still in flight")
-        self.hook, st.e.on_early_grads_final = st.e.on_early_grads_final, None
-        return self
-
-    def __exit__(self, *exc):
-        e = self.stepper.e
-        e.wgrad_overwrite = False
-        e.on_early_grads_final = self.hook
-        e.ps.grads.zero_()
-        if exc[0] is None:
-            assert not self.stepper._pending, f"{self.what} started a gradient collective"
-        return False
-
-
-def backward_batch(stepper, batch, scale_batches, *, first, prepare=None, sample_noise=None, conditioning=None, timestep_low=0,
-                   generator=None):
-    """One micro-batch of the eps-MSE at the stepper's current weights into gradient set 0: the forward and the nsets = 1 backward
-    that loss_fn = simple_neg_del drives, scale 1 / (B * scale_batches).  first: the buffers are zeroed and one-split weight gradients
-    overwrite their tiles; else the micro-batch accumulates (a plain full fill, no sparse key).  Inside quiet_backward."""
-    import torch
-    from .loss import mixture_fwd, mse_bwd_seed
-    e = stepper.e
-    dev = e.device
-    T = int(stepper.ac.numel())
-    e.wgrad_overwrite = first and stepper.wgrad_overwrite
-    if first:
-        e.zero_grad()
-    a0 = batch.to(dev, non_blocking=True)              # (a tensor, or the IndexBatch of an image store / latent cache)
-    if prepare is not None:
-        a0 = prepare(a0, generator)
-    a0 = a0.to(device=dev, dtype=stepper.io_dtype).contiguous()
-    B = a0.shape[0]
-    noise = (sample_noise(a0.shape, dev, generator) if sample_noise is not None
-             else torch.randn(a0.shape, device=dev, generator=generator)).to(stepper.io_dtype).contiguous()
-    t = torch.randint(int(timestep_low), T, (B,), device=dev, generator=generator)
-    m = mixture_fwd(a0, a0, noise, t, torch.zeros(B, device=dev), stepper.ac, stepper.gamma_tab, stepper.sigma_tab, 0.5)
-    pred = e.forward(m.x_mix, t, **dict(conditioning or {}))
-    cot, _, _ = mse_bwd_seed(pred, noise, 1.0 / (B * scale_batches))
-    e.backward(cot, nsets=1)
 
 
 def forget_gradient(stepper, batches_iter, n_batches, *, prepare=None, sample_noise=None, conditioning=None, timestep_low=0,

@@ -25,6 +25,7 @@ from .dp import EXCHANGES, allreduce_flat_grads, allreduce_pieces, can_shard
 from .loss import loss_bwd_seed, mixture_fwd, mse_bwd_seed
 from .optim import FlatAdamW
 from .unet import UNetEngine
+from .variants import VARIANTS, exchange_refusal, exclusive, same_layout
 
 SISS = "importance_sampling_with_mixture"
 NO_IS = "double_forward_with_neg_del"
@@ -67,21 +68,9 @@ class SISSStepper:
         trainable=, lora= and saliency=.  F and theta* live as long as the stepper: a captured step holds their addresses."""
         self.e = engine
         self.lora = lora
-        self.saliency = None
-        if saliency is not None:
-            for other, name in ((trainable, "trainable"), (lora, "lora")):
-                if other is not None:
-                    raise ValueError(f"SISSStepper(saliency=..., {name}=...): the saliency mask selects single weights of every tensor; "
-                                     f"saliency and {name} do not combine")
-        self.ewc = None
-        if ewc is not None:
-            for other, name in ((trainable, "trainable"), (lora, "lora"), (saliency, "saliency")):
-                if other is not None:
-                    raise ValueError(f"SISSStepper(ewc=..., {name}=...): the Fisher anchor is folded into the whole-buffer update; "
-                                     f"ewc and {name} do not combine")
+        self.saliency = self.ewc = None
+        exclusive("SISSStepper", {"ewc=": ewc, "saliency=": saliency, "lora=": lora, "trainable=": trainable})
         if lora is not None:
-            if trainable is not None:
-                raise ValueError("SISSStepper(lora=..., trainable=...): a LoRA run trains the adapters of its targets and nothing else")
             if lora.engine is not engine:
                 raise ValueError("SISSStepper(lora=...): the LoRAState was built over another engine")
             trainable = list(lora.names)
@@ -126,9 +115,11 @@ class SISSStepper:
                                  shadow=None)
         self.subset = self._subset(trainable)
         engine.set_trainable(self.subset)
-        # (the table is built once and lives as long as the stepper: a captured step holds its address)
-        self._ranges = None if self.subset is None or lora is not None else self.subset.table(dev)
-        self._mask = None
+        # the ONE resolved variant (siss_amd/variants.py: at most one is active); set_saliency / set_ewc move a `full` stepper to theirs
+        self.variant = "lora" if lora is not None else "trainable" if self.subset is not None else "full"
+        # what FlatAdamW.launch takes beside the gradients (the table is built once and lives as long as the stepper: a captured step
+        # holds its address)
+        self._launch_kw = {"ranges": self.subset.table(dev)} if self.variant == "trainable" else {}
         self._micro = 0
         self.last = None
         self._pending = []
@@ -139,75 +130,59 @@ class SISSStepper:
         self.exchange = os.environ.get("SISS_DP_EXCHANGE", "allreduce")      # serial mode: "allreduce" | "sharded"
         self._state_shard = None                # (lo, hi) while AdamW's moments are current on this rank's shard only
         assert self.exchange in EXCHANGES
-        overlap = self.dp_on and engine.ps.split < engine.ps.total and os.environ.get("SISS_DP_OVERLAP", "1") != "0"
-        if lora is not None and self.dp_on:
-            # the exchange of a LoRA step: ONE all-reduce of the adapters' [2, L] gradient pair after the projection (linear: the same sum)
-            if overlap:
-                print("[siss_amd] lora: the overlapped early-tail gradient exchange is off (one all-reduce of the adapter gradients "
-                      "after the backward pass)")
-                overlap = False
-            if self.exchange == "sharded":
-                print("[siss_amd] lora: the sharded exchange splits the whole buffer over the ranks; using the all-reduce")
-                self.exchange = "allreduce"
-        elif self.subset is not None and self.dp_on:
-            # the exchange of a subset step: ONE grouped collective over the trainable pieces after the backward pass
-            if overlap:
-                print("[siss_amd] trainable subset: the overlapped early-tail gradient exchange is off (one grouped all-reduce of the "
-                      "trainable pieces after the backward pass)")
-                overlap = False
-            if self.exchange == "sharded":
-                print("[siss_amd] trainable subset: the sharded exchange splits the whole buffer over the ranks; using the all-reduce")
-                self.exchange = "allreduce"
-        self.set_overlap(overlap)
+        self._fit_exchange(self.dp_on and engine.ps.split < engine.ps.total and os.environ.get("SISS_DP_OVERLAP", "1") != "0")
         if saliency is not None:
             self.set_saliency(saliency)
         if ewc is not None:
             self.set_ewc(ewc)
 
+    def _fit_exchange(self, overlap):
+        """set_overlap with what the variant may use of (overlap, self.exchange): a LoRA / subset step has ONE collective after the
+        backward pass, a masked / anchored step the whole-buffer all-reduce (overlapped or serial) -- saying what it switched off."""
+        if self.dp_on:
+            why = exchange_refusal(self.variant, overlap, "allreduce")
+            if why:
+                print(f"[siss_amd] {why}")
+                overlap = False
+            why = exchange_refusal(self.variant, False, self.exchange)
+            if why:
+                print(f"[siss_amd] {why}; using the all-reduce")
+                self.exchange = "allreduce"
+        self.set_overlap(overlap)
+
+    def _adopt(self, name, obj, tensor, require_kernels, launch_kw, ready=None):
+        """set_saliency / set_ewc: a `full` stepper moves to variant `name` (another object of the stepper's own variant replaces the
+        first).  tensor: the per-float device tensor of obj, which must cover this engine's flat buffer on its device; ready(obj): what
+        has to exist before a step is captured."""
+        present = {"ewc=": self.ewc, "saliency=": self.saliency, "lora=": self.lora, "trainable=": self.subset}
+        del present[name + "="]
+        exclusive(f"SISSStepper.set_{name}", {name + "=": obj, **present})
+        require_kernels()
+        what = VARIANTS[name].what
+        if not same_layout(obj, self.e):
+            raise ValueError(f"SISSStepper({name}=...): the {what} was built over another engine's parameter layout")
+        if tensor.device != self.e.ps.flat.device:
+            raise ValueError(f"SISSStepper({name}=...): the {what}'s tensors are on another device than the engine")
+        if ready is not None:
+            ready(obj)
+        setattr(self, name, obj)
+        self.variant, self._launch_kw = name, launch_kw
+        self._fit_exchange(self.overlap)
+
     def set_ewc(self, anchor):
         """Fold the penalty gradient of `anchor` (siss_amd.ewc.FisherAnchor over this engine) into the keep-side set from the next step
         on -- what SISSStepper(ewc=anchor) does; a task calls it once its Fisher is computed (FisherAnchor.from_batches needs the
         stepper).  Before a step is captured: a captured step holds the addresses of F and theta*."""
-        if self.lora is not None or self.subset is not None or self.saliency is not None:
-            raise ValueError("SISSStepper.set_ewc on a stepper with " +
-                             ("lora" if self.lora is not None else "trainable" if self.subset is not None else "saliency") +
-                             ": ewc does not combine with lora / trainable / saliency")
         from .ewc import require_kernels
-        from .saliency import fingerprint
-        require_kernels()
-        fp = fingerprint(self.e)
-        if (anchor.total, anchor.tensors, anchor.params) != (fp["total"], fp["tensors"], fp["real_params"]):
-            raise ValueError("SISSStepper(ewc=...): the anchor was built over another engine's parameter layout")
-        if anchor.fisher.device != self.e.ps.flat.device:
-            raise ValueError("SISSStepper(ewc=...): the anchor's tensors are on another device than the engine")
-        self.opt._ewc_check(anchor)                    # (the slab of the penalty sums: allocated now, not inside a captured step)
-        self.ewc = anchor
-        if self.dp_on and self.exchange == "sharded":
-            # (the overlapped / serial all-reduce of the whole buffer is the full update's and stays as it is)
-            print("[siss_amd] Fisher anchor: there is no sharded fold; using the all-reduce")
-            self.set_overlap(self.overlap, "allreduce")
+        # (ready: the slab of the penalty sums is allocated now, not inside a captured step)
+        self._adopt("ewc", anchor, anchor.fisher, require_kernels, {"ewc": anchor}, ready=self.opt._ewc_check)
 
     def set_saliency(self, mask):
         """Restrict the update to the set bits of `mask` (siss_amd.saliency.SaliencyMask over this engine) from the next step on -- what
         SISSStepper(saliency=mask) does; a task calls it once its mask is computed (forget_gradient needs the stepper).  Before a step
         is captured: a captured step holds the address of the words it was captured with."""
-        if self.ewc is not None:
-            raise ValueError("SISSStepper.set_saliency on a stepper with ewc: saliency does not combine with a Fisher anchor")
-        if self.lora is not None or self.subset is not None:
-            raise ValueError("SISSStepper.set_saliency on a stepper with " + ("lora" if self.lora is not None else "trainable") +
-                             ": saliency does not combine with lora / trainable")
-        from .saliency import fingerprint, require_kernels
-        require_kernels()
-        fp = fingerprint(self.e)
-        if (mask.total, mask.tensors, mask.params) != (fp["total"], fp["tensors"], fp["real_params"]):
-            raise ValueError("SISSStepper(saliency=...): the mask was built over another engine's parameter layout")
-        if mask.bits.device != self.e.ps.flat.device:
-            raise ValueError("SISSStepper(saliency=...): the mask's words are on another device than the engine")
-        self.saliency, self._mask = mask, mask.bits
-        if self.dp_on and self.exchange == "sharded":
-            # (the overlapped / serial all-reduce of the whole buffer is the full update's and stays as it is)
-            print("[siss_amd] saliency mask: there is no masked sharded update; using the all-reduce")
-            self.set_overlap(self.overlap, "allreduce")
+        from .saliency import require_kernels
+        self._adopt("saliency", mask, mask.bits, require_kernels, {"mask": mask.bits})
 
     def _subset(self, trainable):
         """SISSStepper(trainable=...) as a siss_amd.trainable.Subset of the engine's flat buffer (None: the full update)."""
@@ -243,16 +218,9 @@ class SISSStepper:
         if exchange is not None:
             assert exchange in EXCHANGES
             self.exchange = exchange
-        if self.lora is not None and self.dp_on and (self.overlap or self.exchange == "sharded"):
-            raise NotImplementedError("a LoRA step exchanges its adapter gradients in one all-reduce after the backward pass: "
-                                      "set_overlap(False, 'allreduce')")
-        if self.subset is not None and self.dp_on and (self.overlap or self.exchange == "sharded"):
-            raise NotImplementedError("a trainable subset exchanges its gradients in one grouped all-reduce after the backward "
-                                      "pass: set_overlap(False, 'allreduce')")
-        if self.saliency is not None and self.dp_on and self.exchange == "sharded":
-            raise NotImplementedError("a saliency-masked step has no sharded update: set_overlap(on, 'allreduce')")
-        if self.ewc is not None and self.dp_on and self.exchange == "sharded":
-            raise NotImplementedError("a step with a Fisher anchor has no sharded update: set_overlap(on, 'allreduce')")
+        why = exchange_refusal(self.variant, self.overlap, self.exchange) if self.dp_on else None
+        if why:
+            raise NotImplementedError(f"{why}: set_overlap({'on' if VARIANTS[self.variant].overlap is None else 'False'}, 'allreduce')")
         self.e.on_early_grads_final = self._early_allreduce if self.overlap else None
 
     def _gather_optimizer_state(self):
@@ -272,28 +240,43 @@ class SISSStepper:
         self._gather_optimizer_state()
         return self.opt.m, self.opt.v, self.opt.scalars
 
+    def _save_state(self):
+        """For callers that run REAL optimizer steps only to time them (autotune_overlap, try_captured_serial): clones parameters, AdamW
+        moments and the step counter, notes the stepper's own state (NegGrad's decaying superfactor, the last step's statistics, the
+        accumulation count) and returns the function that puts all of it back -- the run that follows starts from what it was given."""
+        self._gather_optimizer_state()          # sharded steps before this call left the moments current on the owner's shard only
+        tensors = (self.opt.p, self.opt.m, self.opt.v, self.opt.scalars)
+        saved = [t.clone() for t in tensors]
+        state = (self.superfactor, self.last, self._micro)
+
+        def restore():
+            self._state_shard = None            # (the moments are overwritten as a whole)
+            for dst, src in zip(tensors, saved):
+                dst.copy_(src)
+            self.superfactor, self.last, self._micro = state
+            if self.lora is not None:
+                # opt.p is the adapters' buffer: the master follows it (autotune_overlap returns early for a LoRA stepper, so only
+                # try_captured_serial reaches this)
+                self.lora.merge()
+            self.e.refresh_weights(cast_shadow=True)
+        return restore
+
     def autotune_overlap(self, step_fn, iters=3):
         """Measure, don't guess: the overlapped exchange shares the chip with the persistent one-block-per-CU GEMMs of
         the high-resolution backward, and whether RCCL's workgroups cost those kernels more than the overlap hides
         depends on the node.  Times `iters` steps each way (max over ranks) and keeps the faster setting."""
-        if not self.dp_on or self.e.ps.split >= self.e.ps.total or self.subset is not None:
-            return self.overlap                      # (a subset has one exchange mode: nothing to choose)
-        masked = self.saliency is not None or self.ewc is not None   # (masked / anchored: overlapped or serial all-reduce, no sharded update)
+        # the three settings a node can tell apart: one all-reduce after the backward, the same exchange overlapped with it,
+        # and the sharded update (reduce-scatter -> shard-local AdamW -> all-gather of the parameters) -- those the variant may use
+        candidates = {"overlap": (True, "allreduce"), "serial": (False, "allreduce")}
+        if can_shard(self.e.ps.total, self.world):
+            candidates["serial_sharded"] = (False, "sharded")
+        candidates = {name: c for name, c in candidates.items() if exchange_refusal(self.variant, *c) is None}
+        if not self.dp_on or self.e.ps.split >= self.e.ps.total or "overlap" not in candidates:
+            return self.overlap                      # (a subset / LoRA step has one exchange mode: nothing to choose)
         import time
         dist = torch.distributed
-        results = {}
-        # the three settings a node can tell apart: one all-reduce after the backward, the same exchange overlapped with it,
-        # and the sharded update (reduce-scatter -> shard-local AdamW -> all-gather of the parameters)
-        candidates = {"overlap": (True, "allreduce"), "serial": (False, "allreduce")}
-        if can_shard(self.e.ps.total, self.world) and not masked:
-            candidates["serial_sharded"] = (False, "sharded")
-        # the timed steps are real optimizer steps: put parameters, AdamW moments, the step counter and the stepper's own
-        # state (NegGrad's decaying superfactor, the last step's statistics) back afterwards -- the run that follows starts
-        # from what it was given, whichever candidate wins
-        self._gather_optimizer_state()          # sharded steps before this call left the moments current on the owner's shard only
-        saved = [t.clone() for t in (self.opt.p, self.opt.m, self.opt.v, self.opt.scalars)]
-        saved_state = (self.superfactor, self.last, self._micro)
-        errors = {}
+        results, errors = {}, {}
+        restore = self._save_state()            # (the timed steps are real optimizer steps)
         for name, (mode, exch) in candidates.items():
             self.set_overlap(mode, exch)
             exc = None
@@ -329,12 +312,7 @@ class SISSStepper:
             dist.all_reduce(tt, op=dist.ReduceOp.MAX, group=self.pg)
             results[name] = float(tt.item()) / iters
         best = min(results, key=results.get)
-        self._state_shard = None                                 # (the moments are overwritten as a whole below)
-        for dst, src in zip((self.opt.p, self.opt.m, self.opt.v, self.opt.scalars), saved):
-            dst.copy_(src)
-        del saved
-        self.superfactor, self.last, self._micro = saved_state
-        self.e.refresh_weights(cast_shadow=True)
+        restore()
         self.set_overlap(best.startswith("overlap"), candidates[best][1])
         self.overlap_timings = {k + "_ms": v * 1e3 for k, v in results.items()}
         if errors:
@@ -350,9 +328,7 @@ class SISSStepper:
         or (None, None, reason) with the previous exchange mode restored -- in process, no re-exec, no relaunch."""
         dist = torch.distributed
         import time
-        self._gather_optimizer_state()
-        saved = [t.clone() for t in (self.opt.p, self.opt.m, self.opt.v, self.opt.scalars)]
-        saved_state = (self.superfactor, self.last, self._micro)
+        restore = self._save_state()
         prev = (self.overlap, self.exchange)
         self.set_overlap(False, "allreduce")
         graph, err, secs = None, None, None
@@ -384,13 +360,8 @@ class SISSStepper:
         else:
             graph, err = None, err or "capture failed on another rank"
             torch.cuda.synchronize()
-        self._pending, self._state_shard = [], None
-        for dst, src in zip((self.opt.p, self.opt.m, self.opt.v, self.opt.scalars), saved):
-            dst.copy_(src)
-        self.superfactor, self.last, self._micro = saved_state
-        if self.lora is not None:
-            self.lora.merge()                           # (opt.p is the adapters' buffer: the master follows it)
-        self.e.refresh_weights(cast_shadow=True)
+        self._pending = []
+        restore()
         if graph is None:
             self.set_overlap(*prev)
         return graph, secs, err
@@ -531,9 +502,7 @@ class SISSStepper:
                 self._pending = []
             else:
                 (EXCHANGES.get(self.exchange) or allreduce_flat_grads)(g, self.pg)     # 'sharded' that cannot shard: all-reduce
-        single = self.loss_fn in (NEG_GRAD, NAIVE)
-        okw = dict(scaling_norm=self.scaling_norm if not single else 1.0,
-                   eta=self.eta if self.loss_fn == ERASEDIFF else None, inf_guard=self.inf_guard or single)
+        okw = self._update_kw()
         if sharded:
             # reduce-scatter -> this rank's 1/N of the norm sums (3 doubles all-reduced) and of the recombine / clip / AdamW
             # pass -> all-gather of the updated f32 parameters (3 P (N-1)/N floats on the wire instead of 4 P (N-1)/N,
@@ -545,11 +514,15 @@ class SISSStepper:
             all_gather_params(self.e.ps.flat, lo, hi, self.pg)
             self.e.refresh_weights(cast_shadow=True)
             return
-        if self.ewc is not None:
-            self.opt.launch(g, ewc=self.ewc, **okw)     # (g[0] becomes g_x + strength * F * (theta - theta*): zeroed before the next step)
-        else:
-            self.opt.launch(g, ranges=self._ranges, mask=self._mask, **okw)
+        # (with an anchor g[0] becomes g_x + strength * F * (theta - theta*): zeroed before the next step)
+        self.opt.launch(g, **self._launch_kw, **okw)
         self.e.refresh_weights(lazy=True)               # (the dgrad weight copies: beside the next forward pass)
+
+    def _update_kw(self):
+        """The recombination of the step as FlatAdamW's keywords: the single-set objectives run the inf-guarded norm fix with s = 0."""
+        single = self.loss_fn in (NEG_GRAD, NAIVE)
+        return dict(scaling_norm=self.scaling_norm if not single else 1.0, eta=self.eta if self.loss_fn == ERASEDIFF else None,
+                    inf_guard=self.inf_guard or single)
 
     def _lora_update(self):
         """The update of a LoRA step: project -> (all-reduce of the adapter gradients) -> norms / recombine / clip / AdamW on the
@@ -559,8 +532,7 @@ class SISSStepper:
         lora.project(nsets=1 if single else 2)
         if self.dp_on:
             allreduce_flat_grads(lora.g, self.pg)       # (the projection is linear: the sum of the ranks' dW projected = this sum)
-        self.opt.launch(lora.g, scaling_norm=self.scaling_norm if not single else 1.0,
-                        eta=self.eta if self.loss_fn == ERASEDIFF else None, inf_guard=self.inf_guard or single)
+        self.opt.launch(lora.g, **self._update_kw())
         lora.merge()
         lora.steps += 1
         self.e.refresh_weights(lazy=True)               # every derived operand copy comes out of the refresh that follows AdamW today
@@ -592,11 +564,20 @@ class SISSStepper:
             done.record()
         else:
             host, done = dev.clone(), None
-        stats_from, ewc = self.opt.stats_from, self.ewc
-        if ewc is not None:                      # (slots 12 / 13 of the same block: no further copy)
-            stats_from = lambda s: dict(self.opt.stats_from(s), **ewc.stats_from(s))
+        # (a variant with fields of its own in the optimizer's scalar block reads them from the same copy: FisherAnchor.stats_from)
         return _PendingStats(host, done, keys, sizes, last.get("subscore"), last.get("superfactor") if "superfactor" in last else None,
-                             stats_from)
+                             self.opt.stats_from, getattr(self._active(), "stats_from", None))
+
+    def _active(self):
+        """The object of the active variant that carries log fields (None: the full update, a trainable subset)."""
+        return {"lora": self.lora, "saliency": self.saliency, "ewc": self.ewc}.get(self.variant)
+
+    def log_fields(self):
+        """What every log line of the run carries beside the step's statistics: the parameters the optimizer updates and the active
+        variant's own fields."""
+        params, tensors = self.trainable_counts()
+        active = self._active()
+        return dict(trainable_params=params, trainable_tensors=tensors, **(active.log_fields() if active is not None else {}))
 
     def trainable_counts(self):
         """(trainable_params, trainable_tensors) of every log line: the parameters the optimizer updates."""
@@ -613,9 +594,10 @@ class SISSStepper:
 class _PendingStats:
     """Handle of SISSStepper.stats_async()."""
 
-    def __init__(self, host, done, keys, sizes, subscore, superfactor, opt_stats_from):
+    def __init__(self, host, done, keys, sizes, subscore, superfactor, opt_stats_from, variant_stats_from=None):
         self.host, self.done, self.keys, self.sizes = host, done, keys, sizes
-        self.subscore, self.superfactor, self.opt_stats_from = subscore, superfactor, opt_stats_from
+        self.subscore, self.superfactor = subscore, superfactor
+        self.opt_stats_from, self.variant_stats_from = opt_stats_from, variant_stats_from
 
     def get(self):
         import math
@@ -623,6 +605,8 @@ class _PendingStats:
             self.done.synchronize()
         host = self.host
         st = self.opt_stats_from(host[:self.sizes[0]])
+        if self.variant_stats_from is not None:
+            st.update(self.variant_stats_from(host[:self.sizes[0]]))
         off = self.sizes[0]
         vals = {}
         for k, n in zip(self.keys, self.sizes[1:]):

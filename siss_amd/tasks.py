@@ -192,6 +192,36 @@ def _sampler_fields(cfg, solver):
     return None if solver is None else solver.record_fields(_inference_steps(cfg))
 
 
+def _built_on_rank0(failed, build, describe, empty, tensor_of, save_dir, rank, world, pg, check=None):
+    """An object the run builds once from its data, the same on every rank (the saliency mask, the Fisher anchor): rank 0 alone runs
+    build(); the others learn FIRST whether it did -- describe(obj), or the error as a string: a refusal (a zero threshold, a non-finite
+    or all-zero F, a file of another layout) is raised on every rank, so nobody waits in a broadcast for values that never come --
+    then make empty(description) and receive tensor_of(obj); check(obj, description) runs on every rank after the broadcast; rank 0
+    saves into save_dir.  failed: how the other ranks' error begins."""
+    if world == 1:
+        obj = build()
+    else:
+        import torch.distributed as dist
+        obj, err = None, None
+        if rank == 0:
+            try:
+                obj = build()
+            except Exception as e:
+                err = e
+        word = [None if rank != 0 else (f"{type(err).__name__}: {err}" if err is not None else describe(obj))]
+        dist.broadcast_object_list(word, src=0, group=pg)
+        if isinstance(word[0], str):
+            raise err if err is not None else RuntimeError(f"{failed} ({word[0]})")
+        if rank != 0:
+            obj = empty(word[0])
+        dist.broadcast(tensor_of(obj), src=0, group=pg)
+        if check is not None:
+            check(obj, word[0])
+    if rank == 0:
+        obj.save(save_dir)
+    return obj
+
+
 class _DeleteBase(Task):
     timestep_low = 999          # delete_celeb.py:593 hard-codes randint(999, 1000)
     inf_guard = False
@@ -333,31 +363,12 @@ class _DeleteBase(Task):
                   f"{anchor.max:.6g}, {anchor.zeros} zeros before normalisation), strength {ec.strength:g}")
             return anchor
 
-        if world == 1:
-            anchor = build()
-        else:
-            # rank 0 builds F; the others learn FIRST whether it did (a refusal -- a non-finite or all-zero F, a file of another layout
-            # -- is raised on every rank: nobody waits in a broadcast for values that never come), then receive F
-            import torch.distributed as dist
-            anchor, err = None, None
-            if rank == 0:
-                try:
-                    anchor = build()
-                except Exception as e:
-                    err = e
-            word = [None if rank != 0 else (f"{type(err).__name__}: {err}" if err is not None else anchor.config())]
-            dist.broadcast_object_list(word, src=0, group=pg)
-            if isinstance(word[0], str):
-                raise err if err is not None else RuntimeError(f"deletion.ewc: rank 0 could not build the Fisher ({word[0]})")
-            c = word[0]
-            if rank != 0:
-                anchor = FisherAnchor(eng, torch.zeros_like(eng.ps.flat), eng.ps.flat.detach().clone(), ec.strength,
-                                      batches=c["batches"], batch_size=c["batch_size"], seed=c["seed"], normalize=c["normalize"],
-                                      mean=c["mean"], max=c["max"], zeros=c["zeros"], source=c["source"])
-            dist.broadcast(anchor.fisher, src=0, group=pg)
-        if rank == 0:
-            anchor.save(str(self.cfg.output_dir))
-        return anchor
+        def empty(c):
+            return FisherAnchor(eng, torch.zeros_like(eng.ps.flat), eng.ps.flat.detach().clone(), ec.strength,
+                                **{k: c[k] for k in ("batches", "batch_size", "seed", "normalize", "mean", "max", "zeros", "source")})
+
+        return _built_on_rank0("deletion.ewc: rank 0 could not build the Fisher", build, FisherAnchor.config, empty,
+                               lambda anchor: anchor.fisher, str(self.cfg.output_dir), rank, world, pg)
 
     # -- deletion.saliency: null | {fraction, batches, seed, path} (OPT-IN; siss_amd/saliency.py) --------------------------------------
     def saliency_config(self):
@@ -401,36 +412,18 @@ class _DeleteBase(Task):
                   f"(k = {mask.k}, {sc.batches} forget micro-batches)")
             return mask
 
-        if world == 1:
-            mask = build()
-        else:
-            # rank 0 builds the mask; the others learn FIRST whether it did (a refusal -- a zero threshold, a non-finite gradient, a
-            # file of another layout -- is raised on every rank: nobody waits in a broadcast for words that never come), then receive
-            # the words and check the number of set bits
-            import torch.distributed as dist
-            mask, err = None, None
-            if rank == 0:
-                try:
-                    mask = build()
-                except Exception as e:
-                    err = e
-            word = [None if rank != 0 else (f"{type(err).__name__}: {err}" if err is not None else
-                                            dict(mask.config(), set_bits=count_bits(mask.bits)))]
-            dist.broadcast_object_list(word, src=0, group=pg)
-            if isinstance(word[0], str):
-                raise err if err is not None else RuntimeError(f"deletion.saliency: rank 0 could not build the mask ({word[0]})")
-            c = word[0]
-            if rank != 0:
-                bits = torch.zeros((eng.ps.total + 31) // 32, dtype=torch.int32, device=device)
-                mask = SaliencyMask(eng, bits, c["count"], k=c["k"], threshold=c["threshold"], fraction=c["fraction"],
-                                    batches=c["batches"], seed=c["seed"])
-            dist.broadcast(mask.bits, src=0, group=pg)
+        def empty(c):
+            bits = torch.zeros((eng.ps.total + 31) // 32, dtype=torch.int32, device=device)
+            return SaliencyMask(eng, bits, c["count"], **{k: c[k] for k in ("k", "threshold", "fraction", "batches", "seed")})
+
+        def same_count(mask, c):
             mine = count_bits(mask.bits)
             if mine != c["set_bits"]:
                 raise RuntimeError(f"deletion.saliency: rank {rank} holds {mine} set bits after the broadcast, rank 0 holds {c['set_bits']}")
-        if rank == 0:
-            mask.save(str(self.cfg.output_dir))
-        return mask
+
+        return _built_on_rank0("deletion.saliency: rank 0 could not build the mask", build,
+                               lambda mask: dict(mask.config(), set_bits=count_bits(mask.bits)), empty, lambda mask: mask.bits,
+                               str(self.cfg.output_dir), rank, world, pg, check=same_count)
 
     # -- deletion.lora: null | {rank, alpha, targets, seed} (OPT-IN; siss_amd/lora.py) ------------------------------------------------
     def lora_config(self):
@@ -795,13 +788,7 @@ class _DeleteBase(Task):
         def record(handle, meta):
             st = handle.get()
             st["global_step"], st["lr"], st["elapsed_s"] = meta          # (elapsed: stamped when the step was queued)
-            st["trainable_params"], st["trainable_tensors"] = stepper.trainable_counts()
-            if lora is not None:
-                st["lora_rank"], st["lora_alpha"], st["lora_params"], st["lora_tensors"] = lora.rank, lora.alpha, lora.params, lora.tensors
-            if saliency is not None:
-                st.update(saliency.log_fields())
-            if ewc is not None:
-                st.update(ewc.log_fields())            # (ewc_penalty / ewc_grad_norm: the step's own block, SISSStepper.stats_async)
+            st.update(stepper.log_fields())         # (the parameters the optimizer updates and the active variant's own fields)
             return st
 
         def say(st, meta):

@@ -8,7 +8,13 @@
   on top of given g_x, g_a, the recombination of oracle/step.py, clip_grad_norm_ and torch.optim.AdamW -- modes 0, 1, 2 and a single-set
   case; the f32 restatement of the fold against its f64 values;
 * FlatAdamW.launch_sharded(ewc=...), launch(ranges=..., ewc=...) and launch(mask=..., ewc=...) refuse before any launch (an optimizer
-  over CPU tensors with a recording launcher in place of the library's).
+  over CPU tensors with a recording launcher in place of the library's); the same recorder pins the entry points and every argument
+  of launch's four paths (plain, ranges, mask, ewc), with and without want_grad;
+* the variants' one table (siss_amd/variants.py): which (overlap, exchange) pairs set_overlap takes per variant, written out as a
+  literal grid and checked on a SISSStepper built without its constructor (the constructor wants a device: what it resolves is set by
+  hand; saliency and ewc go through set_saliency / set_ewc); what _fit_exchange switches off and says; exclusive()'s message;
+* tasks._built_on_rank0 as rank 0 and as rank 1 of 2 over a recording stand-in for torch.distributed: the agreement comes before the
+  tensor broadcast, an error string raises on every rank before any tensor moves.
 """
 import json
 import math
@@ -302,6 +308,239 @@ def test_flat_adamw_refuses_the_anchor_with_ranges_mask_or_shards(monkeypatch):
     assert [s[0] for s in seen] == ["siss_grad_norms_scale_ewc", "siss_recombine_clip_adamw"]
     a = seen[0][1]
     assert a[2] is opt.p and a[3] is anchor.pstar and a[4] is anchor.fisher and a[5] == n and a[6] == 1.0 and a[13] is opt.ewc_partials
+
+
+LAUNCH_PATHS = {"plain": ("siss_grad_norms_scale", "siss_recombine_clip_adamw"),
+                "ranges": ("siss_grad_norms_scale_ranges", "siss_recombine_clip_adamw_ranges"),
+                "mask": ("siss_grad_norms_scale_masked", "siss_recombine_clip_adamw_masked"),
+                "ewc": ("siss_grad_norms_scale_ewc", "siss_recombine_clip_adamw")}
+
+
+@pytest.mark.parametrize("want_grad", [False, True])
+@pytest.mark.parametrize("path", list(LAUNCH_PATHS))
+def test_flat_adamw_launch_sequence(monkeypatch, path, want_grad):
+    """The two entry points of each of launch's four paths and every argument of both, by the header's parameter names; last_grad is
+    allocated once, zero-filled where the path writes only part of it, and passed as g_out (None without want_grad)."""
+    from siss_amd import lib
+    from siss_amd.ewc import FisherAnchor
+    from siss_amd.optim import MODE_NORM_FIX
+    n = 64
+    opt = cpu_optimizer(n)
+    opt.shadow = torch.zeros(n, dtype=torch.bfloat16)
+    grads = torch.zeros(2, n)
+    tab, nr, granules = torch.tensor([4, 0, 8]), 1, 8                # one stretch: granules 4..11 of the 16
+    words = torch.zeros(2, dtype=torch.int32)
+    anchor = FisherAnchor.uniform(fake_engine((n,)), 2.0)
+    kw = {"plain": {}, "ranges": dict(ranges=(tab, nr, granules)), "mask": dict(mask=words), "ewc": dict(ewc=anchor)}[path]
+    seen = []
+    monkeypatch.setattr(lib, "call", lambda name, *a, **k: seen.append((name, a)) or 0)
+    monkeypatch.setattr(lib, "query", lambda name, *a: 4096)
+    monkeypatch.setattr(torch, "empty_like", lambda t: torch.full_like(t, float("nan")))     # (what `empty` leaves is told from zeros)
+    opt.launch(grads, scaling_norm=5.0, want_grad=want_grad, **kw)
+    first = opt.last_grad
+    opt.launch(grads, scaling_norm=5.0, want_grad=want_grad, **kw)
+    assert [s[0] for s in seen] == 2 * list(LAUNCH_PATHS[path])
+    if want_grad:
+        assert first is not None and opt.last_grad is first, "last_grad is allocated once"
+        assert first.shape == opt.p.shape and first.dtype == torch.float32
+        partial = path in ("ranges", "mask")
+        assert bool((first == 0).all()) if partial else bool(first.isnan().all()), "zero-filled for ranges / mask, empty otherwise"
+    else:
+        assert opt.last_grad is None
+    same = lambda a, b: a.data_ptr() == b.data_ptr() and a.shape == b.shape
+    for name, args in seen:
+        assert len(args) == len(lib.PARAMS[name]) - 1, (name, len(args), lib.PARAMS[name])          # (the stream is lib.call's)
+        a = dict(zip(lib.PARAMS[name], args))
+        assert same(a.pop("gx"), grads[0]) and same(a.pop("ga"), grads[1]) and a.pop("n") == n and a.pop("scalars") is opt.scalars
+        assert (a.pop("beta1"), a.pop("beta2")) == opt.betas
+        if path == "ranges":
+            assert a.pop("tab") is tab and (a.pop("nranges"), a.pop("total_granules")) == (nr, granules)
+        if path == "mask":
+            assert a.pop("bits") is words
+        if name.startswith("siss_grad_norms_scale"):
+            assert (a.pop("mode"), a.pop("knob"), a.pop("max_norm")) == (MODE_NORM_FIX, 5.0, 1.0) and a.pop("partials") is opt.partials
+            if path == "ewc":
+                assert a.pop("p") is opt.p and a.pop("pstar") is anchor.pstar and a.pop("F") is anchor.fisher
+                assert a.pop("strength") == 2.0 and a.pop("ewc_partials") is opt.ewc_partials
+        else:
+            assert a.pop("p") is opt.p and a.pop("m") is opt.m and a.pop("v") is opt.v and a.pop("shadow") is opt.shadow
+            assert a.pop("g_out") is (first if want_grad else None)
+            assert (a.pop("lr"), a.pop("eps"), a.pop("wd")) == (opt.lr, opt.eps, opt.wd)
+        assert a == {}, (name, sorted(a))
+    # mode and knob of the other two recombinations
+    del seen[:]
+    opt.launch(grads, scaling_norm=5.0, inf_guard=True, **kw)
+    opt.launch(grads, eta=1e-2, **kw)
+    modes = [(dict(zip(lib.PARAMS[nm], a))["mode"], dict(zip(lib.PARAMS[nm], a))["knob"]) for nm, a in seen[::2]]
+    assert modes == [(2, 5.0), (1, 1e-2)]
+
+
+# ================================================================ which exchange each variant may use
+def host_stepper(variant, monkeypatch):
+    """A SISSStepper without its constructor (which wants a device, like FlatAdamW's): what the constructor resolves is set by hand for
+    full / trainable / lora; saliency and ewc are reached the way a task reaches them, through set_saliency / set_ewc on a full stepper."""
+    from siss_amd import lib
+    from siss_amd.ewc import FisherAnchor
+    from siss_amd.saliency import SaliencyMask
+    from siss_amd.step import SISSStepper
+    monkeypatch.setattr(lib, "query", lambda name, *a: 4096)
+    eng = fake_engine((64,))
+    eng.on_early_grads_final = None
+    st = SISSStepper.__new__(SISSStepper)
+    st.e, st.opt, st.pg, st.world, st.dp_on = eng, cpu_optimizer(64), object(), 1, True        # (dp.FORCE_COLLECTIVES on a stub group)
+    st.lora = st.subset = st.saliency = st.ewc = None
+    st.variant, st._launch_kw, st.overlap, st.exchange = "full", {}, False, "allreduce"
+    st._ranges = st._mask = None
+    if variant == "lora":
+        st.lora = st.subset = types.SimpleNamespace(params=1, tensors=2)
+    elif variant == "trainable":
+        st.subset = types.SimpleNamespace(params=1, tensors=1)
+    if variant in ("lora", "trainable"):
+        st.variant = variant
+    elif variant == "saliency":
+        st.set_saliency(SaliencyMask.ones(eng))
+    elif variant == "ewc":
+        st.set_ewc(FisherAnchor.uniform(eng, 1.0))
+    return st
+
+
+# (overlap, exchange) -> accepted, per variant: written out, not computed from the table under test
+ACCEPTS = {
+    "full": {(True, "allreduce"): True, (True, "sharded"): True, (False, "allreduce"): True, (False, "sharded"): True},
+    "trainable": {(True, "allreduce"): False, (True, "sharded"): False, (False, "allreduce"): True, (False, "sharded"): False},
+    "lora": {(True, "allreduce"): False, (True, "sharded"): False, (False, "allreduce"): True, (False, "sharded"): False},
+    "saliency": {(True, "allreduce"): True, (True, "sharded"): False, (False, "allreduce"): True, (False, "sharded"): False},
+    "ewc": {(True, "allreduce"): True, (True, "sharded"): False, (False, "allreduce"): True, (False, "sharded"): False},
+}
+
+
+@pytest.mark.parametrize("variant", list(ACCEPTS))
+def test_set_overlap_accepts_and_refuses_by_variant(monkeypatch, variant):
+    st = host_stepper(variant, monkeypatch)
+    for (on, exchange), ok in ACCEPTS[variant].items():
+        if ok:
+            st.set_overlap(on, exchange)
+            assert (st.overlap, st.exchange) == (on, exchange)
+            assert (st.e.on_early_grads_final is not None) == on
+        else:
+            with pytest.raises(NotImplementedError, match="allreduce"):
+                st.set_overlap(on, exchange)
+    # without collectives nothing is refused
+    st.dp_on = False
+    for on, exchange in ACCEPTS[variant]:
+        st.set_overlap(on, exchange)
+
+
+@pytest.mark.parametrize("variant,fitted,lines", [("full", (True, "sharded"), 0), ("trainable", (False, "allreduce"), 2),
+                                                  ("lora", (False, "allreduce"), 2), ("saliency", (True, "allreduce"), 1),
+                                                  ("ewc", (True, "allreduce"), 1)])
+def test_the_exchange_asked_for_is_fitted_to_the_variant_and_said(monkeypatch, capsys, variant, fitted, lines):
+    st = host_stepper(variant, monkeypatch)
+    capsys.readouterr()
+    st.exchange = "sharded"
+    st._fit_exchange(True)
+    assert (st.overlap, st.exchange) == fitted
+    said = [l for l in capsys.readouterr().out.splitlines() if l.startswith("[siss_amd] ")]
+    assert len(said) == lines, said
+    assert all("using the all-reduce" in l or "is off" in l for l in said)
+    if variant in ("trainable", "lora"):            # one exchange mode: the autotune has nothing to time and runs no step
+        st.e.ps.split = 0
+        assert st.autotune_overlap(lambda: pytest.fail("a step was run")) is False
+
+
+def test_log_fields_are_the_counts_and_the_active_variants_own(monkeypatch):
+    counts = dict(trainable_params=64, trainable_tensors=1)
+    assert host_stepper("full", monkeypatch).log_fields() == counts
+    assert host_stepper("trainable", monkeypatch).log_fields() == dict(trainable_params=1, trainable_tensors=1)
+    assert host_stepper("ewc", monkeypatch).log_fields() == dict(counts, ewc_strength=1.0)
+    assert host_stepper("saliency", monkeypatch).log_fields() == dict(counts, saliency_params=64, saliency_fraction=1.0,
+                                                                     saliency_threshold=None)
+
+
+def test_exclusive_names_both_keys_and_the_reason():
+    from siss_amd.variants import SHARD, VARIANTS, exclusive
+    exclusive("here", {"ewc=": None, "lora=": 1, "trainable=": None})
+    exclusive("here", {})
+    with pytest.raises(ValueError, match=r"here: ewc= and lora= do not combine") as e:
+        exclusive("here", {"ewc=": 0, "saliency=": None, "lora=": 1, "trainable=": 2})
+    assert VARIANTS["ewc"].alone in str(e.value)
+    with pytest.raises(NotImplementedError, match="mask=") as e:
+        exclusive("there", {"ranges=": None, "mask=": 1, SHARD: True}, NotImplementedError)
+    assert VARIANTS["saliency"].sharded in str(e.value) and SHARD in str(e.value)
+    with pytest.raises(ValueError, match="deletion.lora.*deletion.trainable") as e:
+        exclusive("config", {"deletion.lora": {}, "deletion.trainable": ["attn"]})
+    assert VARIANTS["lora"].alone in str(e.value)
+
+
+# ================================================================ the rank-0 build protocol of the tasks
+class Built:
+    def __init__(self, tensor, note):
+        self.tensor, self.note, self.saved = tensor, note, None
+
+    def save(self, directory):
+        self.saved = directory
+
+
+def rank0_protocol(monkeypatch, rank, sent, build, check=None):
+    """_built_on_rank0 as `rank` of 2 over a recording stand-in for torch.distributed; sent: what rank 0's object list holds."""
+    import torch.distributed as dist
+    from siss_amd.tasks import _built_on_rank0
+    calls = []
+
+    def broadcast_object_list(word, src, group):
+        calls.append(("broadcast_object_list", None if rank != 0 else word[0]))
+        if rank != 0:
+            word[0] = sent
+
+    monkeypatch.setattr(dist, "broadcast_object_list", broadcast_object_list)
+    monkeypatch.setattr(dist, "broadcast", lambda t, src, group: calls.append(("broadcast", t)))
+    try:
+        obj = _built_on_rank0("the.key: rank 0 could not build it", build, lambda o: dict(note=o.note),
+                              lambda c: Built(torch.zeros(4), c["note"]), lambda o: o.tensor, "/out", rank, 2, "group",
+                              check=check)
+    except Exception as e:
+        return e, calls
+    return obj, calls
+
+
+def test_rank0_builds_the_others_agree_first_then_receive(monkeypatch):
+    mine = Built(torch.ones(4), "built here")
+    checked = []
+    # rank 0: builds, sends the description, then the tensor, checks, saves
+    obj, calls = rank0_protocol(monkeypatch, 0, None, lambda: mine, check=lambda o, c: checked.append((o, c)))
+    assert obj is mine and [c[0] for c in calls] == ["broadcast_object_list", "broadcast"]
+    assert calls[0][1] == dict(note="built here") and calls[1][1] is mine.tensor
+    assert checked == [(mine, dict(note="built here"))] and mine.saved == "/out"
+    # rank 1: never builds; an empty object from the description receives the tensor; it does not save
+    never = lambda: pytest.fail("a rank other than 0 built the object")
+    obj, calls = rank0_protocol(monkeypatch, 1, dict(note="from rank 0"), never, check=lambda o, c: checked.append((o, c)))
+    assert [c[0] for c in calls] == ["broadcast_object_list", "broadcast"]
+    assert obj.note == "from rank 0" and calls[1][1] is obj.tensor and obj.saved is None and checked[-1] == (obj, dict(note="from rank 0"))
+    # an error string: every rank raises BEFORE any tensor broadcast -- rank 0 its own exception, the others one that quotes it
+    err, calls = rank0_protocol(monkeypatch, 1, "ValueError: F is zero", never)
+    assert isinstance(err, RuntimeError) and "the.key: rank 0 could not build it (ValueError: F is zero)" in str(err)
+    assert [c[0] for c in calls] == ["broadcast_object_list"]
+    boom = ValueError("F is zero")
+
+    def fails():
+        raise boom
+    err, calls = rank0_protocol(monkeypatch, 0, None, fails)
+    assert err is boom and calls == [("broadcast_object_list", "ValueError: F is zero")]
+    # a failing check raises after the broadcast, before the save
+    def bad(o, c):
+        raise RuntimeError("set bits differ")
+    other = Built(torch.ones(4), "x")
+    err, calls = rank0_protocol(monkeypatch, 0, None, lambda: other, check=bad)
+    assert "set bits differ" in str(err) and len(calls) == 2 and other.saved is None
+
+
+def test_one_rank_builds_and_saves_without_a_collective(monkeypatch):
+    import torch.distributed as dist
+    from siss_amd.tasks import _built_on_rank0
+    monkeypatch.setattr(dist, "broadcast_object_list", lambda *a, **k: pytest.fail("a collective on one rank"))
+    monkeypatch.setattr(dist, "broadcast", lambda *a, **k: pytest.fail("a collective on one rank"))
+    mine = Built(torch.ones(4), "alone")
+    assert _built_on_rank0("x", lambda: mine, None, None, None, "/out", 0, 1, None) is mine and mine.saved == "/out"
 
 
 def test_the_entry_points_are_declared():
