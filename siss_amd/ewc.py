@@ -13,8 +13,8 @@ gradient of the batch-mean loss (batch_size 1 gives the per-sample Fisher).  It 
 The files: `fisher.safetensors` (key `fisher`, the flat buffer's layout) beside `fisher.json` (strength, batches, batch_size, seed,
 normalize, mean / max before the normalisation, the zero count, whether it was computed or loaded, and the fingerprint of the buffer).
 """
-from .variants import (backward_batch, exclusive, files_present, fingerprint, load_tensor, need_bool, need_fields, need_int,
-                       need_opt_str, quiet_backward, real_mask, save_tensor)
+from .variants import (exclusive, files_present, fingerprint, fisher_of_batches, load_tensor, need_bool, need_fields, need_int,
+                       need_opt_str, real_mask, save_tensor)
 
 KEY = "deletion.ewc"
 FISHER_FILE, CONFIG_FILE = "fisher.safetensors", "fisher.json"
@@ -128,20 +128,13 @@ class FisherAnchor:
         sample_noise), then F += g^2 / n_batches (siss_fisher_accumulate on gradient set 0).  forget_gradient's guarantees hold: no
         optimizer launch, the overlap hook off, no collective pending; on return the gradient buffers are zero and parameters, moments,
         step counters and sparse-fill records are what they were.  normalize: F is divided by its f64 mean over the real parameters."""
-        import torch
-        from . import lib
         require_kernels()
         if n_batches < 1:
             raise ValueError(f"FisherAnchor.from_batches: n_batches={n_batches!r}")
         e = stepper.e
         ps = e.ps
-        F = torch.zeros_like(ps.flat)
-        with quiet_backward(stepper, "FisherAnchor.from_batches"):
-            for _ in range(n_batches):
-                # every micro-batch is a gradient of its own: zeroed buffers, one-split weight gradients overwrite their tiles
-                backward_batch(stepper, next(batches_iter), 1, first=True, prepare=prepare, sample_noise=sample_noise,
-                               conditioning=conditioning, timestep_low=timestep_low, generator=generator)
-                lib.call("siss_fisher_accumulate", ps.grads[0], F, ps.total, 1.0 / n_batches)
+        F = fisher_of_batches(stepper, batches_iter, n_batches, "FisherAnchor.from_batches", prepare=prepare, sample_noise=sample_noise,
+                              conditioning=conditioning, timestep_low=timestep_low, generator=generator)
         real = real_mask(ps.specs, ps.total, F.device)
         mean, mx, zeros = normalize_fisher(F, real) if normalize else fisher_stats(F, real)
         return cls(e, F, ps.flat.detach().clone(), strength, batches=int(n_batches), batch_size=batch_size, seed=seed,

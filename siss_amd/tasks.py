@@ -293,6 +293,13 @@ class _DeleteBase(Task):
         if cfg.get("mixed_precision") not in (None, "null", "no", "bf16"):
             raise NotImplementedError(f"mixed_precision={cfg.get('mixed_precision')!r}: only null / bf16 (no loss scaler)")
         _pipeline_sampler(cfg)                                   # pipeline.sampler: a bad name / option is refused before the first step
+        # deletion.ssd: a malformed mapping, an unknown field, both or neither of alpha / fraction, a value out of range, a targets entry
+        # that matches no parameter of the configured UNet and the key together with deletion.lora / deletion.trainable (said first: what
+        # those two select does not matter then) are settled here
+        sc = self.ssd_config()
+        if sc is not None:
+            from .ssd import select_targets as ssd_targets
+            ssd_targets(self.unet_param_names(), sc.targets)
         # deletion.trainable: a malformed entry, an entry that matches no parameter of the configured UNet and a selection of every
         # parameter (said, then the full update) are settled here, from the parameter names the configuration implies
         from .trainable import select
@@ -311,6 +318,82 @@ class _DeleteBase(Task):
         # deletion.ewc: a malformed mapping, an unknown field, a missing or non-positive strength, batches / batch_size < 1 and the key
         # together with deletion.trainable / deletion.lora / deletion.saliency are settled here too
         self.ewc_config()
+
+    # -- deletion.ssd: null | {alpha, fraction, lambda, keep_batches, forget_batches, batch_size, seed, targets, path} (OPT-IN; siss_amd/ssd.py)
+    def ssd_config(self):
+        """The parsed deletion.ssd (siss_amd.ssd.SSDConfig), or None (absent / null: no dampening, today's run)."""
+        from .ssd import parse_ssd
+        d = self.cfg.get("deletion") or {}
+        return parse_ssd(d.get("ssd"), trainable=d.get("trainable"), lora=d.get("lora"))
+
+    def ssd_forget_batches(self, ds_del, bs):
+        """saliency_batches at the micro-batch size of the importances."""
+        src = getattr(self, "forget_cache", None) or self.forget_store
+        if src is not None:
+            return index_batches(self.deletion_sampler(ds_del, bs), bs, src)
+        return batches(ds_del, self.deletion_sampler(ds_del, bs), bs)
+
+    def ssd_dampen(self, stepper, ds_all, ds_del, B, cond, device, rank, world, pg):
+        """Selective Synaptic Dampening of the run (None without the key), once, at the weights the run loaded, before the mask, the
+        anchor and the step-0 metrics: the importances loaded from `path` when both files are there, else F_keep on `keep_batches`
+        micro-batches of `batch_size` from a keep iterator of its own and then F_forget on `forget_batches` from a forget iterator
+        of its own (the task's prepare_batch, sample_noise and conditioning, timesteps uniform in [timestep_low, T), ONE generator
+        seeded with `seed` -- the loop's iterators and generator are not advanced); then the selection, the dampening and the
+        report.  More than one rank: rank 0 alone builds or loads the importances, the ranks agree on success, the ratio is broadcast,
+        every rank selects and dampens and checks its selected count against rank 0's.  Rank 0 writes the two files into output_dir.
+        Returns the fields every train-log line carries."""
+        sc = self.ssd_config()
+        if sc is None:
+            return None
+        from . import ssd
+        eng = stepper.e
+        bs = int(sc.batch_size)
+        out = str(self.cfg.output_dir)
+
+        def build():
+            if sc.path is not None and ssd.Importances.present(sc.path):
+                imp = ssd.Importances.load(sc.path, eng)
+                print(f"[siss_amd] deletion.ssd: importances loaded from {sc.path}")
+                return imp
+            if sc.path is not None:
+                print(f"[siss_amd] deletion.ssd.path {sc.path!r} holds no importance files: computing the importances")
+            gen = torch.Generator(device=device).manual_seed(sc.seed)
+            it_keep = self.ewc_batches(ds_all, bs, device)
+            try:
+                cond_b = cond if bs == B else self.conditioning(bs, device)
+                imp = ssd.Importances.from_batches(stepper, it_keep, self.ssd_forget_batches(ds_del, bs), sc.keep_batches,
+                                                   sc.forget_batches, prepare=self.prepare_batch, sample_noise=self.sample_noise,
+                                                   conditioning=cond_b, timestep_low=self.timestep_low, generator=gen, batch_size=bs,
+                                                   seed=sc.seed)
+            finally:
+                it_keep.close()
+            print(f"[siss_amd] deletion.ssd: empirical Fishers of {sc.keep_batches} keep and {sc.forget_batches} forget micro-batches "
+                  f"of {bs}")
+            return imp
+
+        def empty(c):
+            z = torch.zeros_like(eng.ps.flat)
+            return ssd.Importances(eng, z, z, ratio=torch.zeros_like(z),
+                                   **{k: c[k] for k in ("keep_batches", "forget_batches", "batch_size", "seed", "source")})
+
+        imp = _built_on_rank0("deletion.ssd: rank 0 could not build the importances", build, ssd.Importances.config, empty,
+                              lambda imp: imp.ratio, out, rank, world, pg)
+        names = ssd.select_targets(list(eng.ps.specs), sc.targets)
+        thr, strict, k, count_gt, count_ge = ssd.select(imp, alpha=sc.alpha, fraction=sc.fraction, targets=names)
+        stats = ssd.dampen(eng, imp, thr, strict, sc.lam, apply=True)
+        if world > 1:
+            import torch.distributed as dist
+            word = [stats["selected"] if rank == 0 else None]
+            dist.broadcast_object_list(word, src=0, group=pg)
+            if word[0] != stats["selected"]:
+                raise RuntimeError(f"deletion.ssd: rank {rank} dampened {stats['selected']} weights, rank 0 {word[0]}")
+        if rank == 0:
+            imp.save_report(out, dict(config=sc.as_dict(), threshold=thr, threshold_bits=ssd.float_bits(thr), strict=bool(strict), k=k,
+                                      count_gt=count_gt, count_ge=count_ge, stats=stats, per_tensor=ssd.per_tensor(imp, thr, strict)))
+            print(f"[siss_amd] deletion.ssd: ratio {'>' if strict else '>='} {thr:.6g} selects {stats['selected']} of {imp.params} "
+                  f"parameters ({stats['dampened']} dampened, {stats['zeroed']} to zero, mean beta {stats['mean_beta']}), relative "
+                  f"change of the weights {stats['relative_change']:.6g}")
+        return dict(ssd_selected=stats["selected"], ssd_threshold=thr, ssd_lambda=sc.lam)
 
     # -- deletion.ewc: null | {strength, batches, batch_size, seed, normalize, path} (OPT-IN; siss_amd/ewc.py) -------------------------
     def ewc_config(self):
@@ -776,6 +859,7 @@ class _DeleteBase(Task):
         n_steps = int(cfg.training_steps) * max(1, len(d.get("img_name") or [1]))
         cond = self.conditioning(B, device)
         os.makedirs(cfg.output_dir, exist_ok=True)
+        ssd_fields = self.ssd_dampen(stepper, ds_all, ds_del, B, cond, device, rank, world, pg)
         saliency = self.saliency_mask(stepper, ds_del, B, cond, device, rank, world, pg)
         if saliency is not None:
             stepper.set_saliency(saliency)
@@ -789,6 +873,8 @@ class _DeleteBase(Task):
             st = handle.get()
             st["global_step"], st["lr"], st["elapsed_s"] = meta          # (elapsed: stamped when the step was queued)
             st.update(stepper.log_fields())         # (the parameters the optimizer updates and the active variant's own fields)
+            if ssd_fields is not None:
+                st.update(ssd_fields)
             return st
 
         def say(st, meta):
@@ -1592,6 +1678,9 @@ class TrainUnconditional(Task):
         if (cfg.get("deletion") or {}).get("ewc") is not None:
             raise NotImplementedError("deletion.ewc: the Fisher anchor belongs to the unlearning tasks (delete_celeb / delete_tshirt / "
                                       "delete_sd); the pre-training task has no pretrained weights to stay near")
+        if (cfg.get("deletion") or {}).get("ssd") is not None:
+            raise NotImplementedError("deletion.ssd: Selective Synaptic Dampening belongs to the unlearning tasks (delete_celeb / "
+                                      "delete_tshirt / delete_sd); the pre-training task has no forget set to dampen for")
 
     def dataset(self, shape):
         cfg = self.cfg

@@ -1,8 +1,8 @@
 """The opt-in variants of the unlearning update -- `deletion.trainable`, `deletion.lora`, `deletion.saliency`, `deletion.ewc` -- and
 what they share: ONE table of their static facts (which gradient exchanges a variant may use and why not the others, why it runs
-alone), the one exclusivity check every entry point calls, the field checks of the parsed keys, and the flat-buffer helpers of the
-two variants that are built from backward passes at the pretrained weights (fingerprint, the real-parameter mask, the tensor file
-beside its JSON, quiet_backward / backward_batch).  At most one variant is active in a run; `full` is the reference's protocol.
+alone), the one exclusivity check every entry point calls, the field checks of the parsed keys, and the flat-buffer helpers of what
+is built from backward passes at the pretrained weights -- the saliency mask, the Fisher anchor and the importances of siss_amd/ssd.py
+(fingerprint, the real-parameter mask, the tensor file beside its JSON, quiet_backward / backward_batch / fisher_of_batches).  At most one variant is active in a run; `full` is the reference's protocol.
 Host code only until a tensor is touched.
 """
 import json
@@ -115,18 +115,28 @@ def files_present(directory, *files):
     return bool(directory) and all(os.path.isfile(os.path.join(str(directory), f)) for f in files)
 
 
-def save_tensor(directory, tensor_file, key, tensor, config_file, config):
-    """`tensor` under `key` in a safetensors file beside its JSON config (safetensors and JSON only)."""
+def save_tensors(directory, tensor_file, tensors, config_file, config):
+    """`tensors` ({key: tensor}) in one safetensors file beside its JSON config (safetensors and JSON only)."""
     from safetensors.torch import save_file
     os.makedirs(directory, exist_ok=True)
-    save_file({key: tensor.cpu().contiguous()}, os.path.join(directory, tensor_file))
+    save_file({k: t.cpu().contiguous() for k, t in tensors.items()}, os.path.join(directory, tensor_file))
+    save_config(directory, config_file, config)
+
+
+def save_config(directory, config_file, config):
+    os.makedirs(directory, exist_ok=True)
     with open(os.path.join(directory, config_file), "w") as f:
         json.dump(config, f, indent=1)
 
 
-def load_tensor(directory, tensor_file, key, config_file, engine, what):
-    """(tensor, config) saved by save_tensor, for `engine`: refused, naming the file and the key, when it was taken over another buffer
-    (ps.total, the tensor count or the real parameter count differ)."""
+def save_tensor(directory, tensor_file, key, tensor, config_file, config):
+    """`tensor` under `key` in a safetensors file beside its JSON config."""
+    save_tensors(directory, tensor_file, {key: tensor}, config_file, config)
+
+
+def load_tensors(directory, tensor_file, config_file, engine, what):
+    """({key: tensor}, config) saved by save_tensors, for `engine`: refused, naming the file and the key, when it was taken over another
+    buffer (ps.total, the tensor count or the real parameter count differ)."""
     from safetensors.torch import load_file
     path = os.path.join(directory, config_file)
     with open(path) as f:
@@ -136,7 +146,13 @@ def load_tensor(directory, tensor_file, key, config_file, engine, what):
         if int(c.get(k, -1)) != fp[k]:
             raise ValueError(f"{path}: {k} = {c.get(k)!r}, this UNet has {fp[k]} -- the {what} was computed for another architecture "
                              "or parameter layout")
-    return load_file(os.path.join(directory, tensor_file))[key], c
+    return load_file(os.path.join(directory, tensor_file)), c
+
+
+def load_tensor(directory, tensor_file, key, config_file, engine, what):
+    """(tensor, config): load_tensors for a file of one key."""
+    tensors, c = load_tensors(directory, tensor_file, config_file, engine, what)
+    return tensors[key], c
 
 
 # ---------------------------------------------------------------------------------------------------------------- backward passes outside a step
@@ -194,3 +210,20 @@ def backward_batch(stepper, batch, scale_batches, *, first, prepare=None, sample
     pred = e.forward(m.x_mix, t, **dict(conditioning or {}))
     cot, _, _ = mse_bwd_seed(pred, noise, 1.0 / (B * scale_batches))
     e.backward(cot, nsets=1)
+
+
+def fisher_of_batches(stepper, batches_iter, n_batches, what, **draw):
+    """The empirical Fisher of the eps-MSE at the stepper's current weights at MICRO-BATCH granularity, [ps.total] f32 on the engine's
+    device: zero, then per micro-batch of batches_iter one backward_batch(first=True) at scale 1 / B (`draw`: its prepare /
+    sample_noise / conditioning / timestep_low / generator) and F += g^2 / n_batches (siss_fisher_accumulate on gradient set 0).  The
+    one loop under the Fisher anchor (siss_amd/ewc.py) and the two importances of siss_amd/ssd.py; quiet_backward's guarantees hold."""
+    import torch
+    from . import lib
+    ps = stepper.e.ps
+    F = torch.zeros_like(ps.flat)
+    with quiet_backward(stepper, what):
+        for _ in range(n_batches):
+            # every micro-batch is a gradient of its own: zeroed buffers, one-split weight gradients overwrite their tiles
+            backward_batch(stepper, next(batches_iter), 1, first=True, **draw)
+            lib.call("siss_fisher_accumulate", ps.grads[0], F, ps.total, 1.0 / n_batches)
+    return F
