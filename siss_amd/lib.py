@@ -74,7 +74,7 @@ F32_SAME = {"siss_zero_ranges", "siss_upsample_phase_wgrad_fold", "siss_timestep
             "siss_grad_norms_scale_ranges", "siss_recombine_clip_adamw_ranges",
             "siss_grad_norm_single", "siss_clip_adamw_ema", "siss_ema_advance", "siss_ema_step", "siss_swap_f32",
             "siss_ctx_dgrad", "siss_ctx_reduce", "siss_noise_norm_cot", "siss_prompt_embed_update", "siss_latent_inject", "siss_latent_sample", "siss_image_gather",
-            "siss_lora_project", "siss_lora_merge",
+            "siss_lora_project", "siss_lora_merge", "siss_lora_project_conv", "siss_lora_merge_conv",
             "siss_absf_select", "siss_saliency_mask", "siss_grad_norms_scale_masked", "siss_recombine_clip_adamw_masked",
             "siss_fisher_accumulate", "siss_grad_norms_scale_ewc",
             "siss_ssd_ratio", "siss_ssd_dampen",

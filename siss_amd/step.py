@@ -73,7 +73,7 @@ class SISSStepper:
         if lora is not None:
             if lora.engine is not engine:
                 raise ValueError("SISSStepper(lora=...): the LoRAState was built over another engine")
-            trainable = list(lora.names)
+            trainable = list(lora.names) + list(lora.conv_names)     # (exactly the targets' weight-gradient products run)
         if hasattr(engine, "check_trainable"):
             engine.check_trainable()                # a site without a backward kernel is refused here, not inside the first step
         dev = engine.device

@@ -306,12 +306,12 @@ class _DeleteBase(Task):
         pats = self.trainable_patterns()
         if pats is not None:
             select(self.unet_param_names(), pats)
-        # deletion.lora: a malformed mapping, a rank outside 1..64, a target that matches nothing or is no linear / 1x1 weight, and the key
-        # together with deletion.trainable are settled here too
+        # deletion.lora: a malformed mapping, a rank outside 1..64, a target that matches nothing or is no linear / 1x1 weight, a conv
+        # target that is no 3x3 convolution's weight, and the key together with deletion.trainable are settled here too
         lcfg = self.lora_config()
         if lcfg is not None:
-            from .lora import select_targets
-            select_targets(self.unet_param_specs(), lcfg.patterns)
+            from .lora import resolve_targets
+            resolve_targets(self.unet_param_specs(), lcfg)
         # deletion.saliency: a malformed mapping, an unknown field, a fraction outside (0, 1), batches < 1 and the key together with
         # deletion.trainable / deletion.lora are settled here too
         self.saliency_config()
@@ -508,7 +508,7 @@ class _DeleteBase(Task):
                                lambda mask: dict(mask.config(), set_bits=count_bits(mask.bits)), empty, lambda mask: mask.bits,
                                str(self.cfg.output_dir), rank, world, pg, check=same_count)
 
-    # -- deletion.lora: null | {rank, alpha, targets, seed} (OPT-IN; siss_amd/lora.py) ------------------------------------------------
+    # -- deletion.lora: null | {rank, alpha, targets, conv_targets, seed} (OPT-IN; siss_amd/lora.py) ------------------------------------------------
     def lora_config(self):
         """The parsed deletion.lora (siss_amd.lora.LoRAConfig), or None (absent / null: no adapter, today's run)."""
         from .lora import parse_lora
@@ -520,8 +520,9 @@ class _DeleteBase(Task):
         lcfg = self.lora_config()
         if lcfg is None:
             return None
-        from .lora import LoRAState, select_targets
-        st = LoRAState(unet.engine, select_targets(unet.engine.ps.specs, lcfg.patterns), lcfg.rank, lcfg.alpha, lcfg.seed)
+        from .lora import LoRAState, resolve_targets
+        names, conv_names = resolve_targets(unet.engine.ps.specs, lcfg)
+        st = LoRAState(unet.engine, names, lcfg.rank, lcfg.alpha, lcfg.seed, conv_names=conv_names)
         st.base = str(self.cfg.get("checkpoint_path") or self.cfg.get("pretrained_model_name_or_path") or "") or None
         return st
 

@@ -20,6 +20,15 @@ they move over the 8 TB/s of the data sheet (project reads dW of both sets TWICE
 dA: 16 B per target float; merge reads W0 and writes the master and its bf16 shadow: 10 B), and the bytes of optimizer state (m + v).
 The shader clock is read after each leg's timed work.  One condition is checked and recorded, not enforced: the three LoRA launches
 together take less time than the full-buffer FlatAdamW.launch they replace.
+
+    python tools/bench_lora.py --config celebahq256 --batch 16 --conv-targets [--out profiles/lora_conv_celebahq256.json]
+    python tools/bench_lora.py --config sd15 --batch 4 --conv-targets
+
+--conv-targets puts the adapters on the 3x3 convolutions as well (deletion.lora.conv_targets; peft's Conv2d adapter): every resnet
+conv1 / conv2 -- on the pixel UNets INSTEAD of the attention projections (nearly all of their parameters are convolutions), on SD
+BESIDE them.  The launches timed alone are then the pair of each kind (siss_lora_project + siss_lora_project_conv, the two merges) as
+LoRAState.project() / merge() issue them; a conv target's floats move like a linear target's (dW of both sets read twice, W0 read,
+master and shadow written).  No condition is attached to these figures: a LoRA over every convolution reads every dW twice.
 """
 import argparse
 import json
@@ -66,6 +75,8 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--launch-reps", type=int, default=50, help="back-to-back launches of each update launch timed alone")
+    ap.add_argument("--conv-targets", action="store_true",
+                    help="adapters on every resnet conv1 / conv2 (pixel UNets: instead of the attention projections; sd15: beside them)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_lora.py needs a GPU"
@@ -88,7 +99,14 @@ def main():
         pattern = r"attentions\.\d+\.to_(q|k|v|out\.0)\.weight"
     eng.init_random(seed=42)
     targets = [n for n in eng.ps.specs if re.search(pattern, n)]
-    target_floats = sum(int(eng.ps.specs[n].numel) for n in targets)
+    conv_pattern, conv_targets = None, []
+    if a.conv_targets:
+        conv_pattern = r"resnets\.\d+\.conv[12]\.weight"
+        conv_targets = [n for n in eng.ps.specs if re.search(conv_pattern, n)]
+        assert conv_targets and all(eng.ps.specs[n].kind == "conv3" for n in conv_targets)
+        if not sd:
+            pattern, targets = None, []
+    target_floats = sum(int(eng.ps.specs[n].numel) for n in targets + conv_targets)
     B, hw, cin = a.batch, cfg.sample_size, cfg.in_channels
     g = torch.Generator(device=dev).manual_seed(42)
     cond = None
@@ -124,6 +142,9 @@ def main():
         if st.lora is not None:
             lo = st.lora
             info["rank"], info["adapter_floats"], info["project_tiles"], info["merge_tiles"] = lo.rank, lo.L, lo.project_tiles, lo.merge_tiles
+            info["adapter_bytes"] = 4 * lo.params
+            if lo.conv_names:
+                info["conv_project_tiles"], info["conv_merge_tiles"] = lo.conv_project_tiles, lo.conv_merge_tiles
             pm, om, mm = timed(lo.project, a.launch_reps), timed(lambda: st.opt.launch(lo.g, **okw), a.launch_reps), timed(lo.merge, a.launch_reps)
             info["launches_ms"] = {"siss_lora_project": round(pm, 4), "adamw_on_adapters": round(om, 4), "siss_lora_merge": round(mm, 4),
                                    "sum": round(pm + om + mm, 4)}
@@ -145,9 +166,9 @@ def main():
         legs[name] = (st, graph, info)
 
     make("full")
-    make("trainable", trainable=targets)
+    make("trainable", trainable=targets + conv_targets)
     for r in RANKS:
-        make(f"lora_r{r}", lora=LoRAState(eng, targets, r, float(r), seed=0))
+        make(f"lora_r{r}", lora=LoRAState(eng, targets, r, float(r), seed=0, conv_names=conv_targets))
     for _ in range(a.rounds):
         for name, (st, graph, info) in legs.items():
             graph.replay()
@@ -162,6 +183,7 @@ def main():
     full_ms = legs["full"][2]["launches_ms"]["flat_adamw_full_buffer"]
     res = {"tool": "bench_lora", "device": torch.cuda.get_device_name(0), "config": a.config, "batch": B, "weights": "random-init",
            "dtype": "bf16", "parameters": total_params, "targets": pattern, "target_tensors": len(targets), "target_floats": target_floats,
+           **({"conv_targets": conv_pattern, "conv_target_tensors": len(conv_targets)} if conv_targets else {}),
            "reps": a.reps, "rounds": a.rounds, "launch_reps": a.launch_reps,
            "timing": "device events around `reps` replays of each leg's hipGraph, legs interleaved, one figure per round; launches_ms: "
                      "`launch_reps` back-to-back eager launches between two device events after two warm-up launches",

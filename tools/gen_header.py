@@ -33,7 +33,7 @@ DOCS = {
     'dpm_solver.hip': "The opt-in DPM-Solver++ (2M) evaluation sampler (siss_amd/scheduler.py DPMSolverMultistepScheduler; no counterpart in the\n * reference, whose samplers are diffusers' DDPMScheduler / DDIMScheduler at 50 steps): classifier-free guidance, the x0-prediction and the\n * first / second order multistep update in one streaming launch per sampling step, with the noise norms of siss_cfg_ddim_step.",
     'latent_cache.hip': "The latent cache of the SD task (siss_amd/latent_cache.py; delete_sd.py:879-888 vae.encode(x).latent_dist.sample() *\n * vae.config.scaling_factor, once per micro-batch and batch): the frozen encoder's posterior moments of the dataset stay on the device and a\n * micro-batch of latents is one gather-and-sample launch over the rows its indices name.",
     'image_store.hip': "The image store of the pixel-space tasks (siss_amd/image_store.py; the DataLoader in front of delete_celeb.py:571-580 and\n * train_unconditional.py:366-372: decode, ToTensor / Normalize, stack and a host-to-device copy of f32 images per micro-batch): the dataset\n * stays on the device as uint8 and a micro-batch of images is one table-gather launch over the rows its indices name.",
-    'lora.hip': "Opt-in LoRA unlearning on the UNet's linear projections (siss_amd/lora.py, `deletion.lora`; no counterpart in the reference,\n * whose runs update every parameter): the engine runs on the merged weight W = W0 + s B A, so these are the chain rule from the weight\n * gradients of both sets to the adapter's (dB = s dW A^T, dA = s B^T dW) and the merge back into the f32 master and its bf16 shadow,\n * each ONE launch over a device job table of all targets; f32 MFMA products in fixed orders, no atomics.",
+    'lora.hip': "Opt-in LoRA unlearning on the UNet's linear projections and 3x3 convolutions (siss_amd/lora.py, `deletion.lora`; no counterpart\n * in the reference, whose runs update every parameter): the engine runs on the merged weight W = W0 + s B A, so these are the chain\n * rule from the weight gradients of both sets to the adapter's (dB = s dW A^T, dA = s B^T dW) and the merge back into the f32 master\n * and its bf16 shadow, each ONE launch over a device job table of all targets; the *_conv forms take the tap-major [9, Co, Ci]\n * weights with B shared by the taps (peft's Conv2d adapter); f32 MFMA products in fixed orders, no atomics.",
     'saliency.hip': "Opt-in saliency-masked unlearning (siss_amd/saliency.py, `deletion.saliency`; SalUn, Fan et al., ICLR 2024; no counterpart in the\n * reference, whose runs update every parameter): the exact k-th largest gradient magnitude of the flat buffer by an integer radix select,\n * the packed one-bit-per-weight mask of that threshold, and the two flat passes of optimizer.hip restricted to the weights whose bit is\n * set; integer counts and sums in fixed orders, no atomics on global memory.",
     'ewc.hip': "Opt-in Fisher-weighted anchor of the unlearning update (siss_amd/ewc.py, `deletion.ewc`; elastic weight consolidation as Selective\n * Amnesia uses it, Heng & Soh, NeurIPS 2023, and its uniform case L2-SP; no counterpart in the reference, whose runs have no penalty\n * term): the running empirical Fisher F += g^2 w of the keep gradient, and pass 1 of optimizer.hip with the penalty's gradient\n * strength * F * (p - pstar) folded into the keep-side set before the norms; explicit f32 round-to-nearest operations, f64 sums in\n * fixed orders, no atomics.",
     'ssd.hip': "Opt-in Selective Synaptic Dampening (siss_amd/ssd.py, `deletion.ssd`; Foster, Schoepf & Brintrup, AAAI 2024; no counterpart in\n * the reference, whose runs unlearn by gradient steps only): the ratio of the forget set's empirical Fisher to the keep data's per\n * weight, and ONE streaming pass that selects the weights whose ratio lies above a threshold, scales them by min(lambda / ratio, 1)\n * and reports what it did; explicit f32 round-to-nearest operations, exact counts, f64 sums in fixed orders, no atomics.",
