@@ -77,6 +77,7 @@ F32_SAME = {"siss_zero_ranges", "siss_upsample_phase_wgrad_fold", "siss_timestep
             "siss_lora_project", "siss_lora_merge", "siss_lora_project_conv", "siss_lora_merge_conv",
             "siss_absf_select", "siss_saliency_mask", "siss_grad_norms_scale_masked", "siss_recombine_clip_adamw_masked",
             "siss_fisher_accumulate", "siss_grad_norms_scale_ewc",
+            "siss_grad_norms_scale_surgery", "siss_recombine_clip_adamw_surgery",
             "siss_ssd_ratio", "siss_ssd_dampen",
             "siss_sscd_topk", "siss_sscd_count_above", "siss_sscd_fill_above"}
 for _b, _f in F32_ENTRY.items():          # the header's promise "same argument lists", checked once instead of assumed

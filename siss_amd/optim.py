@@ -34,7 +34,8 @@ class FlatAdamW:
         self.scalars = torch.zeros(lib.query("siss_opt_scalars_words"), dtype=torch.float32, device=dev)
         self.last_grad = None
 
-    def launch(self, grads, *, scaling_norm=None, eta=None, inf_guard=False, want_grad=False, ranges=None, mask=None, ewc=None):
+    def launch(self, grads, *, scaling_norm=None, eta=None, inf_guard=False, want_grad=False, ranges=None, mask=None, ewc=None,
+               surgery=None):
         """Enqueue both passes (no host sync).  grads: [2, P] f32 = (g_x, g_a).  ranges: (device table, stretches, granules) of a
         trainable subset (siss_amd.trainable.Subset.table) -- norms, scaling factor, clip and update over the listed stretches
         only, every other byte of p / m / v / shadow untouched; the caller keeps the table alive (a captured step holds its address).
@@ -42,11 +43,16 @@ class FlatAdamW:
         the elements whose bit is set (csrc/saliency.hip); the caller keeps the words alive likewise.
         ewc: a siss_amd.ewc.FisherAnchor over this buffer -- pass 1 folds strength * F * (p - pstar) into the keep-side set first
         (csrc/ewc.hip) and grads[0] IS OVERWRITTEN with g_x + that term; pass 2 is the plain one.  Not with ranges / mask; the caller
-        keeps the anchor alive likewise."""
+        keeps the anchor alive likewise.
+        surgery: a siss_amd.surgery.Surgery over this buffer -- both passes are those of csrc/surgery.hip: per group of the buffer the
+        conflicting component of the pair is projected out before the norm fix (not with eta: EraseDiff's mode is refused).  Not with
+        the other three; the caller keeps the object alive likewise."""
         n = self.p.numel()
         assert grads.dtype == torch.float32 and grads.shape == (2, n) and grads.is_contiguous()
         mode, knob = _mode_knob(scaling_norm, eta, inf_guard)
-        exclusive("FlatAdamW.launch", {"ranges=": ranges, "mask=": mask, "ewc=": ewc})
+        exclusive("FlatAdamW.launch", {"surgery=": surgery, "ranges=": ranges, "mask=": mask, "ewc=": ewc})
+        if surgery is not None:
+            return self._launch_surgery(grads, surgery, mode, knob, want_grad)
         # pass 1 takes (gx, ga, *head, mode .. partials, *tail, scalars), pass 2 (gx .. g_out, n, *sel, lr .. scalars)
         one, two, head, tail, sel = "siss_grad_norms_scale", "siss_recombine_clip_adamw", None, (), ()
         if ewc is not None:
@@ -80,6 +86,37 @@ class FlatAdamW:
         lib.call(two, grads[0], grads[1], self.p, self.m, self.v, self.shadow, self.last_grad if want_grad else None, n, *sel,
                  self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.scalars)
 
+    def _launch_surgery(self, grads, sg, mode, knob, want_grad):
+        """Both passes of csrc/surgery.hip on the plan and the slabs `sg` owns."""
+        self._surgery_check(sg)
+        if mode == MODE_ERASEDIFF:
+            raise ValueError("FlatAdamW.launch(surgery=..., eta=...): gradient surgery runs with the norm fix; EraseDiff's s <= 0 is "
+                             "that mode's own conflict rule")
+        n = self.p.numel()
+        if want_grad and (self.last_grad is None):
+            self.last_grad = torch.empty_like(self.p)
+        lib.call("siss_grad_norms_scale_surgery", grads[0], grads[1], n, sg.group_offsets, sg.groups, sg.plan, sg.jobs, sg.smode, mode,
+                 knob, self.max_grad_norm, self.betas[0], self.betas[1], sg.partials, sg.group_sums, sg.coef, self.scalars)
+        lib.call("siss_recombine_clip_adamw_surgery", grads[0], grads[1], self.p, self.m, self.v, self.shadow,
+                 self.last_grad if want_grad else None, n, sg.group_offsets, sg.groups, sg.plan, sg.jobs, sg.coef, self.lr,
+                 self.betas[0], self.betas[1], self.eps, self.wd, self.scalars)
+
+    def _surgery_check(self, sg):
+        """Once per object, not per step: the kernels are there and the plan covers this buffer on its device (before a step is
+        captured: SISSStepper.set_surgery calls this)."""
+        if sg is getattr(self, "_surgery_checked", None):
+            return
+        from .surgery import require_kernels
+        require_kernels()
+        n = self.p.numel()
+        if not (sg.total == n and sg.offsets[0] == 0 and sg.offsets[-1] == n and sg.plan.device == self.p.device
+                and sg.plan.numel() == 2 * sg.jobs + 2 * (sg.groups + 1) and sg.chunk == lib.query("siss_surgery_chunk")
+                and sg.partials.numel() >= 3 * sg.jobs and sg.group_sums.numel() == 3 * sg.groups and sg.coef.numel() == 2 * sg.groups
+                and not sg.group_offsets.is_cuda):
+            raise ValueError(f"FlatAdamW.launch(surgery=...): the plan must cover this buffer of {n} floats on {self.p.device}; got one "
+                             f"over {sg.total} floats on {sg.plan.device}")
+        self._surgery_checked = sg
+
     def _ewc_check(self, ewc):
         """Once per anchor, not per step: the kernels are there, F and pstar cover this buffer on its device, and the slab of the
         penalty sums exists (before a step is captured: SISSStepper.set_ewc calls this)."""
@@ -100,14 +137,15 @@ class FlatAdamW:
         self._ewc_checked = ewc
 
     def launch_sharded(self, gx_shard, ga_shard, lo, hi, group, *, scaling_norm=None, eta=None, inf_guard=False, ranges=None, mask=None,
-                       ewc=None):
+                       ewc=None, surgery=None):
         """The same update on THIS rank's parameter shard [lo, hi) (sharded data-parallel exchange):
         gx_shard / ga_shard are the rank-summed gradients of the shard.  The three norm sums are all-reduced (24 bytes),
         so every rank forms the same scaling factor and clip coefficient as the replicated update; p / m / v / shadow are
         touched on [lo, hi) only -- the caller all-gathers the parameters afterwards."""
         import ctypes
         import torch.distributed as dist
-        exclusive("FlatAdamW.launch_sharded", {"ranges=": ranges, "mask=": mask, "ewc=": ewc, SHARD: True}, NotImplementedError)
+        exclusive("FlatAdamW.launch_sharded", {"surgery=": surgery, "ranges=": ranges, "mask=": mask, "ewc=": ewc, SHARD: True},
+                  NotImplementedError)
         n = hi - lo
         assert gx_shard.numel() == n and ga_shard.numel() == n and gx_shard.dtype == torch.float32
         mode, knob = _mode_knob(scaling_norm, eta, inf_guard)

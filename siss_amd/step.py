@@ -43,7 +43,7 @@ class SISSStepper:
                  weight_decay=1e-2, scaling_norm=None, eta=None, lambd=0.5, train_batch_size,
                  grad_accum=1, max_grad_norm=1.0, loss_fn=SISS, inf_guard=False, process_group=None,
                  mixed_precision="bf16", superfactor=1.0, superfactor_decay=None, trainable=None, lora=None, saliency=None,
-                 ewc=None):
+                 ewc=None, surgery=None):
         """trainable: None (every parameter: the reference's protocol), an iterable of parameter names, or "requires_grad" (the flags
         of the parameters of the UNet2DModel / UNet2DConditionModel that owns the engine).  With a subset the norms, the scaling
         factor, the clip and the AdamW update run over the trainable tensors only; the rest keep every byte.  The selection (the
@@ -65,11 +65,16 @@ class SISSStepper:
         ewc: None, or a siss_amd.ewc.FisherAnchor over this engine (opt-in, not the reference's protocol): once per optimizer step,
         after the accumulation and the data-parallel exchange, strength * F * (theta - theta*) is added to the keep-side gradient set
         inside pass 1 of the update (csrc/ewc.hip), so that the norms, the scaling factor, the clip and AdamW see it; exclusive with
-        trainable=, lora= and saliency=.  F and theta* live as long as the stepper: a captured step holds their addresses."""
+        trainable=, lora= and saliency=.  F and theta* live as long as the stepper: a captured step holds their addresses.
+
+        surgery: None, or a siss_amd.surgery.Surgery over this engine (opt-in, not the reference's protocol): once per optimizer step,
+        after the accumulation and the data-parallel exchange, the conflicting component of the (keep, forget) gradient pair is
+        projected out per group of the buffer before the norm fix (csrc/surgery.hip); for the two-set losses with the norm fix only;
+        exclusive with the other four.  Its plan and slabs live as long as the stepper: a captured step holds their addresses."""
         self.e = engine
         self.lora = lora
-        self.saliency = self.ewc = None
-        exclusive("SISSStepper", {"ewc=": ewc, "saliency=": saliency, "lora=": lora, "trainable=": trainable})
+        self.saliency = self.ewc = self.surgery = None
+        exclusive("SISSStepper", {"surgery=": surgery, "ewc=": ewc, "saliency=": saliency, "lora=": lora, "trainable=": trainable})
         if lora is not None:
             if lora.engine is not engine:
                 raise ValueError("SISSStepper(lora=...): the LoRAState was built over another engine")
@@ -135,6 +140,8 @@ class SISSStepper:
             self.set_saliency(saliency)
         if ewc is not None:
             self.set_ewc(ewc)
+        if surgery is not None:
+            self.set_surgery(surgery)
 
     def _fit_exchange(self, overlap):
         """set_overlap with what the variant may use of (overlap, self.exchange): a LoRA / subset step has ONE collective after the
@@ -151,10 +158,11 @@ class SISSStepper:
         self.set_overlap(overlap)
 
     def _adopt(self, name, obj, tensor, require_kernels, launch_kw, ready=None):
-        """set_saliency / set_ewc: a `full` stepper moves to variant `name` (another object of the stepper's own variant replaces the
-        first).  tensor: the per-float device tensor of obj, which must cover this engine's flat buffer on its device; ready(obj): what
-        has to exist before a step is captured."""
-        present = {"ewc=": self.ewc, "saliency=": self.saliency, "lora=": self.lora, "trainable=": self.subset}
+        """set_saliency / set_ewc / set_surgery: a `full` stepper moves to variant `name` (another object of the stepper's own variant
+        replaces the first).  tensor: a device tensor of obj (per float, or the surgery's plan), which must live on the engine's
+        device; obj must cover this engine's flat buffer; ready(obj): what has to exist before a step is captured."""
+        present = {"surgery=": getattr(self, "surgery", None), "ewc=": self.ewc, "saliency=": self.saliency, "lora=": self.lora,
+                   "trainable=": self.subset}
         del present[name + "="]
         exclusive(f"SISSStepper.set_{name}", {name + "=": obj, **present})
         require_kernels()
@@ -176,6 +184,14 @@ class SISSStepper:
         from .ewc import require_kernels
         # (ready: the slab of the penalty sums is allocated now, not inside a captured step)
         self._adopt("ewc", anchor, anchor.fisher, require_kernels, {"ewc": anchor}, ready=self.opt._ewc_check)
+
+    def set_surgery(self, surgery):
+        """Project the conflicting component out of the gradient pair with `surgery` (siss_amd.surgery.Surgery over this engine) from
+        the next step on -- what SISSStepper(surgery=...) does.  Before a step is captured: a captured step holds the addresses of the
+        plan and the slabs.  Refused for the losses without a gradient pair under the norm fix."""
+        from .surgery import check_loss, require_kernels
+        check_loss(self.loss_fn, "SISSStepper(surgery=...)")
+        self._adopt("surgery", surgery, surgery.plan, require_kernels, {"surgery": surgery}, ready=self.opt._surgery_check)
 
     def set_saliency(self, mask):
         """Restrict the update to the set bits of `mask` (siss_amd.saliency.SaliencyMask over this engine) from the next step on -- what
@@ -570,7 +586,7 @@ class SISSStepper:
 
     def _active(self):
         """The object of the active variant that carries log fields (None: the full update, a trainable subset)."""
-        return {"lora": self.lora, "saliency": self.saliency, "ewc": self.ewc}.get(self.variant)
+        return getattr(self, self.variant) if self.variant in ("lora", "saliency", "ewc", "surgery") else None
 
     def log_fields(self):
         """What every log line of the run carries beside the step's statistics: the parameters the optimizer updates and the active

@@ -318,6 +318,20 @@ class _DeleteBase(Task):
         # deletion.ewc: a malformed mapping, an unknown field, a missing or non-positive strength, batches / batch_size < 1 and the key
         # together with deletion.trainable / deletion.lora / deletion.saliency are settled here too
         self.ewc_config()
+        # deletion.surgery: a malformed mapping, an unknown field or value, the key together with deletion.trainable / deletion.lora /
+        # deletion.saliency / deletion.ewc, and a loss without a gradient pair under the norm fix are settled here too
+        self.surgery_config()
+
+    # -- deletion.surgery: null | {mode, granularity} (OPT-IN; siss_amd/surgery.py) ------------------------------------------------------
+    def surgery_config(self):
+        """The parsed deletion.surgery (siss_amd.surgery.SurgeryConfig), or None (absent / null: the plain update, today's run)."""
+        from .surgery import check_loss, parse_surgery
+        d = self.cfg.get("deletion") or {}
+        sc = parse_surgery(d.get("surgery"), trainable=d.get("trainable"), lora=d.get("lora"), saliency=d.get("saliency"),
+                           ewc=d.get("ewc"))
+        if sc is not None:
+            check_loss(d.get("loss_fn"))
+        return sc
 
     # -- deletion.ssd: null | {alpha, fraction, lambda, keep_batches, forget_batches, batch_size, seed, targets, path} (OPT-IN; siss_amd/ssd.py)
     def ssd_config(self):
@@ -867,6 +881,14 @@ class _DeleteBase(Task):
         ewc = self.ewc_anchor(stepper, ds_all, B, cond, device, rank, world, pg)
         if ewc is not None:
             stepper.set_ewc(ewc)
+        sgc = self.surgery_config()
+        if sgc is not None:
+            from .surgery import Surgery
+            stepper.set_surgery(Surgery(eng, sgc.mode, sgc.granularity))
+            if rank == 0:
+                sg = stepper.surgery
+                print(f"[siss_amd] deletion.surgery: mode {sg.mode}, {sg.groups} group(s) ({sg.granularity}), {sg.jobs} jobs of "
+                      f"{sg.chunk} floats")
         if rank == 0 and self.replication is not None:
             self.open_replication(device)
 
@@ -1679,6 +1701,9 @@ class TrainUnconditional(Task):
         if (cfg.get("deletion") or {}).get("ewc") is not None:
             raise NotImplementedError("deletion.ewc: the Fisher anchor belongs to the unlearning tasks (delete_celeb / delete_tshirt / "
                                       "delete_sd); the pre-training task has no pretrained weights to stay near")
+        if (cfg.get("deletion") or {}).get("surgery") is not None:
+            raise NotImplementedError("deletion.surgery: gradient surgery belongs to the unlearning tasks (delete_celeb / delete_tshirt "
+                                      "/ delete_sd); the pre-training task has one gradient set and nothing to project")
         if (cfg.get("deletion") or {}).get("ssd") is not None:
             raise NotImplementedError("deletion.ssd: Selective Synaptic Dampening belongs to the unlearning tasks (delete_celeb / "
                                       "delete_tshirt / delete_sd); the pre-training task has no forget set to dampen for")

@@ -1,4 +1,5 @@
-"""The opt-in variants of the unlearning update -- `deletion.trainable`, `deletion.lora`, `deletion.saliency`, `deletion.ewc` -- and
+"""The opt-in variants of the unlearning update -- `deletion.trainable`, `deletion.lora`, `deletion.saliency`, `deletion.ewc`,
+`deletion.surgery` -- and
 what they share: ONE table of their static facts (which gradient exchanges a variant may use and why not the others, why it runs
 alone), the one exclusivity check every entry point calls, the field checks of the parsed keys, and the flat-buffer helpers of what
 is built from backward passes at the pretrained weights -- the saliency mask, the Fisher anchor and the importances of siss_amd/ssd.py
@@ -22,6 +23,9 @@ VARIANTS = {
     "saliency": Variant("saliency mask", "the saliency mask selects single weights of every tensor", None,
                         "there is no masked sharded update"),
     "ewc": Variant("Fisher anchor", "the Fisher anchor is folded into the whole-buffer update", None, "there is no sharded fold"),
+    # (the overlapped early-tail exchange is allowed: the gram pass reads the whole summed buffer after it)
+    "surgery": Variant("gradient surgery", "the surgery projects the whole-buffer gradient pair group by group", None,
+                       "there is no sharded surgery update"),
 }
 ALIASES = {"ranges": "trainable", "mask": "saliency"}          # FlatAdamW.launch's keywords
 SHARD = "a parameter shard"                                    # launch_sharded's own side of `exclusive`

@@ -36,12 +36,13 @@ DOCS = {
     'lora.hip': "Opt-in LoRA unlearning on the UNet's linear projections and 3x3 convolutions (siss_amd/lora.py, `deletion.lora`; no counterpart\n * in the reference, whose runs update every parameter): the engine runs on the merged weight W = W0 + s B A, so these are the chain\n * rule from the weight gradients of both sets to the adapter's (dB = s dW A^T, dA = s B^T dW) and the merge back into the f32 master\n * and its bf16 shadow, each ONE launch over a device job table of all targets; the *_conv forms take the tap-major [9, Co, Ci]\n * weights with B shared by the taps (peft's Conv2d adapter); f32 MFMA products in fixed orders, no atomics.",
     'saliency.hip': "Opt-in saliency-masked unlearning (siss_amd/saliency.py, `deletion.saliency`; SalUn, Fan et al., ICLR 2024; no counterpart in the\n * reference, whose runs update every parameter): the exact k-th largest gradient magnitude of the flat buffer by an integer radix select,\n * the packed one-bit-per-weight mask of that threshold, and the two flat passes of optimizer.hip restricted to the weights whose bit is\n * set; integer counts and sums in fixed orders, no atomics on global memory.",
     'ewc.hip': "Opt-in Fisher-weighted anchor of the unlearning update (siss_amd/ewc.py, `deletion.ewc`; elastic weight consolidation as Selective\n * Amnesia uses it, Heng & Soh, NeurIPS 2023, and its uniform case L2-SP; no counterpart in the reference, whose runs have no penalty\n * term): the running empirical Fisher F += g^2 w of the keep gradient, and pass 1 of optimizer.hip with the penalty's gradient\n * strength * F * (p - pstar) folded into the keep-side set before the norms; explicit f32 round-to-nearest operations, f64 sums in\n * fixed orders, no atomics.",
+    'surgery.hip': "Opt-in gradient surgery between the keep and forget gradients (siss_amd/surgery.py, `deletion.surgery`; PCGrad, Yu et al.,\n * NeurIPS 2020; gradient-projection unlearning, Hoang et al., WACV 2024; the restricted gradient of Ko et al., NeurIPS 2024; no counterpart\n * in the reference, whose update is g_x - s g_a whatever the sign of <g_x, g_a>): a deterministic segmented reduction of the three sums\n * per group of the flat buffer (the whole buffer, or one parameter tensor), the per-group coefficient table (cx, ca) of the projected\n * pair, and pass 2 of optimizer.hip recombining with it; f64 sums in fixed orders that do not depend on the grid, explicit f32\n * round-to-nearest operations, no atomics.",
     'ssd.hip': "Opt-in Selective Synaptic Dampening (siss_amd/ssd.py, `deletion.ssd`; Foster, Schoepf & Brintrup, AAAI 2024; no counterpart in\n * the reference, whose runs unlearn by gradient steps only): the ratio of the forget set's empirical Fisher to the keep data's per\n * weight, and ONE streaming pass that selects the weights whose ratio lies above a threshold, scales them by min(lambda / ratio, 1)\n * and reports what it did; explicit f32 round-to-nearest operations, exact counts, f64 sums in fixed orders, no atomics.",
     'sscd_search.hip': "Dataset-wide SSCD copy search (siss_amd/sscd_search.py, `metrics.sscd_nn`, tools/find_copies.py; notebooks/sscd.ipynb of the\n * reference: embed a directory, form ALL pairwise similarities on the host, list what lies above a threshold): many unit-row queries\n * against a gallery of N unit rows, keeping per query the best k or the rows at or above a threshold; the nq x N matrix is never formed and\n * no similarity travels to the host.  Exact f32 on v_mfma_f32_16x16x4_f32, one value per pair whatever the entry point, no atomics.",
     'timeemb.hip': "Sinusoidal timestep embedding (diffusers Timesteps/get_timestep_embedding), TimestepEmbedding MLP and\n * ResnetBlock2D.time_emb_proj linears (M = batch rows), forward and backward.",
 }
 ORDER = ['siss_loss.hip', 'gemm_nt.hip', 'gemm_tn.hip', 'groupnorm.hip', 'conv_small.hip', 'attention.hip', 'attn1h.hip', 'flash_attn.hip', 'transformer.hip',
-         'timeemb.hip', 'elementwise.hip', 'optimizer.hip', 'train_state.hip', 'likelihood.hip', 'membership.hip', 'metric_conv.hip', 'metric_train.hip', 'inception.hip', 'kmeans.hip', 'sscd.hip', 'clip_iqa.hip', 'prompt_grad.hip', 'injection.hip', 'dpm_solver.hip', 'latent_cache.hip', 'image_store.hip', 'lora.hip', 'saliency.hip', 'ewc.hip', 'ssd.hip', 'sscd_search.hip', 'f32_path.hip']
+         'timeemb.hip', 'elementwise.hip', 'optimizer.hip', 'train_state.hip', 'likelihood.hip', 'membership.hip', 'metric_conv.hip', 'metric_train.hip', 'inception.hip', 'kmeans.hip', 'sscd.hip', 'clip_iqa.hip', 'prompt_grad.hip', 'injection.hip', 'dpm_solver.hip', 'latent_cache.hip', 'image_store.hip', 'lora.hip', 'saliency.hip', 'ewc.hip', 'surgery.hip', 'ssd.hip', 'sscd_search.hip', 'f32_path.hip']
 HEAD = '''/* siss_hip.h -- C ABI of libsiss_hip.so: the MI355X (gfx950) kernels of the SISS unlearning step.
  *
  * GENERATED by tools/gen_header.py from the .hip sources under siss_amd/csrc -- edit the sources, then regenerate.
