@@ -6,19 +6,17 @@
 // NUMERIC CONTRACT.  The similarity of a pair is ONE f32 value that depends on the two rows (and d) and on nothing else: the fmaf
 // chain over k = 0, 1, ..., d - 1 from +0, which is what the MFMA computes when it is fed four consecutive k per instruction in
 // ascending order.  Every entry point, every nq / ng / k / self0, every tile position and every split of the gallery into pieces
-// runs that same chain (sscd_tile below is the only place a product is formed), so count_above and fill_above agree and a value
+// runs that same chain (sscd_tile of sscd_tile.h is the only place a product is formed), so count_above and fill_above agree and a value
 // returned by topk is the value fill_above lists.  A NaN similarity is never selected and never counted; -0 is returned as +0.
 //
 // ORDER.  (value descending, gallery index ascending) is a total order on the candidates of a query, each piece keeps the exact
 // best k of its rows under it and the fold picks the best k of the pieces' lists under it: the result does not depend on the number of
 // pieces.  No atomics anywhere; the threshold lists are placed by counts -> exclusive scan -> ballot ranks, in ascending index.
 #include "common.h"
+#include "sscd_tile.h"           // kQS, kQT, kGT, transpose4, load4, sscd_tile: shared with feature_sets.hip
 
 namespace {
 
-constexpr int kQS = 2;           // 16-row query sub-tiles per wave tile: each gallery operand feeds both (5 -> 3 operand loads per 16 MFMAs)
-constexpr int kQT = 16 * kQS;    // queries per wave tile
-constexpr int kGT = 64;          // gallery rows per wave tile: four 16-column MFMA tiles; 2 x 4 independent accumulators
 constexpr int kMaxK = 32;
 constexpr int kMaxPieces = 256;  // pieces of the gallery per query (the fold gives each lane at most four lists)
 constexpr int kTargetWaves = 2048;   // 256 CUs x 4 SIMDs x 2 waves
@@ -39,106 +37,6 @@ static inline Split split_for(long nq, long ng) {
     s.tpp = (ntiles + want - 1) / want;
     s.pieces = (int)((ntiles + s.tpp - 1) / s.tpp);
     return s;
-}
-
-// lanes (c, h), c = lane & 15, h = lane >> 4, hold x[j] = row_c[k0 + 4 h + j]; afterwards x[s] = row_c[k0 + 4 s + h]: the operand of
-// the MFMA step s (A[c][k = h] / B[k = h][c]).  A 4 x 4 transpose between the lane bits 4, 5 and the register index: v_permlane16_swap
-// exchanges the odd 16-lane rows of its first operand with the even rows of its second, v_permlane32_swap the upper half of the first
-// with the lower half of the second.  Inline asm with its wait states inside (a VALU write needs two before a permlane swap reads it):
-// written with __builtin_amdgcn_permlane{16,32}_swap, hipcc 7.2 fed two MFMA steps of a trip the SAME register and loaded one dword
-// of the tail's four (seen in the ISA; the exact-data test fails on it).
-__device__ __forceinline__ void transpose4(f32x4_t& x) {
-    float x0 = x[0], x1 = x[1], x2 = x[2], x3 = x[3];
-    asm volatile("s_nop 1\n\t"
-                 "v_permlane16_swap_b32 %0, %1\n\t"
-                 "v_permlane16_swap_b32 %2, %3\n\t"
-                 "s_nop 1\n\t"
-                 "v_permlane32_swap_b32 %0, %2\n\t"
-                 "v_permlane32_swap_b32 %1, %3\n\t"
-                 "s_nop 1"
-                 : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3));
-    x = f32x4_t{x0, x1, x2, x3};
-}
-
-__device__ __forceinline__ f32x4_t load4(const float* p, bool on) {
-    return on ? *reinterpret_cast<const f32x4_t*>(p) : f32x4_t{0.f, 0.f, 0.f, 0.f};
-}
-
-// The 32 x 64 similarities of queries [q0, q0 + 32) against gallery rows [g0, g0 + 64):
-// acc[u][t][r] = <q[q0 + 16 u + 4 h + r], g[g0 + 16 t + c]>.  Rows past the end are read as the last row (their results are discarded by
-// the caller).  k runs in ascending order, 16 per trip (one 16-byte load per lane and operand, transposed in registers), the d % 16
-// tail by the lane groups that own it.
-__device__ __forceinline__ void sscd_tile(const float* __restrict__ q, int nq, const float* __restrict__ g, long ng, int d,
-                                          int q0, long g0, int c, int h, f32x4_t (&acc)[kQS][4]) {
-    const float* qp[kQS];
-    const float* gp[4];
-#pragma unroll
-    for (int u = 0; u < kQS; ++u) {
-        const long qr = (long)q0 + 16 * u + c < nq ? (long)q0 + 16 * u + c : (long)nq - 1;
-        qp[u] = q + qr * d + 4 * h;
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const long gr = g0 + 16 * t + c < ng ? g0 + 16 * t + c : ng - 1;
-        gp[t] = g + gr * d + 4 * h;
-#pragma unroll
-        for (int u = 0; u < kQS; ++u) acc[u][t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    }
-    const int dfull = d & ~15;
-    f32x4_t a[kQS], b[4];
-    if (dfull) {
-#pragma unroll
-        for (int u = 0; u < kQS; ++u) a[u] = load4(qp[u], true);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) b[t] = load4(gp[t], true);
-    }
-    for (int k0 = 0; k0 < dfull; k0 += 16) {
-        f32x4_t an[kQS], bn[4];
-#pragma unroll
-        for (int u = 0; u < kQS; ++u) an[u] = a[u];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) bn[t] = b[t];
-        if (k0 + 16 < dfull) {                       // the next trip's operands travel under this trip's MFMAs
-#pragma unroll
-            for (int u = 0; u < kQS; ++u) an[u] = load4(qp[u] + k0 + 16, true);
-#pragma unroll
-            for (int t = 0; t < 4; ++t) bn[t] = load4(gp[t] + k0 + 16, true);
-        }
-#pragma unroll
-        for (int u = 0; u < kQS; ++u) transpose4(a[u]);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            transpose4(b[t]);
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-#pragma unroll
-                for (int u = 0; u < kQS; ++u) acc[u][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][s], b[t][s], acc[u][t], 0, 0, 0);
-        }
-#pragma unroll
-        for (int u = 0; u < kQS; ++u) a[u] = an[u];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) b[t] = bn[t];
-    }
-    const int steps = (d - dfull) >> 2;              // 0 .. 3 MFMA steps of four k each
-    if (steps) {
-        const bool on = h < steps;                   // lane group h holds the k of step h after the transpose
-#pragma unroll
-        for (int u = 0; u < kQS; ++u) {
-            a[u] = load4(qp[u] + dfull, on);
-            transpose4(a[u]);
-        }
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            b[t] = load4(gp[t] + dfull, on);
-            transpose4(b[t]);
-#pragma unroll
-            for (int s = 0; s < 3; ++s)
-                if (s < steps) {
-#pragma unroll
-                    for (int u = 0; u < kQS; ++u) acc[u][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][s], b[t][s], acc[u][t], 0, 0, 0);
-                }
-        }
-    }
 }
 
 // a before b in the result order (value descending, then index ascending; values are never NaN here)

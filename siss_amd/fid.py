@@ -218,12 +218,14 @@ def frechet_distance(mu1, sigma1, mu2, sigma2):
 class FrechetInceptionDistance:
     """torchmetrics.image.fid.FrechetInceptionDistance(feature=2048, normalize=True, reset_real_features=False): per side the count,
     the f64 feature sum [D] and the f64 sum of outer products [D, D], held on `device` and updated there by one launcher call per
-    batch.  `inception` maps [N, 3, H, W] images in [0, 1] to [N, D] features (None: update_features only)."""
+    batch.  `inception` maps [N, 3, H, W] images in [0, 1] to [N, D] features (None: update_features only).  `sink` (None: nothing
+    changes) is called as sink(f, real) with every batch of features the statistics take (feature_sets.FeatureSets keeps them)."""
 
-    def __init__(self, inception=None, num_features=FEATURES, device="cpu"):
+    def __init__(self, inception=None, num_features=FEATURES, device="cpu", sink=None):
         if num_features % 16:
             raise ValueError(f"num_features={num_features}: a multiple of 16 is needed")
         self.inception, self.num_features, self.device = inception, int(num_features), torch.device(device)
+        self.sink = sink
         D = self.num_features
         for side in ("real", "fake"):
             setattr(self, side + "_features_sum", torch.zeros(D, dtype=torch.float64, device=self.device))
@@ -247,6 +249,8 @@ class FrechetInceptionDistance:
         lib.call("siss_fid_stats_update", f, f.shape[0], self.num_features, getattr(self, side + "_features_sum"),
                  getattr(self, side + "_features_cov_sum"))
         setattr(self, side + "_features_num_samples", getattr(self, side + "_features_num_samples") + int(f.shape[0]))
+        if self.sink is not None:
+            self.sink(f, real)
 
     def compute(self):
         n1, n2 = int(self.real_features_num_samples), int(self.fake_features_num_samples)
@@ -268,11 +272,12 @@ class FrechetInceptionDistance:
 class FIDEvaluator:
     """metrics/fid.py::FIDEvaluator.  Beyond the reference's arguments (keyword-only): inception_ckpt (None: DEFAULT_CKPT, the
     state dict torch-fidelity downloads), allow_random_init (a missing checkpoint is an error unless this is set), data_path (the
-    directory load_celeb walks) and real_stats_path (an .npz the real side's statistics are read from when it exists, written to
-    after the pass otherwise)."""
+    directory load_celeb walks), real_stats_path (an .npz the real side's statistics are read from when it exists, written to
+    after the pass otherwise) and feature_sets (a feature_sets.FeatureSets that receives the features the statistics take; None:
+    nothing changes)."""
 
     def __init__(self, inception_batch_size, device, classifier=None, remove_class=None, filter_fake=True, *, inception_ckpt=None,
-                 allow_random_init=False, data_path="data/examples/celeba_hq_256", real_stats_path=None):
+                 allow_random_init=False, data_path="data/examples/celeba_hq_256", real_stats_path=None, feature_sets=None):
         self.batch_size = int(inception_batch_size)
         if self.batch_size <= 0:
             raise ValueError(f"inception_batch_size={inception_batch_size!r}: a positive batch size is needed")
@@ -289,7 +294,8 @@ class FIDEvaluator:
         else:
             print(f"[siss_amd] allow_random_init: inception checkpoint {ckpt!r} not on disk, RANDOM-INIT Inception-v3: the FID "
                   "figures are NOT comparable with published ones")
-        self.fid_computer = FrechetInceptionDistance(net.to(self.device).eval(), FEATURES, self.device)
+        self.fid_computer = FrechetInceptionDistance(net.to(self.device).eval(), FEATURES, self.device, sink=feature_sets)
+        self.feature_sets = feature_sets
 
     def load_cifar(self, limit=None):
         raise NotImplementedError("FIDEvaluator.load_cifar downloads CIFAR-10 (torchvision.datasets.CIFAR10(download=True)); there is "
@@ -316,6 +322,8 @@ class FIDEvaluator:
                      cov_sum=fc.real_features_cov_sum.cpu().numpy())
 
     def load_celeb(self):
+        if self.feature_sets is not None:
+            return self._load_celeb_with_sets()
         fc, path = self.fid_computer, self.real_stats_path
         if path and os.path.isfile(str(path)):
             self.load_real_stats(path)
@@ -329,6 +337,45 @@ class FIDEvaluator:
             fc.update(batch.to(self.device), real=True)
         if path:
             self.save_real_stats(path)
+
+    def _load_celeb_with_sets(self):
+        """load_celeb with `feature_sets`: the real FEATURES come from its real_features_path when that file was written under this
+        network's weights and these image files (names, sizes, mtimes); otherwise the pass over the images runs and writes it -- also
+        when real_stats_path already supplies the FID's sums, which hold no features (the sums are then left as loaded)."""
+        from .data import CelebAHQ, ToTensor
+        from .feature_sets import FeatureBank, real_fingerprint
+        fc, sets, path = self.fid_computer, self.feature_sets, self.real_stats_path
+        have_stats = bool(path and os.path.isfile(str(path)))
+        if have_stats:
+            self.load_real_stats(path)
+            print(f"Loaded the FID real statistics of {fc.real_features_num_samples} images from {path}")
+        ds = CelebAHQ("all", str(self.data_path), [], ToTensor())
+        fp = real_fingerprint(fc.inception, ds.paths)
+        fpath = sets.real_features_path
+        if fpath and FeatureBank.exists(fpath) and FeatureBank.matches(fpath, fp):
+            sets.adopt_real(FeatureBank.load(fpath, fp, self.device))
+            print(f"[siss_amd] metrics.fid.sets: {len(sets.real)} real feature rows loaded from {fpath}")
+            if have_stats:
+                return
+            fc.sink = None                                   # the pass below feeds the statistics alone
+        else:
+            if fpath and FeatureBank.exists(fpath):
+                print(f"[siss_amd] metrics.fid.sets: the features under {fpath} describe other weights or files: computed again")
+            sets.open_real(len(ds))
+        print("Loading CelebAHQ as FID real examples...")
+        try:
+            for s in range(0, len(ds), self.batch_size):
+                batch = torch.stack([ds[i] for i in range(s, min(s + self.batch_size, len(ds)))]).to(self.device)
+                if have_stats:
+                    sets(fc.inception(batch), True)          # the sums are on file: the features alone
+                else:
+                    fc.update(batch, real=True)
+        finally:
+            loaded, fc.sink = fc.sink is None, sets
+        if path and not have_stats:
+            self.save_real_stats(path)
+        if fpath and not loaded:
+            sets.real.save(fpath, fp)
 
     def add_fake_images(self, fake_imgs):
         if self.remove_class is not None and self.filter_fake:
@@ -352,9 +399,12 @@ class FIDTracker:
     """The FID part of delete_celeb.py's log_metrics (:532-542) for rank 0: at step 0 and every `step_frequency` steps, `num_images`
     samples in batches of `batch_size` -- `sample(n)` returns [n, 3, H, W] images in [0, 1] on the device -- each batch handed to
     add_fake_images as it is produced (the statistics are additive: the result is the reference's all-at-once one, without holding
-    the images); `begin()` / `end()` bracket an evaluation's batches.  One JSON line per evaluation: {global_step, fid, fake_images, real_images, seconds}."""
+    the images); `begin()` / `end()` bracket an evaluation's batches.  One JSON line per evaluation: {global_step, fid, fake_images, real_images, seconds}.
+    `sets` (a feature_sets.FeatureSets; None: the record is exactly the one above) adds the KID and precision / recall / density /
+    coverage of the same features: NOT the reference's protocol, which reports FID only."""
 
-    def __init__(self, evaluator, out_path, sample, step_frequency, num_images, batch_size, begin=None, end=None):
+    def __init__(self, evaluator, out_path, sample, step_frequency, num_images, batch_size, begin=None, end=None, sets=None):
+        self.sets = sets
         self.evaluator, self.out_path, self.sample, self.begin, self.end = evaluator, out_path, sample, begin, end
         self.step_frequency, self.num_images, self.batch_size = int(step_frequency), int(num_images), int(batch_size)
         self.extra = None                                # fields added to every record (pipeline.sampler: name and step count)
@@ -365,6 +415,8 @@ class FIDTracker:
         t0 = time.perf_counter()
         fc = self.evaluator.fid_computer
         fc.reset()
+        if self.sets is not None:
+            self.sets.begin()
         if self.begin is not None:
             self.begin()                                 # (`begin()` runs before an evaluation's first batch)
         try:
@@ -377,5 +429,7 @@ class FIDTracker:
         fid = float(self.evaluator.compute(reset=True))
         rec = {"global_step": int(global_step), "fid": finite_or_none(fid), "fake_images": fake, "real_images": real,
                "seconds": time.perf_counter() - t0, **(self.extra or {})}
+        if self.sets is not None:
+            rec.update(self.sets.evaluate())
         print(f"FID: {fid}")
         return append_jsonl(self.out_path, rec)

@@ -995,6 +995,12 @@ class DeleteCeleb(_DeleteBase):
         data = str(cc.get("data_path") or "data/examples/celeba_hq_256")
         if not (stats and os.path.isfile(str(stats))) and not os.path.isdir(data):
             raise FileNotFoundError(f"metrics.fid.class_cfg.data_path {data!r} (the real images of the FID) is not a directory on disk")
+        if fid.get("sets") is not None:                  # OPT-IN: KID and precision / recall / density / coverage on the same features
+            from . import feature_sets
+            feature_sets.parse_config(hydra_lite._plain(fid.get("sets")), n)
+            if not os.path.isdir(data):
+                raise FileNotFoundError(f"metrics.fid.sets needs metrics.fid.class_cfg.data_path {data!r} (the real images: their features "
+                                        "are kept, and the FID's statistics file holds none) as a directory on disk")
 
     def deletion_metrics(self, unet, sched, forget_image, device):
         """`metrics.fid` (class_cfg, step_frequency, num_imgs_to_generate, batch_size), OPT-IN: None when not configured.  The
@@ -1002,14 +1008,20 @@ class DeleteCeleb(_DeleteBase):
         num_imgs_to_generate samples (`pipeline.num_inference_steps` steps, batches of batch_size, a generator of its own seeded from
         random_seed) go through add_fake_images batch by batch (each batch comes back from Evaluator.sample_images as a host array and
         is copied to the device again: one round trip per batch, negligible next to its sampling), and {global_step, fid, fake_images, real_images, seconds} is
-        appended to fid_rank0.jsonl (fid.FIDTracker)."""
+        appended to fid_rank0.jsonl (fid.FIDTracker).  `metrics.fid.sets` (absent: nothing changes) keeps the features and adds the KID and
+        precision / recall / density / coverage to the record (feature_sets.FeatureSets; NOT the reference's protocol)."""
         cfg = self.cfg
         fid = (cfg.get("metrics") or {}).get("fid")
         if not fid:
             return None
         from .fid import FIDTracker
         from .sampler import Evaluator
-        evaluator = hydra_lite.instantiate(fid.class_cfg, device=device)
+        sets = None
+        if fid.get("sets") is not None:                  # OPT-IN (`+metrics.fid.sets={kid:{...},prdc:{...}}`); refused in check_metrics
+            from . import feature_sets
+            sets = feature_sets.FeatureSets(feature_sets.parse_config(hydra_lite._plain(fid.get("sets")), int(fid.num_imgs_to_generate)),
+                                            int(fid.num_imgs_to_generate), device)
+        evaluator = hydra_lite.instantiate(fid.class_cfg, device=device, **({} if sets is None else {"feature_sets": sets}))
         evaluator.load_celeb()
         steps = _inference_steps(cfg)
         gen = torch.Generator(device=device).manual_seed(self.seed())
@@ -1029,7 +1041,7 @@ class DeleteCeleb(_DeleteBase):
             return torch.from_numpy(imgs).permute(0, 3, 1, 2).to(device)
 
         tracker = FIDTracker(evaluator, os.path.join(cfg.output_dir, "fid_rank0.jsonl"), sample, fid.step_frequency,
-                             fid.num_imgs_to_generate, fid.batch_size, begin=begin, end=end)
+                             fid.num_imgs_to_generate, fid.batch_size, begin=begin, end=end, sets=sets)
         tracker.extra = _sampler_fields(cfg, solver)
         return tracker
 
