@@ -80,7 +80,8 @@ F32_SAME = {"siss_zero_ranges", "siss_upsample_phase_wgrad_fold", "siss_timestep
             "siss_grad_norms_scale_surgery", "siss_recombine_clip_adamw_surgery",
             "siss_ssd_ratio", "siss_ssd_dampen",
             "siss_sscd_topk", "siss_sscd_count_above", "siss_sscd_fill_above",
-            "siss_feat_sqnorm", "siss_feat_knn_radius", "siss_feat_ball_stats", "siss_kid_sums"}
+            "siss_feat_sqnorm", "siss_feat_knn_radius", "siss_feat_ball_stats", "siss_kid_sums",
+            "siss_jl_project"}
 for _b, _f in F32_ENTRY.items():          # the header's promise "same argument lists", checked once instead of assumed
     if SIGNATURES[_b] != SIGNATURES[_f]:
         raise TypeError(f"{_f} does not have the argument types of {_b} in {HEADER}")
