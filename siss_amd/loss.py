@@ -96,6 +96,28 @@ def mse_bwd_seed(pred, target, scale, want_loss=False, partials=None):
     return c, loss, sums
 
 
+def teacher_seed(pred, noise, teach, B, cfg, scale, cot=None, sums=None, partials=None):
+    """The teacher-target objective's post-kernel (csrc/teacher.hip siss_teacher_seed; siss_amd/teacher.py, NOT the reference's): pred
+    [R, ...] f32 the student's rows ([keep B | forget B], or [forget B] with cfg.keep == "none"), teach [Rt, ...] f32 the teacher's
+    rows (teacher.row_layout), noise [B, ...] f32 / bf16; cot = 2 * scale * (pred - y) into `cot`, returns the per-row sums of
+    (pred - y)^2 [R] f32.  cot / sums / partials: the caller's persistent buffers (allocated here when None)."""
+    from .teacher import FORGETS, KEEPS
+    assert pred.dtype == torch.float32 and pred.is_contiguous() and teach.dtype == torch.float32 and teach.is_contiguous()
+    R, chw, dev = pred.shape[0], pred[0].numel(), pred.device
+    assert teach[0].numel() == chw and R == (B if cfg.keep == "none" else 2 * B)
+    noise = noise.contiguous()
+    assert noise.dtype in (torch.float32, torch.bfloat16) and noise.shape[0] == B and noise[0].numel() == chw
+    if cot is None:
+        cot = torch.empty_like(pred)
+    if sums is None:
+        sums = torch.empty(R, dtype=torch.float32, device=dev)
+    if partials is None:
+        partials = torch.empty(lib.query("siss_teacher_partials_words", R, chw), dtype=torch.float64, device=dev)
+    lib.call("siss_teacher_seed", pred, noise, int(noise.dtype == torch.bfloat16), teach, teach.shape[0], B, chw,
+             KEEPS.index(cfg.keep), FORGETS.index(cfg.forget), float(cfg.guidance), float(scale), cot, sums, partials)
+    return sums
+
+
 # --------------------------------------------------------------------------------------------
 # Drop-in class surface of the reference (losses/ddpm_deletion_loss.py:3-122)
 # --------------------------------------------------------------------------------------------

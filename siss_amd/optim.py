@@ -35,7 +35,7 @@ class FlatAdamW:
         self.last_grad = None
 
     def launch(self, grads, *, scaling_norm=None, eta=None, inf_guard=False, want_grad=False, ranges=None, mask=None, ewc=None,
-               surgery=None):
+               surgery=None, fixed_weight=None):
         """Enqueue both passes (no host sync).  grads: [2, P] f32 = (g_x, g_a).  ranges: (device table, stretches, granules) of a
         trainable subset (siss_amd.trainable.Subset.table) -- norms, scaling factor, clip and update over the listed stretches
         only, every other byte of p / m / v / shadow untouched; the caller keeps the table alive (a captured step holds its address).
@@ -46,9 +46,15 @@ class FlatAdamW:
         keeps the anchor alive likewise.
         surgery: a siss_amd.surgery.Surgery over this buffer -- both passes are those of csrc/surgery.hip: per group of the buffer the
         conflicting component of the pair is projected out before the norm fix (not with eta: EraseDiff's mode is refused).  Not with
-        the other three; the caller keeps the object alive likewise."""
+        the other three; the caller keeps the object alive likewise.
+        fixed_weight: a positive float w -- the teacher-target objective's plain weighted sum g = clip (g_x + w g_a): pass 1 is
+        siss_grad_norms_weighted (csrc/teacher.hip: the scaling factor fixed at s = -w; scaling_norm and inf_guard are not read), pass 2
+        the plain one.  Not with ranges / mask / ewc / surgery / eta: their pass 1 has no weighted form."""
         n = self.p.numel()
         assert grads.dtype == torch.float32 and grads.shape == (2, n) and grads.is_contiguous()
+        if fixed_weight is not None:
+            return self._launch_weighted(grads, fixed_weight, want_grad, {"surgery=": surgery, "ewc=": ewc, "mask=": mask,
+                                                                          "ranges=": ranges, "eta=": eta})
         mode, knob = _mode_knob(scaling_norm, eta, inf_guard)
         exclusive("FlatAdamW.launch", {"surgery=": surgery, "ranges=": ranges, "mask=": mask, "ewc=": ewc})
         if surgery is not None:
@@ -85,6 +91,22 @@ class FlatAdamW:
                  self.partials, *tail, self.scalars)
         lib.call(two, grads[0], grads[1], self.p, self.m, self.v, self.shadow, self.last_grad if want_grad else None, n, *sel,
                  self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.scalars)
+
+    def _launch_weighted(self, grads, weight, want_grad, others):
+        """Pass 1 of csrc/teacher.hip (s = -weight), then the plain pass 2."""
+        from .teacher import fixed_weight_exclusive, require_kernels
+        fixed_weight_exclusive("FlatAdamW.launch", others)
+        weight = float(weight)
+        if not (0.0 < weight < float("inf")):
+            raise ValueError(f"FlatAdamW.launch(fixed_weight={weight!r}): a positive finite weight is needed")
+        require_kernels()
+        n = self.p.numel()
+        if want_grad and (self.last_grad is None):
+            self.last_grad = torch.empty_like(self.p)
+        lib.call("siss_grad_norms_weighted", grads[0], grads[1], n, weight, self.max_grad_norm, self.betas[0], self.betas[1],
+                 self.partials, self.scalars)
+        lib.call("siss_recombine_clip_adamw", grads[0], grads[1], self.p, self.m, self.v, self.shadow,
+                 self.last_grad if want_grad else None, n, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.scalars)
 
     def _launch_surgery(self, grads, sg, mode, knob, want_grad):
         """Both passes of csrc/surgery.hip on the plan and the slabs `sg` owns."""
@@ -137,13 +159,16 @@ class FlatAdamW:
         self._ewc_checked = ewc
 
     def launch_sharded(self, gx_shard, ga_shard, lo, hi, group, *, scaling_norm=None, eta=None, inf_guard=False, ranges=None, mask=None,
-                       ewc=None, surgery=None):
+                       ewc=None, surgery=None, fixed_weight=None):
         """The same update on THIS rank's parameter shard [lo, hi) (sharded data-parallel exchange):
         gx_shard / ga_shard are the rank-summed gradients of the shard.  The three norm sums are all-reduced (24 bytes),
         so every rank forms the same scaling factor and clip coefficient as the replicated update; p / m / v / shadow are
         touched on [lo, hi) only -- the caller all-gathers the parameters afterwards."""
         import ctypes
         import torch.distributed as dist
+        if fixed_weight is not None:
+            raise NotImplementedError("FlatAdamW.launch_sharded: fixed_weight= and a parameter shard do not combine -- the teacher "
+                                      "target's weighted pass 1 has no sharded form (use the all-reduce)")
         exclusive("FlatAdamW.launch_sharded", {"surgery=": surgery, "ranges=": ranges, "mask=": mask, "ewc=": ewc, SHARD: True},
                   NotImplementedError)
         n = hi - lo

@@ -22,7 +22,7 @@ import torch
 from . import lib
 from . import dp
 from .dp import EXCHANGES, allreduce_flat_grads, allreduce_pieces, can_shard
-from .loss import loss_bwd_seed, mixture_fwd, mse_bwd_seed
+from .loss import loss_bwd_seed, mixture_fwd, mse_bwd_seed, teacher_seed
 from .optim import FlatAdamW
 from .unet import UNetEngine
 from .variants import VARIANTS, exchange_refusal, exclusive, same_layout
@@ -33,17 +33,19 @@ ERASEDIFF = "erasediff"
 NEG_GRAD = "simple_neg_del"
 NAIVE = "naive_del"
 SUBSCORE = "subscore_bernoulli"
+TEACHER = "teacher_target"          # opt-in, not the reference's: siss_amd/teacher.py
 
 
 class SISSStepper:
     _warned_fp32 = False
     wgrad_overwrite = True          # (A/B switch; see UNetEngine.wgrad_overwrite)
+    teacher = teacher_cfg = None    # the frozen teacher of loss_fn="teacher_target" and its parsed key (siss_amd/teacher.py)
 
     def __init__(self, engine: UNetEngine, alphas_cumprod, *, lr, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=1e-2, scaling_norm=None, eta=None, lambd=0.5, train_batch_size,
                  grad_accum=1, max_grad_norm=1.0, loss_fn=SISS, inf_guard=False, process_group=None,
                  mixed_precision="bf16", superfactor=1.0, superfactor_decay=None, trainable=None, lora=None, saliency=None,
-                 ewc=None, surgery=None):
+                 ewc=None, surgery=None, teacher=None, teacher_cfg=None):
         """trainable: None (every parameter: the reference's protocol), an iterable of parameter names, or "requires_grad" (the flags
         of the parameters of the UNet2DModel / UNet2DConditionModel that owns the engine).  With a subset the norms, the scaling
         factor, the clip and the AdamW update run over the trainable tensors only; the rest keep every byte.  The selection (the
@@ -70,10 +72,17 @@ class SISSStepper:
         surgery: None, or a siss_amd.surgery.Surgery over this engine (opt-in, not the reference's protocol): once per optimizer step,
         after the accumulation and the data-parallel exchange, the conflicting component of the (keep, forget) gradient pair is
         projected out per group of the buffer before the norm fix (csrc/surgery.hip); for the two-set losses with the norm fix only;
-        exclusive with the other four.  Its plan and slabs live as long as the stepper: a captured step holds their addresses."""
+        exclusive with the other four.  Its plan and slabs live as long as the stepper: a captured step holds their addresses.
+
+        teacher, teacher_cfg: a siss_amd.teacher.Teacher beside this engine and a TeacherConfig (None: its defaults), with
+        loss_fn="teacher_target" (opt-in, not the reference's protocol; each without the other is refused): the rows are regressed onto
+        targets built from the frozen teacher's predictions (csrc/teacher.hip) and the update is the plain weighted sum g_x + weight g_a.
+        Combines with lora=; refused with the other four, whose pass 1 has no weighted form."""
         self.e = engine
         self.lora = lora
         self.saliency = self.ewc = self.surgery = None
+        self.teacher, self.teacher_cfg = self._teacher_args(loss_fn, teacher, teacher_cfg, {
+            "surgery=": surgery, "ewc=": ewc, "saliency=": saliency, "trainable=": trainable})
         exclusive("SISSStepper", {"surgery=": surgery, "ewc=": ewc, "saliency=": saliency, "lora=": lora, "trainable=": trainable})
         if lora is not None:
             if lora.engine is not engine:
@@ -135,6 +144,9 @@ class SISSStepper:
         self.exchange = os.environ.get("SISS_DP_EXCHANGE", "allreduce")      # serial mode: "allreduce" | "sharded"
         self._state_shard = None                # (lo, hi) while AdamW's moments are current on this rank's shard only
         assert self.exchange in EXCHANGES
+        if self.teacher is not None and self.exchange == "sharded":
+            print("[siss_amd] teacher target: the weighted pass 1 has no sharded form; using the all-reduce")
+            self.exchange = "allreduce"
         self._fit_exchange(self.dp_on and engine.ps.split < engine.ps.total and os.environ.get("SISS_DP_OVERLAP", "1") != "0")
         if saliency is not None:
             self.set_saliency(saliency)
@@ -157,6 +169,29 @@ class SISSStepper:
                 self.exchange = "allreduce"
         self.set_overlap(overlap)
 
+    def _teacher_args(self, loss_fn, teacher, teacher_cfg, others):
+        """(teacher, its config) of SISSStepper(loss_fn="teacher_target", teacher=...), or (None, None): each of the two without the
+        other, a teacher over another architecture or device, a missing embedding and the four variants without a weighted pass 1
+        are refused here, before any launch."""
+        if (loss_fn == TEACHER) != (teacher is not None):
+            raise ValueError("SISSStepper: loss_fn='teacher_target' needs teacher= (a siss_amd.teacher.Teacher)" if teacher is None else
+                             f"SISSStepper: teacher= is set but loss_fn={loss_fn!r}: the teacher serves loss_fn='teacher_target' only")
+        if teacher is None:
+            if teacher_cfg is not None:
+                raise ValueError("SISSStepper: teacher_cfg= without teacher=")
+            return None, None
+        from .teacher import parse_teacher, require_kernels, teacher_exclusive
+        teacher_exclusive("SISSStepper", "teacher=", teacher, others)
+        require_kernels()
+        cfg = teacher_cfg if teacher_cfg is not None else parse_teacher({})
+        if not same_layout(teacher, self.e) or teacher.engine.adt != self.e.adt:
+            raise ValueError("SISSStepper(teacher=...): the teacher was built over another engine's parameter layout or dtype")
+        if teacher.engine.ps.flat.device != self.e.ps.flat.device:
+            raise ValueError("SISSStepper(teacher=...): the teacher is on another device than the engine")
+        teacher.check(cfg)
+        teacher.cfg = cfg
+        return teacher, cfg
+
     def _adopt(self, name, obj, tensor, require_kernels, launch_kw, ready=None):
         """set_saliency / set_ewc / set_surgery: a `full` stepper moves to variant `name` (another object of the stepper's own variant
         replaces the first).  tensor: a device tensor of obj (per float, or the surgery's plan), which must live on the engine's
@@ -164,6 +199,9 @@ class SISSStepper:
         present = {"surgery=": getattr(self, "surgery", None), "ewc=": self.ewc, "saliency=": self.saliency, "lora=": self.lora,
                    "trainable=": self.subset}
         del present[name + "="]
+        if self.teacher is not None:
+            from .teacher import teacher_exclusive
+            teacher_exclusive(f"SISSStepper.set_{name}", "teacher=", self.teacher, {name + "=": obj})
         exclusive(f"SISSStepper.set_{name}", {name + "=": obj, **present})
         require_kernels()
         what = VARIANTS[name].what
@@ -456,6 +494,29 @@ class SISSStepper:
                                                                    superfactor=self.superfactor)
             if not keep and self.superfactor_decay is not None:
                 self.superfactor *= self.superfactor_decay         # applied after the loss call (delete_celeb.py:658-662)
+        elif self.loss_fn == TEACHER:
+            # NOT the reference's: keep / forget rows as the NO_IS branch makes them, regressed onto targets the frozen teacher supplies
+            tc, th = self.teacher_cfg, self.teacher
+            keep_none = tc.keep == "none"
+            mf = mixture_fwd(x0, a0, noise, t, torch.zeros(B, device=e.device), self.ac, self.gamma_tab,
+                             self.sigma_tab, 0.5)  # u=0 <= .5: forget rows -> q_sample(a0)
+            if keep_none:
+                m, xin, tin, cond2 = None, mf.x_mix, t, cond
+            else:
+                m = mixture_fwd(x0, a0, noise, t, torch.ones(B, device=e.device), self.ac, self.gamma_tab,
+                                self.sigma_tab, 0.0)   # u=1 > 0: keep rows -> q_sample(x0)
+                xin, tin = torch.cat([m.x_mix, mf.x_mix], 0), torch.cat([t, t], 0)
+                cond2 = {k: torch.cat([v, v], 0) for k, v in cond.items()}
+            pred = e.forward(xin, tin, **cond2)
+            teach = th.predict(tc, None if m is None else m.x_mix, mf.x_mix, t, cond)      # forward only, constants
+            # keep: none -- the forget rows alone, ONE set, the weight folded into the scale; the second set stays zero (zero_grad
+            # above) and g = g_x through the inf-guarded s = 0, as the NegGrad branch runs
+            sums = teacher_seed(pred, noise, teach, B, tc, scale * tc.weight if keep_none else scale,
+                                cot=e._buf("cot", tuple(pred.shape)), sums=e._buf("teacher_sums", (pred.shape[0],)),
+                                partials=self._teacher_partials(pred.shape[0], pred[0].numel()))
+            e.backward(e._buf("cot", tuple(pred.shape)), nsets=1 if keep_none else 2)
+            chw = pred[0].numel()
+            self.last = dict(loss_a=sums / chw) if keep_none else dict(loss_x=sums[:B] / chw, loss_a=sums[B:] / chw)
         elif self.loss_fn == SUBSCORE:
             # ddpm_deletion_loss.py:99-122: Bernoulli keep/forget rows against the plain noise target; the row
             # selection loss[mask] / (1 - lambd), loss[~mask] is a per-sample weight on the shared forward
@@ -484,6 +545,9 @@ class SISSStepper:
 
     def _partials(self, B, chw):
         return self.e._buf("loss_partials", (lib.query("siss_loss_partials_words", B, chw),), torch.float64)
+
+    def _teacher_partials(self, R, chw):
+        return self.e._buf("teacher_partials", (lib.query("siss_teacher_partials_words", R, chw),), torch.float64)
 
     def _early_allreduce(self):
         if self._micro + 1 != self.ga:          # only the sync micro-step communicates
@@ -536,15 +600,21 @@ class SISSStepper:
 
     def _update_kw(self):
         """The recombination of the step as FlatAdamW's keywords: the single-set objectives run the inf-guarded norm fix with s = 0."""
-        single = self.loss_fn in (NEG_GRAD, NAIVE)
+        if self.teacher is not None and self.teacher_cfg.keep != "none":
+            return dict(fixed_weight=self.teacher_cfg.weight)          # g = g_x + weight g_a (csrc/teacher.hip: s = -weight)
+        single = self._single_set()
         return dict(scaling_norm=self.scaling_norm if not single else 1.0, eta=self.eta if self.loss_fn == ERASEDIFF else None,
                     inf_guard=self.inf_guard or single)
+
+    def _single_set(self):
+        """The objectives with ONE gradient set (the second stays zero): NegGrad, naive, and the teacher target with keep: none."""
+        return self.loss_fn in (NEG_GRAD, NAIVE) or (self.teacher is not None and self.teacher_cfg.keep == "none")
 
     def _lora_update(self):
         """The update of a LoRA step: project -> (all-reduce of the adapter gradients) -> norms / recombine / clip / AdamW on the
         adapters -> merge -> operand copies.  Same stream, persistent tables, no host sync, no allocation: capturable like the rest."""
         lora = self.lora
-        single = self.loss_fn in (NEG_GRAD, NAIVE)
+        single = self._single_set()
         lora.project(nsets=1 if single else 2)
         if self.dp_on:
             allreduce_flat_grads(lora.g, self.pg)       # (the projection is linear: the sum of the ranks' dW projected = this sum)
@@ -593,7 +663,8 @@ class SISSStepper:
         variant's own fields."""
         params, tensors = self.trainable_counts()
         active = self._active()
-        return dict(trainable_params=params, trainable_tensors=tensors, **(active.log_fields() if active is not None else {}))
+        teacher = self.teacher.log_fields(self.teacher_cfg, self.train_batch_size) if self.teacher is not None else {}
+        return dict(trainable_params=params, trainable_tensors=tensors, **(active.log_fields() if active is not None else {}), **teacher)
 
     def trainable_counts(self):
         """(trainable_params, trainable_tensors) of every log line: the parameters the optimizer updates."""

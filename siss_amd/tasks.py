@@ -293,6 +293,10 @@ class _DeleteBase(Task):
         if cfg.get("mixed_precision") not in (None, "null", "no", "bf16"):
             raise NotImplementedError(f"mixed_precision={cfg.get('mixed_precision')!r}: only null / bf16 (no loss scaler)")
         _pipeline_sampler(cfg)                                   # pipeline.sampler: a bad name / option is refused before the first step
+        # deletion.teacher / loss_fn=teacher_target: each without the other, a task whose forget target is not defined through prompts, a
+        # malformed mapping, an unknown field or value, the key together with deletion.trainable / saliency / ewc / surgery, a path
+        # without unet/ and (DeleteSD) an anchor prompt that cannot be embedded are settled here, before the other keys speak
+        self.teacher_config()
         # deletion.ssd: a malformed mapping, an unknown field, both or neither of alpha / fraction, a value out of range, a targets entry
         # that matches no parameter of the configured UNet and the key together with deletion.lora / deletion.trainable (said first: what
         # those two select does not matter then) are settled here
@@ -321,6 +325,49 @@ class _DeleteBase(Task):
         # deletion.surgery: a malformed mapping, an unknown field or value, the key together with deletion.trainable / deletion.lora /
         # deletion.saliency / deletion.ewc, and a loss without a gradient pair under the norm fix are settled here too
         self.surgery_config()
+
+    # -- deletion.teacher: null | {forget, keep, guidance, weight, anchor_prompt, path} (OPT-IN; siss_amd/teacher.py) -----------------------
+    teacher_refusal = "both forget targets (esd, anchor) are defined through prompts, and this task's UNet takes none"
+
+    def teacher_config(self):
+        """The parsed deletion.teacher (siss_amd.teacher.TeacherConfig) of a loss_fn=teacher_target run, or None (neither is set: today's
+        run).  The task says in `teacher_refusal` why it does not take the key (None: it does -- delete_sd)."""
+        from .teacher import KEY, LOSS, check_path, parse_teacher
+        d = self.cfg.get("deletion") or {}
+        value, loss = d.get("teacher"), d.get("loss_fn")
+        if value is None and loss != LOSS:
+            return None
+        if self.teacher_refusal is not None:
+            raise NotImplementedError(f"{KEY} / deletion.loss_fn={LOSS}: {self.teacher_refusal} (the teacher target belongs to delete_sd)")
+        if value is None:
+            raise ValueError(f"deletion.loss_fn={LOSS} needs the key {KEY} (e.g. +{KEY}={{forget:esd,keep:teacher}})")
+        if loss != LOSS:
+            raise ValueError(f"{KEY} is set but deletion.loss_fn={loss!r}: the teacher serves deletion.loss_fn={LOSS} only (set it, or "
+                             "leave the key out)")
+        tc = parse_teacher(value, trainable=d.get("trainable"), saliency=d.get("saliency"), ewc=d.get("ewc"), surgery=d.get("surgery"))
+        if tc.path is not None:
+            check_path(tc.path)
+        return tc
+
+    def build_teacher(self, eng, device, rank=0):
+        """(Teacher, TeacherConfig) of a loss_fn=teacher_target run -- built from the weights the run loaded, before anything touches them
+        -- or (None, None)."""
+        tc = self.teacher_config()
+        if tc is None:
+            return None, None
+        from .teacher import Teacher
+        teacher = Teacher.from_path(eng, tc.path) if tc.path is not None else Teacher(eng)
+        teacher.set_embeddings(**self.teacher_embeddings(tc, device))
+        teacher.cfg = tc
+        if rank == 0:
+            os.makedirs(self.cfg.output_dir, exist_ok=True)
+            teacher.save_config(self.cfg.output_dir, tc)
+            print(f"[siss_amd] deletion.teacher: forget {tc.forget}, keep {tc.keep}, guidance {tc.guidance:g}, weight {tc.weight:g}; a frozen "
+                  f"copy of the UNet from {teacher.source}, {teacher.nbytes} bytes")
+        return teacher, tc
+
+    def teacher_embeddings(self, tc, device):
+        raise NotImplementedError(self.teacher_refusal)
 
     # -- deletion.surgery: null | {mode, granularity} (OPT-IN; siss_amd/surgery.py) ------------------------------------------------------
     def surgery_config(self):
@@ -846,6 +893,7 @@ class _DeleteBase(Task):
         self.check_metrics()
         unet = self.load_unet(device)
         eng = unet.engine
+        teacher, teacher_cfg = self.build_teacher(eng, device, rank)     # (the weights the run loaded: before deletion.ssd, before a step)
         sched = self.load_scheduler()
         lr, betas, eps, wd = self.optimizer_args()
         from .scheduler import lr_multiplier
@@ -864,7 +912,8 @@ class _DeleteBase(Task):
             loss_fn=d.loss_fn, inf_guard=self.inf_guard, process_group=pg,
             mixed_precision=cfg.get("mixed_precision"),
             superfactor=float((d.loss_params or {}).get("superfactor", 1.0)),
-            superfactor_decay=d.get("superfactor_decay"), trainable=self.trainable_names(unet), lora=self.lora_state(unet))
+            superfactor_decay=d.get("superfactor_decay"), trainable=self.trainable_names(unet), lora=self.lora_state(unet),
+            teacher=teacher, teacher_cfg=teacher_cfg)
         lora = stepper.lora
         shape = (unet.config.in_channels, unet.config.sample_size, unet.config.sample_size)
         ds_all, ds_del = self.datasets(shape)
@@ -1246,6 +1295,34 @@ class DeleteSD(_DeleteBase):
         return m
 
     unet_engine = "siss_amd.unet_cond.UNetCondEngine"
+    teacher_refusal = None      # deletion.teacher is this task's: the prompts the two forget targets need are here
+
+    def teacher_config(self):
+        tc = super().teacher_config()
+        if tc is not None and tc.forget == "anchor":
+            self._check_embeddable(tc.anchor_prompt, "deletion.teacher.anchor_prompt")
+        path = str(self.cfg.get("pretrained_model_name_or_path") or "")
+        if tc is not None and tc.forget == "esd" and not (os.path.isdir(os.path.join(path, "text_encoder")) or self.cfg.get("allow_synthetic")):
+            raise FileNotFoundError("deletion.teacher (forget: esd) needs the empty prompt's embedding: no text_encoder/ in the checkpoint "
+                                    "directory (pass allow_synthetic=true for a synthetic one)")
+        return tc
+
+    def _check_embeddable(self, p, key):
+        """_prompt_embedding's rules, from the disk alone (check_supported runs before anything is loaded)."""
+        cfg = self.cfg
+        path = str(cfg.get("pretrained_model_name_or_path") or "")
+        if (str(p).endswith(".pt") and os.path.exists(str(p))) or cfg.get("allow_synthetic") or all(
+                os.path.isdir(os.path.join(path, sub)) for sub in ("text_encoder", "tokenizer")):
+            return
+        raise FileNotFoundError(f"{key}={p!r} cannot be embedded: it is neither a .pt embedding / token file on disk nor a prompt with a "
+                                "text_encoder/ + tokenizer/ on disk; pass allow_synthetic=true for a synthetic embedding")
+
+    def teacher_embeddings(self, tc, device):
+        """What the teacher's extra rows are conditioned on: the empty prompt (esd) or the anchor prompt (anchor; its synthetic stand-in
+        is a seeded embedding of its own, not the prompt's)."""
+        if tc.forget == "esd":
+            return dict(empty=self._empty_prompt_embedding(device, "deletion.teacher (forget: esd)"))
+        return dict(anchor=self._prompt_embedding(tc.anchor_prompt, device, synthetic_seed=2))
 
     def unet_checkpoint(self):
         path = self.cfg.get("pretrained_model_name_or_path")
@@ -1498,9 +1575,10 @@ class DeleteSD(_DeleteBase):
         return (SyntheticImages(4096, shape, seed=1, scale=self.VAE_SCALE, normal=True),
                 SyntheticImages(1, shape, seed=2, scale=self.VAE_SCALE, normal=True))
 
-    def _prompt_embedding(self, p, device):
+    def _prompt_embedding(self, p, device, synthetic_seed=0):
         """[1, L, X] f32 embedding of one validation prompt: a .pt embedding / token-id file, a string through text_encoder/ +
-        tokenizer/, or (allow_synthetic) a seeded synthetic embedding."""
+        tokenizer/, or (allow_synthetic) a seeded synthetic embedding (seed() + synthetic_seed: 0 the prompt, 1 the empty prompt, 2 the
+        teacher's anchor)."""
         cfg = self.cfg
         X = int((cfg.get("unet") or {}).get("cross_attention_dim", 768))
         if p and str(p).endswith(".pt") and os.path.exists(str(p)):
@@ -1516,7 +1594,7 @@ class DeleteSD(_DeleteBase):
                       return_tensors="pt").input_ids
             e = self.text_encoder(ids)[0].float()
         elif cfg.get("allow_synthetic"):
-            e = torch.randn(1, 77, X, generator=torch.Generator().manual_seed(self.seed())).to(device)
+            e = torch.randn(1, 77, X, generator=torch.Generator().manual_seed(self.seed() + synthetic_seed)).to(device)
         else:
             raise FileNotFoundError("validation_prompts[0] is neither a .pt embedding / token file on disk nor a prompt with a "
                                     "text_encoder/ + tokenizer/ on disk; pass allow_synthetic=true for a synthetic embedding")
@@ -1529,12 +1607,30 @@ class DeleteSD(_DeleteBase):
 
     pipeline = None             # the validation pipeline (SDSampler), built at the first evaluation
 
+    def _empty_prompt_embedding(self, device, what):
+        """[1, L, X] f32 embedding of the empty prompt: the text encoder's output for it, or (allow_synthetic) a seeded synthetic one --
+        the negative prompt of the validation pipeline and the unconditional rows of the teacher's esd target."""
+        from .sd_sampler import uncond_ids
+        cfg = self.cfg
+        path = str(cfg.get("pretrained_model_name_or_path") or "")
+        if self.text_encoder is not None:
+            ids = uncond_ids(path)
+            if int(ids.max()) >= self.text_encoder.tok.shape[0]:      # (checked here: a bad id would fault the gather on the device)
+                raise ValueError(f"empty-prompt token ids reach {int(ids.max())}, beyond the text encoder's vocabulary of "
+                                 f"{self.text_encoder.tok.shape[0]}: put the checkpoint's tokenizer/ beside it")
+            return self.text_encoder(ids)[0].float()
+        if cfg.get("allow_synthetic"):
+            X = int((cfg.get("unet") or {}).get("cross_attention_dim", 768))
+            return torch.randn(1, 77, X, generator=torch.Generator().manual_seed(self.seed() + 1)).to(device)
+        raise FileNotFoundError(f"{what} needs the empty prompt's embedding: no text_encoder/ in the checkpoint directory "
+                                "(pass allow_synthetic=true for a synthetic one)")
+
     def _validation_pipeline(self, unet, device):
         """The SD pipeline of log_validation (delete_sd.py:185-204), built at the first evaluation: the VAE decoder is read from
         vae/ only now (no vae/ on disk: noise norms without images); the negative prompt is the text encoder's output for the
         empty prompt, or a seeded synthetic embedding where the prompts are synthetic too."""
         from .scheduler import DDIMScheduler
-        from .sd_sampler import SDSampler, uncond_ids
+        from .sd_sampler import SDSampler
         cfg = self.cfg
         path = str(cfg.get("pretrained_model_name_or_path") or "")
         vae = None
@@ -1543,18 +1639,7 @@ class DeleteSD(_DeleteBase):
             vae = VAEDecoder.from_pretrained(path, "vae", device)
         else:
             print(f"[siss_amd] evaluation: no vae/ under {path!r}: noise norms only, no validation images")
-        if self.text_encoder is not None:
-            ids = uncond_ids(path)
-            if int(ids.max()) >= self.text_encoder.tok.shape[0]:      # (checked here: a bad id would fault the gather on the device)
-                raise ValueError(f"empty-prompt token ids reach {int(ids.max())}, beyond the text encoder's vocabulary of "
-                                 f"{self.text_encoder.tok.shape[0]}: put the checkpoint's tokenizer/ beside it")
-            neg = self.text_encoder(ids)[0].float()
-        elif cfg.get("allow_synthetic"):
-            X = int((cfg.get("unet") or {}).get("cross_attention_dim", 768))
-            neg = torch.randn(1, 77, X, generator=torch.Generator().manual_seed(self.seed() + 1)).to(device)
-        else:
-            raise FileNotFoundError("evaluation needs the empty prompt's embedding: no text_encoder/ in the checkpoint directory "
-                                    "(pass allow_synthetic=true for a synthetic one)")
+        neg = self._empty_prompt_embedding(device, "evaluation")
         self.pipeline = SDSampler(unet, vae=vae, scheduler=self._sd_solver() or DDIMScheduler.from_pretrained(path or None),
                                   vae_encoder=self.vae)
         self._negative_embeds = neg
@@ -1716,6 +1801,9 @@ class TrainUnconditional(Task):
         if (cfg.get("deletion") or {}).get("surgery") is not None:
             raise NotImplementedError("deletion.surgery: gradient surgery belongs to the unlearning tasks (delete_celeb / delete_tshirt "
                                       "/ delete_sd); the pre-training task has one gradient set and nothing to project")
+        if (cfg.get("deletion") or {}).get("teacher") is not None:
+            raise NotImplementedError("deletion.teacher: the teacher target belongs to the unlearning task delete_sd; the pre-training "
+                                      "task has no forget set and no pretrained network to take targets from")
         if (cfg.get("deletion") or {}).get("ssd") is not None:
             raise NotImplementedError("deletion.ssd: Selective Synaptic Dampening belongs to the unlearning tasks (delete_celeb / "
                                       "delete_tshirt / delete_sd); the pre-training task has no forget set to dampen for")

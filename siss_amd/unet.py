@@ -231,8 +231,10 @@ class UNetEngine:
     # What it buys is measured by tools/bench_trainable.py (docs/experiments.md).
     skip_frozen_wgrad = True
 
-    def __init__(self, cfg: UNet2DConfig, device="cuda", dtype=torch.bfloat16, f32_fused=False):
-        """dtype = torch.float32: the f32 PARITY MODE (`mixed_precision: null` of the reference's YAMLs; csrc/f32_path.hip) -- every
+    def __init__(self, cfg: UNet2DConfig, device="cuda", dtype=torch.bfloat16, f32_fused=False, grad_sets=2):
+        """grad_sets: the gradient sets ParamStore.allocate makes (2: the dual backward's g_x, g_a); 0 for an engine that only ever runs
+        forward -- the frozen teacher of siss_amd/teacher.py -- which then holds the master, its operand copy and no gradient buffer.
+        dtype = torch.float32: the f32 PARITY MODE (`mixed_precision: null` of the reference's YAMLs; csrc/f32_path.hip) -- every
         activation and operand f32, every product on the f32 MFMA, the same engine code; the fused bf16-only forms (persistent
         3x3 kernel and what rides in it, depth-to-space epilogue, grouped / side-stream wgrads, slab GroupNorm) are off.  An
         instrument (1/16 of the bf16 MFMA rate at best, and simple kernels): it pins the network to the fp32 oracle at 1e-4."""
@@ -257,7 +259,7 @@ class UNetEngine:
         self.ps = ParamStore()
         self._declare_params()
         self.ps.relayout(self._grads_final_early)
-        self.ps.allocate(self.device, f32=self.f32)
+        self.ps.allocate(self.device, nsets=int(grad_sets), f32=self.f32)
         self._build_temb_tables()
         self._init_runtime_state()
 

@@ -46,8 +46,8 @@ class UNetCondEngine(UNetEngine):
     fuse_geglu_fwd = True      # GEGLU forward in the epilogue of its input projection (round 6)
     fuse_kv = True             # cross-attention: to_k / to_v as one [2C][Ckv] projection and one weight-gradient product (round 6)
 
-    def __init__(self, cfg: UNet2DConditionConfig, device="cuda", dtype=torch.bfloat16):
-        super().__init__(cfg, device, dtype=dtype)
+    def __init__(self, cfg: UNet2DConditionConfig, device="cuda", dtype=torch.bfloat16, grad_sets=2):
+        super().__init__(cfg, device, dtype=dtype, grad_sets=grad_sets)
         self.ctx = None
         self._ctx_slabs, self._ctx_site = None, 0          # context_vjp(): the per-site f32 slabs of the text gradient, the next site
         # fused attention (csrc/flash_attn.hip) for the transformer blocks; False: batched GEMMs + row softmax with the
