@@ -82,7 +82,8 @@ F32_SAME = {"siss_zero_ranges", "siss_upsample_phase_wgrad_fold", "siss_timestep
             "siss_ssd_ratio", "siss_ssd_dampen",
             "siss_sscd_topk", "siss_sscd_count_above", "siss_sscd_fill_above",
             "siss_feat_sqnorm", "siss_feat_knn_radius", "siss_feat_ball_stats", "siss_kid_sums",
-            "siss_jl_project"}
+            "siss_jl_project",
+            "siss_mia_gather", "siss_mia_transfer", "siss_mia_transfer_sqerr", "siss_mia_powdiff"}
 for _b, _f in F32_ENTRY.items():          # the header's promise "same argument lists", checked once instead of assumed
     if SIGNATURES[_b] != SIGNATURES[_f]:
         raise TypeError(f"{_f} does not have the argument types of {_b} in {HEADER}")

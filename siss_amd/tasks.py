@@ -722,10 +722,13 @@ class _DeleteBase(Task):
     def check_metrics(self):
         """Refuse, before the first step, a metrics block that cannot run (a host-side check: no GPU needed)."""
         self.check_membership()
+        self.mia = self.check_mia()
         self.injection = self.check_injection_score()
         self.replication = self.check_sscd_nn()
 
     membership_supported = True
+    mia_supported = True        # metrics.mia: the pixel-space tasks (no latent-space form of the attacks is built)
+    mia = None                  # metrics.mia: its settings (check_mia), None when not configured
     injection = None            # the injection check's scorer / settings (check_injection_score), None when not configured
     replication = None          # metrics.sscd_nn: its settings (check_sscd_nn) until the index is there (open_replication), then the tracker
 
@@ -861,6 +864,62 @@ class _DeleteBase(Task):
         out = os.path.join(cfg.output_dir, "membership_rank0.jsonl")
         return int(ml.step_frequency), lambda global_step: log_membership(metric, timesteps, global_step, out)
 
+    def check_mia(self, in_loop=True):
+        """metrics.mia (OPT-IN, absent from the repo's configs): {attacks, step_frequency, num_members, num_forget, batch_size,
+        holdout: {path, limit}, fpr, secmi, pia, loss, seed} -- membership inference attacks (siss_amd/mia.py) on members drawn from
+        the keep dataset, the forget images and holdout images the model never saw.  Refused here, before the UNet is loaded: a task
+        without a pixel-space UNet, an unknown field or attack, a timestep outside [0, num_train_timesteps), a holdout path that is not
+        on disk.  Returns the settings, or None.  in_loop=False (tools/mia.py: one evaluation outside a run): step_frequency is not
+        needed and an absent key means the defaults."""
+        cfg = self.cfg
+        metrics = cfg.get("metrics") or {}
+        if metrics.get("mia") is None:
+            if in_loop:
+                return None
+            metrics = {"mia": {}}
+        if not self.mia_supported:
+            raise NotImplementedError("metrics.mia: the membership inference attacks are built for the pixel-space tasks (DeleteCeleb, "
+                                      "DeleteTShirt) only -- no latent-space form of SecMI / PIA is built")
+        from .mia import parse_config
+        T = int((cfg.get("scheduler") or {}).get("num_train_timesteps", 1000))
+        settings = parse_config(hydra_lite._plain(metrics.get("mia")), T, need_frequency=in_loop)
+        ho = settings["holdout"]
+        if ho is not None and ho["path"] is None and not cfg.get("allow_synthetic"):
+            raise ValueError("metrics.mia.holdout.path is needed: a directory of images, or an .npz, the model never trained on "
+                             "(allow_synthetic=true: synthetic stand-ins; holdout=null: score means only)")
+        if ho is not None and ho["path"] is not None and not os.path.exists(ho["path"]):
+            raise FileNotFoundError(f"metrics.mia.holdout.path {ho['path']!r} is not on disk")
+        return settings
+
+    def mia_evaluation(self, unet, sched, ds_all, ds_del, device, path):
+        """The MiaEvaluation of the checked settings: the members (num_members keep indices from a generator of their own, seeded with
+        metrics.mia.seed), the forget images (each dataset index once, up to num_forget) and the holdout images, drawn ONCE, here.  No
+        stream of the loop and no global generator is touched."""
+        from . import mia
+        cfg, s = self.cfg, self.mia
+        attack = mia.MembershipAttack(unet, sched, device, attacks=s["attacks"], batch_size=s["batch_size"], **s["settings"])
+        stack = lambda ds, idx: torch.stack([ds[i] for i in idx]).float()
+        members = stack(ds_all, mia.draw_members(len(ds_all), s["num_members"], s["seed"]))
+        forget = stack(ds_del, mia.unique_in_order(range(len(ds_del)))[:s["num_forget"]])
+        ho, holdout = s["holdout"], None
+        if ho is not None and ho["path"] is not None:
+            transform = hydra_lite.instantiate(cfg.transform) if cfg.get("transform") is not None else None
+            holdout = mia.load_holdout(ho["path"], ho["limit"], transform, int(members.shape[1]))
+            if tuple(holdout.shape[1:]) != tuple(members.shape[1:]):
+                raise ValueError(f"metrics.mia.holdout: images of shape {tuple(holdout.shape[1:])}, the task's are {tuple(members.shape[1:])}")
+        elif ho is not None:
+            print(f"[siss_amd] metrics.mia: allow_synthetic and no holdout.path -- {ho['limit']} SYNTHETIC holdout images")
+            holdout = stack(SyntheticImages(ho["limit"], tuple(members.shape[1:]), seed=3 + s["seed"]), range(ho["limit"]))
+        return mia.MiaEvaluation(attack, members, forget, holdout, s["fpr"], s["seed"], path)
+
+    def mia_metric(self, unet, sched, ds_all, ds_del, device):
+        """`metrics.mia`: None when not configured, else (step_frequency, evaluate(global_step)); each evaluation appends one record to
+        mia_rank0.jsonl (mia.MiaEvaluation)."""
+        if self.mia is None:
+            return None
+        out = os.path.join(self.cfg.output_dir, "mia_rank0.jsonl")
+        return int(self.mia["step_frequency"]), self.mia_evaluation(unet, sched, ds_all, ds_del, device, out)
+
     def deletion_metrics(self, unet, sched, forget_image, device):
         """The tracker of the configured deletion metrics (a callable of global_step), or None: none here."""
         return None
@@ -876,6 +935,7 @@ class _DeleteBase(Task):
         tracker = self.deletion_metrics(unet, sched, ds_del[0], device)
         yield None if tracker is None else (1, tracker)
         yield self.membership_metric(unet, sched, ds_all, ds_del, device)
+        yield self.mia_metric(unet, sched, ds_all, ds_del, device)
 
     def fill_cfg(self):
         """Placeholders of the config that are read from files before anything else (delete_sd.py:342-348): none here."""
@@ -1188,6 +1248,7 @@ class DeleteSD(_DeleteBase):
     default_unet = staticmethod(UNet2DConditionConfig.sd15)
     VAE_SCALE = 0.18215            # vae.config.scaling_factor (delete_sd.py:883,888)
     membership_supported = False   # (delete_sd.py has no membership loss)
+    mia_supported = False          # (metrics.mia: no latent-space form of the attacks is built)
     vae = None
     text_encoder = None
 
@@ -1807,6 +1868,9 @@ class TrainUnconditional(Task):
         if (cfg.get("deletion") or {}).get("ssd") is not None:
             raise NotImplementedError("deletion.ssd: Selective Synaptic Dampening belongs to the unlearning tasks (delete_celeb / "
                                       "delete_tshirt / delete_sd); the pre-training task has no forget set to dampen for")
+        if (cfg.get("metrics") or {}).get("mia") is not None:
+            raise NotImplementedError("metrics.mia: the membership inference attacks belong to the pixel-space unlearning tasks "
+                                      "(delete_celeb / delete_tshirt); the pre-training task has no forget set to place among holdout images")
 
     def dataset(self, shape):
         cfg = self.cfg

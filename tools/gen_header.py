@@ -22,6 +22,7 @@ DOCS = {
     'transformer.hip': "Token-space pieces of the SD UNet's Transformer2DModel (diffusers BasicTransformerBlock: LayerNorm,\n * GEGLU feed-forward, multi-head self / cross attention reshapes and softmax).  Call site: delete_sd.py:977-985\n * -> losses/ddpm_deletion_loss.py:24 with conditioning['encoder_hidden_states'].",
     'likelihood.hip': "The forget-set likelihood metric (metrics/likelihood.py + metrics/song_likelihood of the reference): the probability-flow\n * drift of the VP-SDE with its Hutchinson divergence (get_div_fn) and the f64 stage / error-norm arithmetic of scipy's RK45\n * (solve_ivp) over the joint state [x ; delta log p].",
     'membership.hip': "The membership-loss metric (metrics/class_membership.py of the reference, MembershipLoss.compute_membership_losses):\n * the (image, noise, timestep) work items of an evaluation noised straight into the forward's input and their squared errors\n * summed per pair, both driven by one device index table -- replaces the three expanded I x J tensors, add_noise x2 and\n * torch.sum((out - noise) ** 2) of :77-110.",
+    'mia.hip': "Opt-in membership inference attacks (siss_amd/mia.py, `metrics.mia`, tools/mia.py; SecMI, Duan et al., ICML 2023; PIA,\n * Kong et al., ICLR 2024; NOT the reference's protocol, whose only membership evidence is the mean eps-MSE above): the element-wise\n * passes between the forwards of a deterministic DDIM chain over the rows of one image pool -- the gather of a batch, the transfer\n * y = cx x + ce e, SecMI's last transfer fused with its squared t-error, PIA's |e0 - e1|^p; explicit f32 round-to-nearest operations,\n * one f64 partial per (row, block) folded in index order, no atomics.",
     'kmeans.hip': "The SD deletion fraction (delete_sd.py:224-225,:269-275: joblib's scikit-learn KMeans.predict on 255 * ToTensor(PIL) of the\n * validation images, on the CPU) and the fit that produces that classifier: the decoder's output to uint8 with its distances to the\n * centres in one pass, Lloyd's assignment and update over uint8 rows; f64 / integer sums in fixed orders, no atomics.",
     'metric_conv.hip': "What the four f32 metric networks share (the MNIST ResNet-18 of metrics/mnist_resnet.py, the FID Inception-v3, the SSCD\n * ResNet-50 and the CLIP RN50 image tower; siss_amd/metric_net.py): one implicit-GEMM convolution for every layer, fc and projection\n * (NHWC gather with zero fill, or the NCHW image; independent KH / KW / padding; folded-BN bias, optional residual, optional ReLU,\n * written into a channel slice; deterministic split-K) and the 3 x 3 max pool.",
     'metric_train.hip': "Training of the MNIST ResNet-18 metric classifier (notebooks/cnn-resnet18-mnist.ipynb of the reference: train-mode\n * BatchNorm, F.cross_entropy, autograd, torch.optim.Adam; siss_amd/classifier_train.py), f32: the convolution's data and weight\n * gradients on the packed weights of siss_metric_conv above, batch-statistics BatchNorm forward / backward, the 3 x 3 / 2 max pool's\n * backward and softmax cross-entropy; sums in f64 or in fixed orders, no atomics.",
@@ -45,7 +46,7 @@ DOCS = {
     'timeemb.hip': "Sinusoidal timestep embedding (diffusers Timesteps/get_timestep_embedding), TimestepEmbedding MLP and\n * ResnetBlock2D.time_emb_proj linears (M = batch rows), forward and backward.",
 }
 ORDER = ['siss_loss.hip', 'gemm_nt.hip', 'gemm_tn.hip', 'groupnorm.hip', 'conv_small.hip', 'attention.hip', 'attn1h.hip', 'flash_attn.hip', 'transformer.hip',
-         'timeemb.hip', 'elementwise.hip', 'optimizer.hip', 'train_state.hip', 'likelihood.hip', 'membership.hip', 'metric_conv.hip', 'metric_train.hip', 'inception.hip', 'kmeans.hip', 'sscd.hip', 'clip_iqa.hip', 'prompt_grad.hip', 'injection.hip', 'dpm_solver.hip', 'latent_cache.hip', 'image_store.hip', 'lora.hip', 'saliency.hip', 'ewc.hip', 'surgery.hip', 'teacher.hip', 'ssd.hip', 'sscd_search.hip', 'feature_sets.hip', 'attribution.hip', 'f32_path.hip']
+         'timeemb.hip', 'elementwise.hip', 'optimizer.hip', 'train_state.hip', 'likelihood.hip', 'membership.hip', 'mia.hip', 'metric_conv.hip', 'metric_train.hip', 'inception.hip', 'kmeans.hip', 'sscd.hip', 'clip_iqa.hip', 'prompt_grad.hip', 'injection.hip', 'dpm_solver.hip', 'latent_cache.hip', 'image_store.hip', 'lora.hip', 'saliency.hip', 'ewc.hip', 'surgery.hip', 'teacher.hip', 'ssd.hip', 'sscd_search.hip', 'feature_sets.hip', 'attribution.hip', 'f32_path.hip']
 HEAD = '''/* siss_hip.h -- C ABI of libsiss_hip.so: the MI355X (gfx950) kernels of the SISS unlearning step.
  *
  * GENERATED by tools/gen_header.py from the .hip sources under siss_amd/csrc -- edit the sources, then regenerate.
