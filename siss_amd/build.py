@@ -19,12 +19,12 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 # classifier's uint8 image, the SSCD preprocessing, the prompt embedding's AdamW, the img2img starting latents, the
 # latent cache's sampling launch, the image store's table gather, the single-set update with its EMA, the DPM-Solver++ step and its
 # noise norms, the masked AdamW pair, the SSCD search's similarities, the Fisher accumulation and the anchor fold, the
-# SSD ratio and dampening, the gradient surgery's sums, coefficients and update, the feature sets' distances and kernel sums, the teacher target's
+# SSD ratio and dampening, the UCE increments and their add, the gradient surgery's sums, coefficients and update, the feature sets' distances and kernel sums, the teacher target's
 # cotangent and the weighted pass 1, the DDIM transfers of the membership attacks) must not
 # contract a*b+c into fma
 EXACT = {"siss_loss.hip", "optimizer.hip", "train_state.hip", "likelihood.hip", "membership.hip", "kmeans.hip", "sscd.hip", "prompt_grad.hip",
          "injection.hip", "latent_cache.hip", "image_store.hip", "dpm_solver.hip", "saliency.hip", "sscd_search.hip", "ewc.hip", "ssd.hip",
-         "surgery.hip", "feature_sets.hip", "teacher.hip", "mia.hip"}
+         "surgery.hip", "feature_sets.hip", "teacher.hip", "mia.hip", "uce.hip"}
 # per-file extras.  flash_attn.hip: MFMA results straight into VGPRs -- the softmax arithmetic consumes every accumulator of every
 # tile, and with the default (AGPR destinations) each one cost a v_accvgpr_read in loops that are VALU-bound (832 -> 10 in the file);
 # no SLP vectoriser: it pairs the softmax arithmetic into v_pk_*_f32 (526 in the file), which cost more issue slots beside MFMAs than

@@ -80,6 +80,7 @@ F32_SAME = {"siss_zero_ranges", "siss_upsample_phase_wgrad_fold", "siss_timestep
             "siss_grad_norms_scale_surgery", "siss_recombine_clip_adamw_surgery",
             "siss_teacher_seed", "siss_grad_norms_weighted",
             "siss_ssd_ratio", "siss_ssd_dampen",
+            "siss_uce_delta", "siss_uce_apply",
             "siss_sscd_topk", "siss_sscd_count_above", "siss_sscd_fill_above",
             "siss_feat_sqnorm", "siss_feat_knn_radius", "siss_feat_ball_stats", "siss_kid_sums",
             "siss_jl_project",

@@ -304,6 +304,10 @@ class _DeleteBase(Task):
         if sc is not None:
             from .ssd import select_targets as ssd_targets
             ssd_targets(self.unet_param_names(), sc.targets)
+        # deletion.uce: a task without cross-attention, a malformed mapping, an unknown field, a missing or empty edit list, a value out of
+        # range, a target that matches nothing or is no [*, cross_attention_dim] matrix, a prompt that cannot be embedded and the key
+        # together with deletion.lora are settled here
+        self.uce_check()
         # deletion.trainable: a malformed entry, an entry that matches no parameter of the configured UNet and a selection of every
         # parameter (said, then the full update) are settled here, from the parameter names the configuration implies
         from .trainable import select
@@ -379,6 +383,26 @@ class _DeleteBase(Task):
         if sc is not None:
             check_loss(d.get("loss_fn"))
         return sc
+
+    # -- deletion.uce: null | {edit, preserve, preserve_file, lambda, edit_scale, preserve_scale, targets, path} (OPT-IN; siss_amd/uce.py) ----
+    uce_refusal = "no cross-attention: this task's UNet takes no prompt, and the edit rewrites the key / value projections of one"
+
+    def uce_config(self):
+        """The parsed deletion.uce (siss_amd.uce.UCEConfig), or None (absent / null: no edit, today's run).  The task says in
+        `uce_refusal` why it does not take the key (None: it does -- delete_sd)."""
+        from .uce import KEY, parse_uce
+        d = self.cfg.get("deletion") or {}
+        if d.get("uce") is None:
+            return None
+        if self.uce_refusal is not None:
+            raise NotImplementedError(f"{KEY}: {self.uce_refusal} (Unified Concept Editing belongs to delete_sd)")
+        return parse_uce(d.get("uce"), lora=d.get("lora"))
+
+    def uce_check(self):
+        self.uce_config()
+
+    def uce_edit(self, stepper, device, rank, world, pg):
+        return None
 
     # -- deletion.ssd: null | {alpha, fraction, lambda, keep_batches, forget_batches, batch_size, seed, targets, path} (OPT-IN; siss_amd/ssd.py)
     def ssd_config(self):
@@ -983,6 +1007,7 @@ class _DeleteBase(Task):
         n_steps = int(cfg.training_steps) * max(1, len(d.get("img_name") or [1]))
         cond = self.conditioning(B, device)
         os.makedirs(cfg.output_dir, exist_ok=True)
+        uce_fields = self.uce_edit(stepper, device, rank, world, pg)      # (before deletion.ssd: its Fishers are the edited model's)
         ssd_fields = self.ssd_dampen(stepper, ds_all, ds_del, B, cond, device, rank, world, pg)
         saliency = self.saliency_mask(stepper, ds_del, B, cond, device, rank, world, pg)
         if saliency is not None:
@@ -1005,6 +1030,8 @@ class _DeleteBase(Task):
             st = handle.get()
             st["global_step"], st["lr"], st["elapsed_s"] = meta          # (elapsed: stamped when the step was queued)
             st.update(stepper.log_fields())         # (the parameters the optimizer updates and the active variant's own fields)
+            if uce_fields is not None:
+                st.update(uce_fields)
             if ssd_fields is not None:
                 st.update(ssd_fields)
             return st
@@ -1367,6 +1394,114 @@ class DeleteSD(_DeleteBase):
             raise FileNotFoundError("deletion.teacher (forget: esd) needs the empty prompt's embedding: no text_encoder/ in the checkpoint "
                                     "directory (pass allow_synthetic=true for a synthetic one)")
         return tc
+
+    uce_refusal = None          # deletion.uce is this task's: the cross-attention projections and the prompts are here
+
+    def _cross_dim(self):
+        return int(self.unet_config().cross_attention_dim)
+
+    def uce_check(self):
+        uc = self.uce_config()
+        if uc is None:
+            return
+        from .uce import KEY, check_targets, select_targets
+        specs = self.unet_param_specs()
+        check_targets(specs, select_targets(list(specs), uc.targets), self._cross_dim())
+        path = str(self.cfg.get("pretrained_model_name_or_path") or "")
+        for i, (p, t) in enumerate(uc.edit):
+            self._check_embeddable(p, f"{KEY}.edit[{i}].prompt")
+            if t is not None:
+                self._check_embeddable(t, f"{KEY}.edit[{i}].target")
+            elif not (os.path.isdir(os.path.join(path, "text_encoder")) or self.cfg.get("allow_synthetic")):
+                raise FileNotFoundError(f"{KEY}.edit[{i}].target=null needs the empty prompt's embedding: no text_encoder/ in the "
+                                        "checkpoint directory (pass allow_synthetic=true for a synthetic one)")
+        for i, p in enumerate(uc.preserved_prompts()):
+            self._check_embeddable(p, f"{KEY}.preserve[{i}]")
+
+    def uce_rows(self, uc, device):
+        """(C_e, C_t, C_p) [rows, X] of the parsed key: every token row of every prompt's embedding.  Synthetic embeddings
+        (allow_synthetic) are seeded seed() + 16 + i, i running over the edit sources, their destinations and the preserved prompts, so
+        that distinct prompts get distinct rows; a null destination is the empty prompt's embedding."""
+        X = self._cross_dim()
+        pres = uc.preserved_prompts()
+        n = len(uc.edit)
+        src = [self._prompt_embedding(p, device, synthetic_seed=16 + i) for i, (p, _) in enumerate(uc.edit)]
+        dst = [self._empty_prompt_embedding(device, "deletion.uce (target: null)") if t is None
+               else self._prompt_embedding(t, device, synthetic_seed=16 + n + i) for i, (_, t) in enumerate(uc.edit)]
+        keep = [self._prompt_embedding(p, device, synthetic_seed=16 + 2 * n + i) for i, p in enumerate(pres)]
+        for i, (a, b) in enumerate(zip(src, dst)):
+            if a.shape != b.shape or a.shape[-1] != X:
+                raise ValueError(f"deletion.uce.edit[{i}]: the prompt embeds to {tuple(a.shape)}, its destination to {tuple(b.shape)}; both "
+                                 f"must be [1, L, {X}] with one L")
+        rows = lambda es: torch.cat([e.reshape(-1, X) for e in es]).double().cpu() if es else torch.zeros(0, X, dtype=torch.float64)
+        return rows(src), rows(dst), rows(keep), pres
+
+    def uce_edit(self, stepper, device, rank, world, pg):
+        """Unified Concept Editing of the run (None without the key), once, at the weights the run loaded -- after the teacher took its
+        copy, before deletion.ssd, the mask, the anchor and the step-0 metrics: the edit loaded from `path` when both files are there
+        (a foreign X or other embeddings are refused by field), else built from the prompts' embeddings; then the two launches, the
+        statistics and the residuals.  More than one rank: rank 0 alone builds or loads the edit, the ranks agree on success, E is
+        broadcast, every rank applies and compares the bits of its sum of delta^2 with rank 0's.  Rank 0 writes the two files into
+        output_dir.  Returns the fields every train-log line carries."""
+        uc = self.uce_config()
+        if uc is None:
+            return None
+        import struct
+        from . import uce
+        eng = stepper.e
+        X = self._cross_dim()
+        out = str(self.cfg.output_dir)
+        names = uce.check_targets(eng.ps.specs, uce.select_targets(list(eng.ps.specs), uc.targets), X)
+        rows = {}
+
+        def build():
+            Ce, Ct, Cp, pres = rows["all"] = self.uce_rows(uc, device)
+            if uc.path is not None and uce.present(uc.path):
+                ed = uce.load(uc.path, X)
+                digest = uce.embeddings_digest(X, Ce.numpy(), Ct.numpy(), Cp.numpy())
+                if ed.digest != digest:
+                    raise ValueError(f"{os.path.join(uc.path, uce.CONFIG_FILE)}: embeddings = {ed.digest!r}, this run's prompts embed to "
+                                     f"{digest!r} -- the edit was computed for other prompts or another text encoder")
+                print(f"[siss_amd] deletion.uce: edit loaded from {uc.path}")
+            else:
+                if uc.path is not None:
+                    print(f"[siss_amd] deletion.uce.path {uc.path!r} holds no edit files: computing the edit")
+                ed = uce.edit_matrix(Ce, Ct, Cp, uc.lam, uc.edit_scale, uc.preserve_scale)
+            ed.E_dev = torch.from_numpy(ed.E).to(device)
+            return ed
+
+        def empty(c):
+            import numpy as np
+            ed = uce.UCEEdit(np.zeros((X, X), np.float32), None, None, c["edit_rows"], c["preserve_rows"], c["lambda"], c["edit_scale"],
+                             c["preserve_scale"], c["cond"], digest=c["embeddings"], source=c["source"])
+            ed.E_dev = torch.zeros(X, X, dtype=torch.float32, device=device)
+            return ed
+
+        ed = _built_on_rank0("deletion.uce: rank 0 could not build the edit", build, uce.UCEEdit.config, empty, lambda ed: ed.E_dev,
+                             out, rank, world, pg)
+        before = None
+        if rank == 0:
+            Ce, Ct, Cp, pres = rows["all"]
+            before = uce.values_before(eng, names, Ct, Cp)
+        stats = uce.apply(eng, ed, names, apply=True)
+        if world > 1:
+            import torch.distributed as dist
+            mine = struct.unpack("<Q", struct.pack("<d", stats["sum_delta2"]))[0]
+            word = [mine if rank == 0 else None]
+            dist.broadcast_object_list(word, src=0, group=pg)
+            if word[0] != mine:
+                raise RuntimeError(f"deletion.uce: rank {rank}'s sum of delta^2 has the bits {mine:#018x}, rank 0's {word[0]:#018x}")
+        if rank == 0:
+            res = uce.residuals(eng, names, before, Ce, Cp)
+            ed.save_report(out, dict(config=uc.as_dict(), edit_prompts=[p for p, _ in uc.edit], edit_targets=[t for _, t in uc.edit],
+                                     preserved_prompts=pres, targets=names, stats=stats, residuals=res))
+            drift = res["preserve_drift"]
+            print(f"[siss_amd] deletion.uce: {len(uc.edit)} edit(s) over {ed.n_edit} rows, {len(pres)} preserved prompt(s) over "
+                  f"{ed.n_preserve} rows, lambda {uc.lam:g}, cond(M) {ed.cond:.4g}; {len(names)} tensors, {stats['floats']} floats, "
+                  f"relative change {stats['relative_change']:.6g}, edit residual {res['edit_residual']:.6g}, preserve drift "
+                  f"{'none' if drift is None else format(drift, '.6g')}")
+        return dict(uce_edits=len(uc.edit), uce_preserved=len(uc.preserved_prompts()), uce_lambda=uc.lam,
+                    uce_relative_change=stats["relative_change"])
 
     def _check_embeddable(self, p, key):
         """_prompt_embedding's rules, from the disk alone (check_supported runs before anything is loaded)."""
@@ -1868,6 +2003,9 @@ class TrainUnconditional(Task):
         if (cfg.get("deletion") or {}).get("ssd") is not None:
             raise NotImplementedError("deletion.ssd: Selective Synaptic Dampening belongs to the unlearning tasks (delete_celeb / "
                                       "delete_tshirt / delete_sd); the pre-training task has no forget set to dampen for")
+        if (cfg.get("deletion") or {}).get("uce") is not None:
+            raise NotImplementedError("deletion.uce: no cross-attention: the pre-training task's UNet takes no prompt (Unified Concept "
+                                      "Editing belongs to the unlearning task delete_sd)")
         if (cfg.get("metrics") or {}).get("mia") is not None:
             raise NotImplementedError("metrics.mia: the membership inference attacks belong to the pixel-space unlearning tasks "
                                       "(delete_celeb / delete_tshirt); the pre-training task has no forget set to place among holdout images")

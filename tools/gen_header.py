@@ -40,13 +40,14 @@ DOCS = {
     'surgery.hip': "Opt-in gradient surgery between the keep and forget gradients (siss_amd/surgery.py, `deletion.surgery`; PCGrad, Yu et al.,\n * NeurIPS 2020; gradient-projection unlearning, Hoang et al., WACV 2024; the restricted gradient of Ko et al., NeurIPS 2024; no counterpart\n * in the reference, whose update is g_x - s g_a whatever the sign of <g_x, g_a>): a deterministic segmented reduction of the three sums\n * per group of the flat buffer (the whole buffer, or one parameter tensor), the per-group coefficient table (cx, ca) of the projected\n * pair, and pass 2 of optimizer.hip recombining with it; f64 sums in fixed orders that do not depend on the grid, explicit f32\n * round-to-nearest operations, no atomics.",
     'teacher.hip': "Opt-in teacher-target unlearning (siss_amd/teacher.py, `deletion.loss_fn=teacher_target` with `deletion.teacher`; ESD, Gandikota\n * et al., ICCV 2023, and Concept Ablation, Kumari et al., ICCV 2023; NOT the reference's protocol, whose objectives regress onto the drawn\n * noise): the regression target from a frozen teacher's outputs with the cotangent of the student's stacked rows and the per-row loss sums\n * in one launch, and pass 1 of optimizer.hip with the scaling factor fixed at -weight (a plain weighted sum of the two gradient sets);\n * explicit f32 round-to-nearest operations, f64 sums in fixed orders that do not depend on the grid, no atomics.",
     'ssd.hip': "Opt-in Selective Synaptic Dampening (siss_amd/ssd.py, `deletion.ssd`; Foster, Schoepf & Brintrup, AAAI 2024; no counterpart in\n * the reference, whose runs unlearn by gradient steps only): the ratio of the forget set's empirical Fisher to the keep data's per\n * weight, and ONE streaming pass that selects the weights whose ratio lies above a threshold, scales them by min(lambda / ratio, 1)\n * and reports what it did; explicit f32 round-to-nearest operations, exact counts, f64 sums in fixed orders, no atomics.",
+    'uce.hip': "Opt-in Unified Concept Editing of the SD UNet (siss_amd/uce.py, `deletion.uce`; Gandikota, Orgad, Belinkov, Materzynska\\n * & Bau, WACV 2024; no counterpart in the reference, whose runs unlearn by gradient steps only): the closed-form edit W' = W + W dT of\\n * the cross-attention key / value projections, dT ONE X x X matrix for every edited weight (formed in f64 on the host): the increments\\n * of all targets in one launch over a host job table (exact f32 on v_mfma_f32_16x16x4_f32, the tile of sscd_search.hip), and ONE f32\\n * add over the targets' floats that reports what it did; f64 sums in fixed orders, no atomics.",
     'sscd_search.hip': "Dataset-wide SSCD copy search (siss_amd/sscd_search.py, `metrics.sscd_nn`, tools/find_copies.py; notebooks/sscd.ipynb of the\n * reference: embed a directory, form ALL pairwise similarities on the host, list what lies above a threshold): many unit-row queries\n * against a gallery of N unit rows, keeping per query the best k or the rows at or above a threshold; the nq x N matrix is never formed and\n * no similarity travels to the host.  Exact f32 on v_mfma_f32_16x16x4_f32, one value per pair whatever the entry point, no atomics.",
     'feature_sets.hip': "Pairwise work on feature sets (siss_amd/feature_sets.py, `metrics.fid.sets`; torchmetrics' KernelInceptionDistance,\n * Binkowski et al. 2018, and precision / recall / density / coverage, Kynkaanniemi et al. 2019, Naeem et al. 2020, on the [N, 2048]\n * features the FID's Inception-v3 already produces; NOT the reference's protocol, which reports FID only): squared norms, k-th-neighbour\n * radii, ball membership counts with the nearest row, and the cubic polynomial-kernel sums of all subsets in one launch; no N x M matrix\n * is formed.  Exact f32 on v_mfma_f32_16x16x4_f32 (the tile of sscd_search.hip), one distance per pair whatever the entry point,\n * f64 kernel sums in fixed orders, no atomics.",
     'attribution.hip': "Gradient-feature data attribution (siss_amd/attribution.py, tools/attribute.py; TRAK, Park et al., ICML 2023; D-TRAK, Zheng\n * et al., ICLR 2024; NOT the reference's protocol, which has no attribution step): the dense Rademacher projection of the whole flat\n * gradient buffer (or of listed stretches of it) to k dimensions, the n x k sign matrix defined by a counter hash and never in memory;\n * one f32 partial per chunk and column, chunks folded in f64 in a fixed order, no atomics.",
     'timeemb.hip': "Sinusoidal timestep embedding (diffusers Timesteps/get_timestep_embedding), TimestepEmbedding MLP and\n * ResnetBlock2D.time_emb_proj linears (M = batch rows), forward and backward.",
 }
 ORDER = ['siss_loss.hip', 'gemm_nt.hip', 'gemm_tn.hip', 'groupnorm.hip', 'conv_small.hip', 'attention.hip', 'attn1h.hip', 'flash_attn.hip', 'transformer.hip',
-         'timeemb.hip', 'elementwise.hip', 'optimizer.hip', 'train_state.hip', 'likelihood.hip', 'membership.hip', 'mia.hip', 'metric_conv.hip', 'metric_train.hip', 'inception.hip', 'kmeans.hip', 'sscd.hip', 'clip_iqa.hip', 'prompt_grad.hip', 'injection.hip', 'dpm_solver.hip', 'latent_cache.hip', 'image_store.hip', 'lora.hip', 'saliency.hip', 'ewc.hip', 'surgery.hip', 'teacher.hip', 'ssd.hip', 'sscd_search.hip', 'feature_sets.hip', 'attribution.hip', 'f32_path.hip']
+         'timeemb.hip', 'elementwise.hip', 'optimizer.hip', 'train_state.hip', 'likelihood.hip', 'membership.hip', 'mia.hip', 'metric_conv.hip', 'metric_train.hip', 'inception.hip', 'kmeans.hip', 'sscd.hip', 'clip_iqa.hip', 'prompt_grad.hip', 'injection.hip', 'dpm_solver.hip', 'latent_cache.hip', 'image_store.hip', 'lora.hip', 'saliency.hip', 'ewc.hip', 'surgery.hip', 'teacher.hip', 'ssd.hip', 'uce.hip', 'sscd_search.hip', 'feature_sets.hip', 'attribution.hip', 'f32_path.hip']
 HEAD = '''/* siss_hip.h -- C ABI of libsiss_hip.so: the MI355X (gfx950) kernels of the SISS unlearning step.
  *
  * GENERATED by tools/gen_header.py from the .hip sources under siss_amd/csrc -- edit the sources, then regenerate.
